@@ -23,7 +23,13 @@ N_splats * n_gpus / step time.  Two exchange patterns compute that batch (--dp-m
   auto      (default) times a few untimed steps of both and runs the faster one; the choice and
             both calibration timings are reported in the JSON line.
 
-The JSON line carries two extra objects:
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, W warm-up steps, --ramp-s
+seconds of untimed steps (the GPU reaches its sustained clocks), exactly K timed steps between device synchronisations, and the JSON
+line (metric, value, unit, ms_per_step = the K steps' wall time / K, ...).  --dump-outputs DIR additionally writes what the
+last timed step computed (see dump_outputs).  Everything below is measured only with --full, which also repeats the timed
+region until --min-timed-s has been measured (ms_per_step is then the mean over all regions).
+
+With --full, the JSON line carries two extra objects:
   roofline      the dominant kernel (largest average time per step among the C-ABI entry
                 points, timed live with HIP events on the launch stream inside the timed
                 region): algorithmic bytes / average
@@ -37,6 +43,7 @@ peak_mem_gb / step_mem_gb (the reference protocol's Mem column), ms_per_step_den
 with a dense [C,H,W,3] image gradient instead of the protocol's broadcast one), psnr_vs_oracle (config 1).
 """
 import argparse
+import contextlib
 import gc
 import json
 import os
@@ -135,14 +142,20 @@ def parse():
     ap.add_argument("--ada-mask", action="store_true",
                     help="with --quantize: the learnable shN mask of the reference's compression benchmark (--shN_ada_mask_opt, "
                          "examples/benchmarks/compression/mcmc_tt_sim.sh:31-33) active in the hooks")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: the cold-protocol region, the per-entry-point pass and the "
+                         "roofline, repeated timed regions (--min-timed-s), the dense-gradient variants, the config-1 PSNR, the "
+                         "multi-GPU projection and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MiB; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-scene-grid", type=int, default=0,
                     help="scene_grid of the cpu_baseline sample (0 = the bench scene itself: ~3 s per pass on 128 threads)")
     ap.add_argument("--min-timed-s", type=float, default=0.5,
-                    help="the exactly-K-step timed region is repeated until this much time has been measured")
+                    help="with --full: the exactly-K-step timed region is repeated until this much time has been measured")
     ap.add_argument("--ramp-s", type=float, default=0.6,
                     help="untimed back-to-back steps for this long right before the timed regions (GPU clocks reach their sustained level)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the dense-image-gradient variant and the config-1 PSNR")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the dense-image-gradient variant and the config-1 PSNR")
     ap.add_argument("--breakdown", action="store_true", help="print per-entry-point timings to stderr")
     ap.add_argument("--dp-mode", choices=["auto", "camera", "camera_sparse", "gaussian", "gaussian_dense"], default="auto",
                     help="multi-GPU exchange pattern (see the module docstring); ignored with one GPU")
@@ -162,7 +175,7 @@ def parse():
     ap.add_argument("--dynamic-order", choices=["shuffle", "morton"], default="shuffle",
                     help="memory order of the dynamic splats: a seeded shuffle (default, what a trained scene looks like) or a Z-order curve")
     ap.add_argument("--no-dp-projection", action="store_true",
-                    help="(one GPU) skip the multi-GPU projection: the exchange modes re-timed on this GPU with their collectives "
+                    help="(one GPU, with --full) skip the multi-GPU projection: the exchange modes re-timed on this GPU with their collectives "
                          "forced through RCCL (world 1), next to the bytes a world-8 run would put on the xGMI links")
     return ap.parse_args()
 
@@ -199,6 +212,55 @@ class CallTimer:
     def totals_ms(self):
         torch.cuda.synchronize()
         return {k: [a.elapsed_time(b) for a, b in v] for k, v in self.events.items()}
+
+
+DUMP_IMAGE_BYTES = 24 * 2**20  # a larger image is written as a seeded sample of its pixels, [n, channels]
+DUMP_SPLAT_ROWS = 1 << 15      # per-splat arrays: a seeded sample of this many splats (the same rows in every array)
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def _seeded_rows(n, k, seed):
+    if n <= k:
+        return None
+    return torch.from_numpy(np.sort(np.random.RandomState(seed).choice(n, k, replace=False)))
+
+
+def dump_outputs(out_dir, images, per_splat):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy in float32 (float64 stays float64).
+    images: name -> [..., channels] tensor, written whole up to DUMP_IMAGE_BYTES, else as a seeded sample of its pixels.
+    per_splat: name -> (tensor, splat axis), written as the DUMP_SPLAT_ROWS seeded splat rows along that axis.  The inputs of
+    the bench are seeded too, so two builds run with the same arguments can be compared file by file."""
+    arrays = {}
+    for name, t in images.items():
+        t = t.detach()
+        if t.numel() * 4 > DUMP_IMAGE_BYTES:
+            t = t.reshape(-1, t.shape[-1])
+            t = t[_seeded_rows(t.shape[0], DUMP_IMAGE_BYTES // (4 * t.shape[-1]), 1).to(t.device)]
+        arrays[name] = t
+    for name, (t, axis) in per_splat.items():
+        rows = _seeded_rows(t.shape[axis], DUMP_SPLAT_ROWS, 2)
+        arrays[name] = t.detach() if rows is None else t.detach().index_select(axis, rows.to(t.device))
+    arrays = {k: (v if v.dtype == torch.float64 else v.float()).cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
+def splat_outputs(params, meta):
+    """The per-splat arrays a step hands its caller, for dump_outputs: the parameter gradients and the projection's radii,
+    means2d, depths and conics.  The projection leaves the last three unwritten for culled splats (radius 0): zeroed here, so
+    that only values the step computed are compared."""
+    out = {f"{k}_grad": (p.grad, 0) for k, p in params.items() if p.grad is not None}
+    radii = meta["radii"]
+    out["radii"] = (radii, 1)
+    for k in ("means2d", "depths", "conics"):
+        t = meta[k].detach()
+        if t.shape[:radii.dim()] == radii.shape:
+            vis = (radii > 0).reshape(radii.shape + (1,) * (t.dim() - radii.dim()))
+            out[k] = (torch.where(vis, t, torch.zeros((), dtype=t.dtype, device=t.device)), 1)
+    return out
 
 
 def algorithmic_bytes(stats):
@@ -299,7 +361,7 @@ def dp_projection(args, t1_ms, stats):
     out = {}
     for mode in ("camera", "camera_sparse", "gaussian"):
         env = dict(os.environ, GS_BENCH_PG="1", GS_DIST_FORCE_COLLECTIVES="1", MASTER_PORT=str(29600 + (os.getpid() % 300)))
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--dp-mode", mode, "--steps", "20", "--warmup", "5",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--gpus", "1", "--dp-mode", mode, "--steps", "20", "--warmup", "5",
                "--min-timed-s", "0.3", "--no-cpu-baseline", "--no-extras", "--no-dp-projection", "--scene-grid", str(args.scene_grid),
                "--width", str(args.width), "--height", str(args.height), "--sh-degree", str(args.sh_degree)]
         rec = {"wire_bytes_out_per_rank_world8": wire8[mode], "xgmi_floor_ms": wire8[mode] / (7 * 153e9) * 1e3}
@@ -468,6 +530,7 @@ def main_dynamic(args):
     D = args.dynamic_channels
     form = args.dynamic_form
     last_meta = {}
+    last_out = {}  # (--dump-outputs) the render of the last step
 
     def features(q, tau):
         if D == 3:
@@ -484,6 +547,8 @@ def main_dynamic(args):
             if use_pg:
                 all_reduce_splat_grads(params, world_size=world, average=False)
             last_meta.update(meta)
+            if args.dump_outputs:
+                last_out.update(render_colors=rc, render_alphas=ra)
             return
         if form == "reference":
             q, _ = sim.simulate_compression(params, step=1)
@@ -503,6 +568,8 @@ def main_dynamic(args):
         if use_pg:
             all_reduce_splat_grads(params, world_size=world, average=False)
         last_meta.update(meta)
+        if args.dump_outputs:
+            last_out.update(render_colors=rc, render_alphas=ra)
 
     def max_over_ranks(x):
         if not use_pg:
@@ -519,26 +586,27 @@ def main_dynamic(args):
     for _ in range(args.warmup):
         step()
     barrier()
-    # pass A (untimed): every C-ABI entry point with events, on the operator path (see main())
     from gscodec_studio_amd import _step
     step_driver_on = _step.ENABLED
-    _step.ENABLED = False
-    for _ in range(2):
-        step()
-    with CallTimer(B) as ct:
+    if args.full:
+        # pass A (untimed): every C-ABI entry point with events, on the operator path (see main())
+        _step.ENABLED = False
         for _ in range(2):
             step()
-    _step.ENABLED = step_driver_on
-    for _ in range(2):
-        step()
-    per_call = {k: float(np.mean(v)) for k, v in ct.totals_ms().items()}
-    calls_per_step = {k: len(v) / 2 for k, v in ct.events.items()}
-    per_step = {k: per_call[k] * calls_per_step[k] for k in per_call}
-    dominant = max((k for k in per_step if not k.startswith("gs_step_")), key=per_step.get)
+        with CallTimer(B) as ct:
+            for _ in range(2):
+                step()
+        _step.ENABLED = step_driver_on
+        for _ in range(2):
+            step()
+        per_call = {k: float(np.mean(v)) for k, v in ct.totals_ms().items()}
+        calls_per_step = {k: len(v) / 2 for k, v in ct.events.items()}
+        per_step = {k: per_call[k] * calls_per_step[k] for k in per_call}
+        dominant = max((k for k in per_step if not k.startswith("gs_step_")), key=per_step.get)
 
-    def timed_region(n_steps, timer_only):
+    def timed_region(n_steps, timer_only=None):
         barrier()
-        with CallTimer(B, only=timer_only) as ct_:
+        with (CallTimer(B, only=timer_only) if timer_only is not None else contextlib.nullcontext()) as ct_:
             t0_ = time.perf_counter()
             for _ in range(n_steps):
                 step()
@@ -557,31 +625,23 @@ def main_dynamic(args):
         for _ in range(int(min(5000, args.ramp_s / max(max_over_ranks(time.perf_counter() - t0) / 5, 1e-5)))):
             step()
     torch.cuda.reset_peak_memory_stats(dev)
-    elapsed, ct = timed_region(args.steps, {dominant})
-    dom_all = list(ct.totals_ms().get(dominant, ())) or [per_call[dominant]]
+    elapsed, ct = timed_region(args.steps, {dominant} if args.full else None)
     peak_mem = torch.cuda.max_memory_allocated(dev)
     regions = [elapsed]
-    for _ in range(int(min(200, max(0, np.ceil(args.min_timed_s / max(elapsed, 1e-6)) - 1)))):
-        regions.append(timed_region(args.steps, set())[0])
+    if args.full:
+        dom_all = list(ct.totals_ms().get(dominant, ())) or [per_call[dominant]]
+        for _ in range(int(min(200, max(0, np.ceil(args.min_timed_s / max(elapsed, 1e-6)) - 1)))):
+            regions.append(timed_region(args.steps, set())[0])
+        dom_ms = float(np.mean(dom_all))
     gc.enable()
-    dom_ms = float(np.mean(dom_all))
     ms_per_step = sum(regions) / (len(regions) * args.steps) * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out, splat_outputs(params, last_meta))
 
     if rank == 0:
         meta = last_meta
         V, I = int((meta["radii"] > 0).sum()), int(meta["flatten_ids"].numel())
         P, T = W_ * H_, meta["tile_width"] * meta["tile_height"]
-        # floats per splat the hooks quantize outside the projection kernel: all 17, or -- form "full" -- what the kernel does not take
-        A_hooks = DYN_QUANT_FLOATS if form != "full" else (6 if D == 3 else 9)
-        alg = dynamic_algorithmic_bytes(N, V, I, P, T, D, A_hooks)
-        dyn_key = f"dynamic_{N}_{W_}x{H_}_ch{D}_{form}"
-        # whole step: SURVEY 8(d)'s closed form with the [N, D] colours in place of the SH rows, plus the hooks (8 A each way is the
-        # survey's figure; the round STE's backward is the identity: 0) and the slice both ways
-        total_alg = (alg["gs_quantize_round_fwd"] + alg["gs_temporal_slice_fwd"] + alg["gs_projection_rows_fwd"]
-                     + (32 * V + 4 * N + 12 * I) + 24 * I + (8 * I + 4 * T) + alg["gs_rasterize_fwd"]
-                     + alg["gs_rasterize_bwd"] + alg["gs_projection_rows_bwd"] + alg["gs_temporal_slice_bwd"])
-        achieved = alg.get(dominant, 0) / (dom_ms * 1e-3) / 1e9
-        gpu_entry_ms = sum(per_step.values())
         out = {
             "metric": "Msplats/s fwd+bwd @1080p (2M dynamic splats, config 5 step)",
             "value": N * world / (ms_per_step * 1e-3) / 1e6, "unit": "Msplats/s",
@@ -603,7 +663,20 @@ def main_dynamic(args):
                 "visible": V, "n_isects": I, "channels": D, "native_step_driver": bool(step_driver_on), "splat_order": w["order"],
                 "parallelism": f"frames round-robin over {world} rank(s)" + (", RCCL sum of the parameter gradients" if world > 1 else ""),
             },
-            "roofline": {
+        }
+        if args.full:
+            # floats per splat the hooks quantize outside the projection kernel: all 17, or -- form "full" -- what the kernel does not take
+            A_hooks = DYN_QUANT_FLOATS if form != "full" else (6 if D == 3 else 9)
+            alg = dynamic_algorithmic_bytes(N, V, I, P, T, D, A_hooks)
+            dyn_key = f"dynamic_{N}_{W_}x{H_}_ch{D}_{form}"
+            # whole step: SURVEY 8(d)'s closed form with the [N, D] colours in place of the SH rows, plus the hooks (8 A each way is the
+            # survey's figure; the round STE's backward is the identity: 0) and the slice both ways
+            total_alg = (alg["gs_quantize_round_fwd"] + alg["gs_temporal_slice_fwd"] + alg["gs_projection_rows_fwd"]
+                         + (32 * V + 4 * N + 12 * I) + 24 * I + (8 * I + 4 * T) + alg["gs_rasterize_fwd"]
+                         + alg["gs_rasterize_bwd"] + alg["gs_projection_rows_bwd"] + alg["gs_temporal_slice_bwd"])
+            achieved = alg.get(dominant, 0) / (dom_ms * 1e-3) / 1e9
+            gpu_entry_ms = sum(per_step.values())
+            out["roofline"] = {
                 "bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                 "traffic": measured_pmc(dominant, dyn_key, path=TRAFFIC_JSON_DYNAMIC, wide=D > 4), "kernel_ms": dom_ms,
                 "algorithmic_bytes": alg.get(dominant, 0),
@@ -625,8 +698,7 @@ def main_dynamic(args):
                               for k in ("gs_quantize_round_fwd", "gs_quantize_round_multi_fwd", "gs_temporal_slice_fwd", "gs_temporal_slice_bwd", "gs_projection_rows_fwd",
                                         "gs_projection_rows_bwd", "gs_projection_rows_dyn_fwd", "gs_projection_rows_dyn_bwd")
                               if k in per_step and per_step[k] > 0},
-            },
-        }
+            }
     if use_pg:
         dist.barrier()
         dist.destroy_process_group()
@@ -707,6 +779,7 @@ def main():
                                     cap_max=N)
 
     last_meta = {}
+    last_out = {}  # (--dump-outputs) the render of the last step
     dense_grad = [None]  # set to a dense tensor of ones for the dense-image-gradient variant
 
     def make_step(mode):
@@ -760,7 +833,10 @@ def main():
             if mode in ("camera", "camera_sparse") and use_pg:
                 all_reduce_splat_grads(params, world_size=world, average=False, plan=plan)
             last_meta.update(meta)
+            if args.dump_outputs:
+                last_out.update(render_colors=rc, render_alphas=ra)
 
+        step.params = params
         return step
 
     def max_over_ranks(x):
@@ -796,43 +872,45 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    # the protocol as the reference runs it (profiling/main.py:28-37): W warm-up steps, then K steps between synchronisations -- no
-    # ramp, no repetitions.  Reported as ms_per_step_cold_protocol next to the headline (which is taken at sustained clocks, below)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    barrier()
-    cold_ms = max_over_ranks(time.perf_counter() - t0) / args.steps * 1e3
+    if args.full:
+        # the protocol as the reference runs it (profiling/main.py:28-37): W warm-up steps, then K steps between synchronisations -- no
+        # ramp, no repetitions.  Reported as ms_per_step_cold_protocol next to the headline (which is taken at sustained clocks, below)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        barrier()
+        cold_ms = max_over_ranks(time.perf_counter() - t0) / args.steps * 1e3
 
-    # pass A (untimed): find the dominant entry point.  rasterization()'s fast path issues its forward through the native
-    # step driver (gs_step_fwd_*: bundles of operator calls made inside the library, invisible to this timer), so this pass
-    # runs the OPERATOR path -- the same launches through the same entry points, one ctypes call each -- to time them one
-    # by one; the timed regions below run the default path and carry events around the dominant operator only.
     from gscodec_studio_amd import _step
     step_driver_on = _step.ENABLED
-    _step.ENABLED = False
-    for _ in range(2):
-        step()
-    with CallTimer(B) as ct:
+    if args.full or args.breakdown:
+        # pass A (untimed): find the dominant entry point.  rasterization()'s fast path issues its forward through the native
+        # step driver (gs_step_fwd_*: bundles of operator calls made inside the library, invisible to this timer), so this pass
+        # runs the OPERATOR path -- the same launches through the same entry points, one ctypes call each -- to time them one
+        # by one; the timed regions below run the default path and carry events around the dominant operator only.
+        _step.ENABLED = False
         for _ in range(2):
             step()
-    _step.ENABLED = step_driver_on
-    for _ in range(2):
-        step()
-    per_call = {k: float(np.mean(v)) for k, v in ct.totals_ms().items()}
-    calls_per_step = {k: len(v) / 2 for k, v in ct.events.items()}
-    per_step = {k: per_call[k] * calls_per_step[k] for k in per_call}
-    dominant = max((k for k in per_step if not k.startswith("gs_step_")), key=per_step.get)
-    if args.breakdown and rank == 0:
-        for k, v in sorted(per_step.items(), key=lambda kv: -kv[1]):
-            print(f"  {k:32s} {v:8.3f} ms/step", file=sys.stderr)
+        with CallTimer(B) as ct:
+            for _ in range(2):
+                step()
+        _step.ENABLED = step_driver_on
+        for _ in range(2):
+            step()
+        per_call = {k: float(np.mean(v)) for k, v in ct.totals_ms().items()}
+        calls_per_step = {k: len(v) / 2 for k, v in ct.events.items()}
+        per_step = {k: per_call[k] * calls_per_step[k] for k in per_call}
+        dominant = max((k for k in per_step if not k.startswith("gs_step_")), key=per_step.get)
+        if args.breakdown and rank == 0:
+            for k, v in sorted(per_step.items(), key=lambda kv: -kv[1]):
+                print(f"  {k:32s} {v:8.3f} ms/step", file=sys.stderr)
 
-    # timed region: exactly K steps between barrier + synchronize on both sides, only the dominant entry point carries
-    # events.  K = 20 steps last ~20 ms, so the region is REPEATED (every repetition bracketed the same way, the number of
+    # timed region: exactly K steps between barrier + synchronize on both sides.  With --full, only the dominant entry point carries
+    # events, and as K = 20 steps last ~20 ms, the region is REPEATED (every repetition bracketed the same way, the number of
     # repetitions agreed by all ranks) until --min-timed-s has been measured; ms_per_step is total time / total steps.
-    def timed_region(n_steps, timer_only):
+    def timed_region(n_steps, timer_only=None):
         barrier()
-        with CallTimer(B, only=timer_only) as ct_:
+        with (CallTimer(B, only=timer_only) if timer_only is not None else contextlib.nullcontext()) as ct_:
             t0_ = time.perf_counter()
             for _ in range(n_steps):
                 step()
@@ -864,26 +942,30 @@ def main():
     torch.cuda.reset_peak_memory_stats(dev)
     mem_before = torch.cuda.memory_allocated(dev)
     D.WIRE["bytes"] = 0
-    elapsed, ct = timed_region(args.steps, {dominant})
+    elapsed, ct = timed_region(args.steps, {dominant} if args.full else None)
     wire_bytes_per_step = D.WIRE["bytes"] / args.steps
-    # (with the native step driver on, the compositing FORWARD is launched inside gs_step_fwd_finish and never passes through
-    # this timer: at sizes where it, not the backward, dominates -- small scenes -- its duration comes from pass A instead)
-    dom_all = list(ct.totals_ms().get(dominant, ())) or [per_call[dominant]]
-    dom_source = "timed region" if dominant in ct.events else "pass A (operator path, untimed steps)"
     peak_mem = torch.cuda.max_memory_allocated(dev)
     regions = [elapsed]
-    n_rep = int(min(200, max(0, np.ceil(args.min_timed_s / max(elapsed, 1e-6)) - 1)))
-    for _ in range(n_rep):  # (the repetitions run without event timers: nothing but the steps inside the region)
-        e_, _ = timed_region(args.steps, set())
-        regions.append(e_)
-    dom_ms = float(np.mean(dom_all))
+    if args.full:
+        # (with the native step driver on, the compositing FORWARD is launched inside gs_step_fwd_finish and never passes through
+        # this timer: at sizes where it, not the backward, dominates -- small scenes -- its duration comes from pass A instead)
+        dom_all = list(ct.totals_ms().get(dominant, ())) or [per_call[dominant]]
+        dom_source = "timed region" if dominant in ct.events else "pass A (operator path, untimed steps)"
+        dom_ms = float(np.mean(dom_all))
+        n_rep = int(min(200, max(0, np.ceil(args.min_timed_s / max(elapsed, 1e-6)) - 1)))
+        for _ in range(n_rep):  # (the repetitions run without event timers: nothing but the steps inside the region)
+            e_, _ = timed_region(args.steps, set())
+            regions.append(e_)
     ms_per_step = sum(regions) / (len(regions) * args.steps) * 1e3
     if args.breakdown and rank == 0:
         print("  regions (ms/step): " + " ".join(f"{r / args.steps * 1e3:.3f}" for r in regions), file=sys.stderr)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out, splat_outputs(step.params, last_meta))
+
     # variant: a DENSE image gradient (what a real training loss produces) next to the broadcast one of the protocol
     dense_ms = nosum_ms = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         dense_grad[0] = torch.ones((1, w["height"], w["width"], 3), dtype=torch.float32, device=dev)
         for _ in range(3):
             step()
@@ -904,18 +986,6 @@ def main():
         vis = (meta["tiles_per_gauss"] > 0) if mode.startswith("gaussian") else (meta["radii"] > 0)
         stats = dict(N=N, V=int(vis.sum()), I=int(meta["flatten_ids"].numel()),
                      P=w["width"] * w["height"], T=meta["tile_width"] * meta["tile_height"], K=(args.sh_degree + 1) ** 2)
-        alg = algorithmic_bytes(stats)
-        achieved = alg.get(dominant, 0) / (dom_ms * 1e-3) / 1e9
-        # whole step: SURVEY.md 8(d)'s closed form (every stage once: projection, SH, binning with the sort at its
-        # compulsory one read + one write, compositing, and the three backward stages) -- NOT the sum over every entry
-        # point the library exports (round 2 summed alternatives the step never calls and overstated this by 40 %)
-        Ns, Vs, Is, Ps, Ts, Ks_ = (stats[k] for k in ("N", "V", "I", "P", "T", "K"))
-        total_alg = (48 * Ns + (80 + 12 * Ks_) * Vs + 84 * Is + 4 * Ts + 20 * Ps) + \
-                    ((44 + 12 * Ks_) * Ns + (164 + 12 * Ks_) * Vs + 40 * Is + 24 * Ps)
-        called_alg = sum(alg[k] for k in per_step if k in alg)
-        # gs_projection_rows_bwd with prefilled outputs: radii of every pair, then only the visible gaussians' inputs (40 B), splat and
-        # gradient rows (92 B used), SH rows in and out (24 K B) and the 44 B of per-gaussian gradients
-        kernel_only = {"gs_projection_rows_bwd": 4 * Ns + (92 + 40 + 44 + 24 + 24 * Ks_) * Vs}
         out = {
             "metric": "Msplats/s fwd+bwd @1080p (1M splats)",
             "value": N * world / (ms_per_step * 1e-3) / 1e6,
@@ -931,9 +1001,6 @@ def main():
             # the measured step time can be read against
             "wire": {"bytes_out_per_rank_per_step": wire_bytes_per_step, "xgmi_floor_ms": wire_bytes_per_step / (7 * 153e9) * 1e3,
                      "xgmi_peak_gbs_per_gpu": 7 * 153} if use_pg else None,
-            "ms_per_step_cold_protocol": cold_ms,
-            "ms_per_step_dense_image_grad": dense_ms,
-            "ms_per_step_without_loss_forward": nosum_ms,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {
                 "workload": f"BASELINE config 2: load_test_data(scene_grid={args.scene_grid}) -> {N} gaussians, "
@@ -945,7 +1012,24 @@ def main():
                 **({"dp_mode": mode, "dp_calibration_ms_per_step": calib} if use_pg else {}),
                 **({"launch_fallback": os.environ["GS_BENCH_LAUNCH_FALLBACK"]} if os.environ.get("GS_BENCH_LAUNCH_FALLBACK") else {}),
             },
-            "roofline": {
+        }
+        if args.full:
+            alg = algorithmic_bytes(stats)
+            achieved = alg.get(dominant, 0) / (dom_ms * 1e-3) / 1e9
+            # whole step: SURVEY.md 8(d)'s closed form (every stage once: projection, SH, binning with the sort at its
+            # compulsory one read + one write, compositing, and the three backward stages) -- NOT the sum over every entry
+            # point the library exports (round 2 summed alternatives the step never calls and overstated this by 40 %)
+            Ns, Vs, Is, Ps, Ts, Ks_ = (stats[k] for k in ("N", "V", "I", "P", "T", "K"))
+            total_alg = (48 * Ns + (80 + 12 * Ks_) * Vs + 84 * Is + 4 * Ts + 20 * Ps) + \
+                        ((44 + 12 * Ks_) * Ns + (164 + 12 * Ks_) * Vs + 40 * Is + 24 * Ps)
+            called_alg = sum(alg[k] for k in per_step if k in alg)
+            # gs_projection_rows_bwd with prefilled outputs: radii of every pair, then only the visible gaussians' inputs (40 B), splat and
+            # gradient rows (92 B used), SH rows in and out (24 K B) and the 44 B of per-gaussian gradients
+            kernel_only = {"gs_projection_rows_bwd": 4 * Ns + (92 + 40 + 44 + 24 + 24 * Ks_) * Vs}
+            out["ms_per_step_cold_protocol"] = cold_ms
+            out["ms_per_step_dense_image_grad"] = dense_ms
+            out["ms_per_step_without_loss_forward"] = nosum_ms
+            out["roofline"] = {
                 "bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS,
                 "traffic": measured_traffic(dominant, f"grid{args.scene_grid}_{w['width']}x{w['height']}_sh{args.sh_degree}"),
@@ -993,14 +1077,13 @@ def main():
                                                "entry_points": sorted(k for k in per_step if k in BINNING_ENTRIES)})(
                     sum(v for k, v in per_step.items() if k in BINNING_ENTRIES),
                     (32 * Vs + 4 * Ns + 12 * Is) + 24 * Is + (8 * Is + 4 * Ts)),
-            },
-        }
-        if not args.no_extras and world == 1:
-            out["psnr_vs_oracle"] = psnr_vs_oracle(dev)
-        if world == 1 and not use_pg and not args.no_dp_projection and not args.quantize:
-            out["multi_gpu_projection"] = dp_projection(args, ms_per_step, stats)
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(args, args.sh_degree)
+            }
+            if not args.no_extras and world == 1:
+                out["psnr_vs_oracle"] = psnr_vs_oracle(dev)
+            if world == 1 and not use_pg and not args.no_dp_projection and not args.quantize:
+                out["multi_gpu_projection"] = dp_projection(args, ms_per_step, stats)
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(args, args.sh_degree)
     if use_pg:
         dist.barrier()
         dist.destroy_process_group()

@@ -10,13 +10,14 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAST = ["--steps", "2", "--warmup", "1", "--scene-grid", "1", "--no-cpu-baseline", "--no-extras"]
+FAST = ["--steps", "2", "--warmup", "1", "--scene-grid", "1", "--full", "--no-cpu-baseline", "--no-extras"]
 
 
 def _env(share):
@@ -98,8 +99,8 @@ def test_failed_auto_run_falls_back_to_camera_mode():
 def test_dynamic_bench_one_and_two_ranks(form):
     """``bench.py --dynamic`` (BASELINE config 5's frame step): the one-GPU line carries roofline + streaming rows, and the driver's
     ``--gpus 2`` form shards frames round-robin (each rank its own timestamp) and sums the parameter gradients."""
-    args = ["--dynamic", "--dynamic-form", form, "--dynamic-splats", "150000", "--steps", "2", "--warmup", "1", "--min-timed-s", "0",
-            "--ramp-s", "0"]
+    args = ["--dynamic", "--dynamic-form", form, "--dynamic-splats", "150000", "--steps", "2", "--warmup", "1", "--full", "--min-timed-s",
+            "0", "--ramp-s", "0"]
     r = subprocess.run([sys.executable, "bench.py"] + args, cwd=ROOT, env=_env(False), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = _last_json(r.stdout)
@@ -113,3 +114,37 @@ def test_dynamic_bench_one_and_two_ranks(form):
     assert r.returncode == 0, r.stderr[-3000:]
     rec2 = _last_json(r.stdout)
     assert rec2["n_gpus"] == 2 and rec2["value"] > 0 and "frames round-robin over 2" in rec2["config"]["parallelism"]
+
+
+def test_plain_run_times_exactly_k_steps_and_dumps_outputs(tmp_path):
+    """A plain one-GPU run times exactly --steps steps in one region and reports only the headline (the other measurements are
+    --full's); --dump-outputs writes the last timed step's render, gradients and projection outputs, from the same seeded inputs
+    in every run."""
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--scene-grid", "1", "--ramp-s", "0"]
+    recs = []
+    for i in range(2):
+        r = subprocess.run([sys.executable, "bench.py"] + args + ["--dump-outputs", str(tmp_path / f"run{i}")], cwd=ROOT,
+                           env=_env(False), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        recs.append(_last_json(r.stdout))
+    rec = recs[0]
+    assert rec["steps"] == 3 and rec["timed"]["regions"] == 1 and rec["timed"]["steps_per_region"] == 3
+    assert rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["unit"] == "Msplats/s" and rec["dtype"] == "f32"
+    assert rec["higher_is_better"] is True and rec["metric"].startswith("Msplats/s")
+    assert not {"roofline", "cpu_baseline", "psnr_vs_oracle", "multi_gpu_projection", "ms_per_step_cold_protocol"} & set(rec)
+    names = sorted(os.listdir(tmp_path / "run0"))
+    assert {"render_colors.npy", "render_alphas.npy", "means_grad.npy", "sh_grad.npy", "radii.npy"} <= set(names), names
+    assert names == sorted(os.listdir(tmp_path / "run1"))
+    total = 0
+    for name in names:
+        a, b = np.load(tmp_path / "run0" / name), np.load(tmp_path / "run1" / name)
+        assert a.dtype == np.float32 and a.shape == b.shape, name
+        total += a.nbytes
+        # only computed values (no unwritten memory): the forward outputs bit for bit, the gradients up to the order of the float
+        # atomics they are summed with
+        assert np.isfinite(a).all() and np.isfinite(b).all(), name
+        if not name.endswith("_grad.npy"):
+            assert np.array_equal(a, b), name
+        rel = np.linalg.norm((a - b).astype(np.float64)) / max(np.linalg.norm(b.astype(np.float64)), 1e-30)
+        assert rel < 1e-3, (name, rel)
+    assert total <= 64 * 2**20

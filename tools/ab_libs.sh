@@ -8,7 +8,7 @@ shift || true
 for r in $(seq 1 "$rounds"); do
     for lib in default "$root"/build_ab/*.so; do
         if [ "$lib" = default ]; then unset GSPLAT_HIP_LIB; else export GSPLAT_HIP_LIB=$lib; fi
-        ms=$(timeout 300 python "$root/bench.py" --no-cpu-baseline --no-extras --no-dp-projection "$@" 2>/dev/null < /dev/null |
+        ms=$(timeout 300 python "$root/bench.py" --full --no-cpu-baseline --no-extras --no-dp-projection "$@" 2>/dev/null < /dev/null |
              python -c "import sys,json; print('%.4f' % json.loads(sys.stdin.read())['ms_per_step'])")
         echo "$(basename "$lib") $ms"
     done

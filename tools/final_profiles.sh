@@ -9,11 +9,11 @@ cd "$root"
 # (the counter passes first: bench.py reads roofline.traffic / roofline.valu from the file they produce)
 bash tools/pmc.sh "$out/${tag}_pmc_traffic.json" > "$out/pmc.log" 2>&1
 cp "$out/${tag}_pmc_traffic.json" profiles/${tag}_pmc_traffic.json
-python bench.py > "$out/${tag}_bench.json" 2> "$out/bench.err" < /dev/null
+python bench.py --full > "$out/${tag}_bench.json" 2> "$out/bench.err" < /dev/null
 python bench.py --gpus 1 --steps 20 --warmup 5 > "$out/${tag}_bench_driver_cmd.json" 2>> "$out/bench.err" < /dev/null
 {
   for f in "--quantize" "--quantize --quantize-reference-calls" "--quantize --ada-mask" "--quantize --ada-mask --quantize-reference-calls"; do
-    python bench.py --no-cpu-baseline --no-extras --no-dp-projection $f 2>/dev/null < /dev/null | tail -1
+    python bench.py --full --no-cpu-baseline --no-extras --no-dp-projection $f 2>/dev/null < /dev/null | tail -1
   done
 } > "$out/${tag}_bench_quantize.jsonl"
 bash tools/prof.sh $tag > "$out/prof.log" 2>&1
@@ -28,7 +28,7 @@ cp gpurun_out/prof_${tag}q_last_step.txt "$out/${tag}_quantize_last_step_timelin
   AB=1 python tools/cpu_overhead.py 2>/dev/null | head -2
   AB=1 python tools/cpu_overhead.py 2>/dev/null | head -2
   for cfg in "1 1" "0 1" "1 0" "0 0"; do set -- $cfg
-    GS_PRESORT=$1 GS_STEP_DRIVER=$2 python bench.py --steps 100 --min-timed-s 2 --no-cpu-baseline --no-extras --no-dp-projection 2>/dev/null < /dev/null | tail -1 | \
+    GS_PRESORT=$1 GS_STEP_DRIVER=$2 python bench.py --full --steps 100 --min-timed-s 2 --no-cpu-baseline --no-extras --no-dp-projection 2>/dev/null < /dev/null | tail -1 | \
       python -c "import json,sys; d=json.loads(sys.stdin.read()); print('A/B bucketed pre-sort', sys.argv[1], 'step driver', sys.argv[2], ': ms/step', round(d['ms_per_step'],4))" $1 $2
   done
 } > "$out/${tag}_secondary.txt" 2>&1
@@ -38,9 +38,9 @@ python -m pytest tests/test_gpu_fullsize_parity.py -q -s 2>&1 | grep -E "full si
 ./build_abl/presort_bench > "$out/${tag}_presort_breakdown.txt" 2>&1
 {
   python tools/host_phases.py 2>&1 | grep " us"
-  python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-dp-projection 2>/dev/null < /dev/null | tail -1 | python -c "import sys,json; print('plain ms/step', round(json.loads(sys.stdin.read())['ms_per_step'], 4))"
+  python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-dp-projection 2>/dev/null < /dev/null | tail -1 | python -c "import sys,json; print('plain ms/step', round(json.loads(sys.stdin.read())['ms_per_step'], 4))"
   for i in 1 2 3; do
-    GS_BENCH_PG=1 GS_DIST_FORCE_COLLECTIVES=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=2965$i python bench.py --gpus 1 --dp-mode gaussian --steps 20 --warmup 5 --min-timed-s 0.3 --no-cpu-baseline --no-extras --no-dp-projection 2>/dev/null < /dev/null | tail -1 | python -c "import sys,json; print('gaussian-sharded, world 1, forced collectives: ms/step', round(json.loads(sys.stdin.read())['ms_per_step'], 4))"
+    GS_BENCH_PG=1 GS_DIST_FORCE_COLLECTIVES=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=2965$i python bench.py --full --gpus 1 --dp-mode gaussian --steps 20 --warmup 5 --min-timed-s 0.3 --no-cpu-baseline --no-extras --no-dp-projection 2>/dev/null < /dev/null | tail -1 | python -c "import sys,json; print('gaussian-sharded, world 1, forced collectives: ms/step', round(json.loads(sys.stdin.read())['ms_per_step'], 4))"
   done
 } > "$out/${tag}_gaussian_mode.txt" 2>&1
 # 5..32 colour channels (round 5): the step at config 2's size, the reference's 32-channel protocol row, kernel stats
@@ -65,10 +65,10 @@ PMC_BENCH_ARGS="--dynamic" PMC_WORKLOAD_KEY=dynamic_2000000_1920x1080_ch3_full b
 cp "$out/${tag}_pmc_traffic_dynamic.json" profiles/${tag}_pmc_traffic_dynamic.json
 {
   for f in reference activate fused full; do for d in 3 9; do
-    python bench.py --dynamic --dynamic-form $f --dynamic-channels $d 2>/dev/null < /dev/null | tail -1
+    python bench.py --full --dynamic --dynamic-form $f --dynamic-channels $d 2>/dev/null < /dev/null | tail -1
   done; done
   # the same splats in Z-order (config.splat_order = "morton"): what a spatially sorted array buys the streaming stages
-  for f in reference full; do python bench.py --dynamic --dynamic-form $f --dynamic-order morton 2>/dev/null < /dev/null | tail -1; done
+  for f in reference full; do python bench.py --full --dynamic --dynamic-form $f --dynamic-order morton 2>/dev/null < /dev/null | tail -1; done
 } > "$out/${tag}_bench_dynamic.jsonl"
 for f in reference full; do
   bash tools/prof.sh ${tag}dyn_$f --dynamic --dynamic-form $f > "$out/prof_dyn_$f.log" 2>&1

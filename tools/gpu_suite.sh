@@ -1,4 +1,5 @@
-# The whole GPU test suite + one headline bench line on the GPU box:  gpurun -- bash tools/gpu_suite.sh  -> gpurun_out/r06c/
-mkdir -p gpurun_out/r06c
-timeout 2400 python -m pytest tests -q -m gpu -x 2>&1 | tail -30 > gpurun_out/r06c/tests.txt
-python bench.py --no-dp-projection --no-cpu-baseline 2>/dev/null | tail -1 > gpurun_out/r06c/bench.json
+# The whole GPU test suite + one full bench line on the GPU box:  bash tools/gpu_suite.sh OUT_DIR  -> OUT_DIR/tests.txt, OUT_DIR/bench.json
+out=${1:?usage: tools/gpu_suite.sh OUT_DIR}
+mkdir -p "$out"
+timeout 2400 python -m pytest tests -q -m gpu -x 2>&1 | tail -30 > "$out/tests.txt"
+python bench.py --full --no-dp-projection --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench.json"

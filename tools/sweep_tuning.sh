@@ -3,7 +3,7 @@
 # One bench.py run per setting (the values travel through GS_RASTER_* -> gs_raster_plan).
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 run() {
-    ms=$(env "$@" python "$root/bench.py" --no-cpu-baseline --no-extras --steps 30 --warmup 10 --min-timed-s 0.3 2>/dev/null | tail -1 |
+    ms=$(env "$@" python "$root/bench.py" --full --no-cpu-baseline --no-extras --steps 30 --warmup 10 --min-timed-s 0.3 2>/dev/null | tail -1 |
          python -c "import sys, json; print('%.4f' % json.loads(sys.stdin.read())['ms_per_step'])")
     echo "$ms ms/step  $*"
 }
