@@ -9,10 +9,11 @@ instead of seven operator calls with their Python glue: ~0.6 ms of host work per
 Autograd sees the same two nodes as on the operator path, so that ``meta["means2d"]`` stays an autograd intermediate
 (``retain_grad()`` / ``.absgrad`` of the reference's densification strategies, strategy/default.py:150, 221-226):
 
-* ``_StepProject``   forward: the WHOLE forward (both native calls); backward: ``_ProjectRows.backward`` (projection + SH);
-* ``_StepComposite`` forward: hands out the images node 1 rendered; backward: ``_RasterizeToPixels.backward``.
+* ``_StepProject``   forward: the WHOLE forward (both native calls); backward: ``_wrapper._project_rows_bwd`` (projection + SH);
+* ``_StepComposite`` forward: hands out the images node 1 rendered; backward: ``_wrapper._rasterize_bwd``.
 
-The backward bodies are the operator path's own (same saved tensors, same context attributes), so every property tested
+There is no native backward: both nodes save their state through the operator path's helpers (``_save_projection``,
+``_save_composite``) and run its backward bodies, gradients keyed by input name (``INPUTS``), so every property tested
 there -- prefilled gradients, repeated backward, partial requires_grad, expanded image gradients -- carries over.
 """
 from __future__ import annotations
@@ -37,7 +38,7 @@ class _Plan(ctypes.Structure):  # gs_raster_plan
                 ("scratch_bytes", ctypes.c_uint64), ("reserved", ctypes.c_uint32 * 6)]
 
 
-_P, _U32, _I32, _U64, _I64, _F = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_float
+_P, _U32, _I32, _U64, _F = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_float
 
 
 class _Step(ctypes.Structure):  # gs_step of include/gsplat_hip.h (field for field)
@@ -49,28 +50,24 @@ class _Step(ctypes.Structure):  # gs_step of include/gsplat_hip.h (field for fie
         ("eps2d", _F), ("near_plane", _F), ("far_plane", _F), ("radius_clip", _F),
         ("camera_model", _I32), ("antialiased", _I32), ("tile_size", _U32), ("tile_width", _U32), ("tile_height", _U32),
         ("bucketed", _I32), ("lds_capacity", _U32), ("sh_mask_binary", _I32),
-        ("sh_mask_logits", _P), ("v_sh_mask_logits", _P), ("sh_mask_temperature", _F), ("rows_ready", _U32),
+        ("sh_mask_logits", _P), ("sh_mask_temperature", _F), ("rows_ready", _U32),
         ("backgrounds", _P),
         ("radii", _P), ("depths", _P), ("rows", _P), ("tiles_per_gauss", _P), ("depth_keys", _P), ("depth_vals", _P),
         ("sort_temp", _P), ("sort_temp_bytes", _U64), ("splitters", _P), ("sorted_keys", _P), ("perm", _P), ("n_kept", _P),
         ("group_sums", _P), ("group_prefix", _P), ("cumsum_scratch", _P), ("cumsum_scratch_bytes", _U64), ("block_sums", _P),
         ("n_isects", _U64), ("n_kept_host", _U32), ("reserved1", _U32), ("isect_ids", _P), ("flatten_ids", _P), ("offsets", _P), ("work", _P), ("work_bytes", _U64),
         ("render_colors", _P), ("render_alphas", _P), ("last_ids", _P), ("plan", _Plan), ("scratch", _P), ("zero_fill", _P),
-        ("zero_fill_bytes", _U64),
-        ("v_render_colors", _P), ("v_render_alphas", _P), ("vrc_pixel_stride", _I64), ("vrc_channel_stride", _I64),
-        ("grad_rows", _P), ("v_depths", _P), ("v_means", _P), ("v_covars", _P), ("v_quats", _P), ("v_scales", _P),
-        ("v_opacities", _P), ("v_colors", _P), ("v_sh", _P), ("v_sh_rest", _P),
-        ("absgrad", _I32), ("outputs_prefilled", _I32), ("skip_projection_bwd", _I32), ("finish_phase", _I32),
+        ("zero_fill_bytes", _U64), ("finish_phase", _I32),
         ("dyn_motion", _P), ("dyn_omega", _P), ("dyn_trbf_center", _P), ("dyn_trbf_scale", _P),
         ("dyn_timestamp", _F), ("dyn_raw_params", _U32), ("dyn_quant_mask", _U32), ("dyn_min_trbf", _F),
         ("dyn_quant_lo", _F * 4), ("dyn_quant_hi", _F * 4), ("dyn_quant_range", _F * 4), ("dyn_quant_step_norm", _F * 4),
-        ("v_dyn_motion", _P), ("v_dyn_omega", _P), ("v_dyn_trbf_center", _P), ("v_dyn_trbf_scale", _P), ("dyn_trbf_alive", _P),
+        ("dyn_trbf_alive", _P),
     ]
 
 
 _LAYOUT_FIELDS = ("C", "sh_K", "eps2d", "tile_size", "sh_mask_logits", "rows_ready", "backgrounds", "radii", "sort_temp_bytes", "block_sums",
-                  "n_isects", "n_kept_host", "work_bytes", "plan", "scratch", "zero_fill_bytes", "v_render_colors", "vrc_pixel_stride", "grad_rows",
-                  "v_sh_rest", "absgrad", "finish_phase", "dyn_motion", "dyn_timestamp", "dyn_quant_lo", "v_dyn_motion")
+                  "n_isects", "n_kept_host", "work_bytes", "plan", "scratch", "zero_fill_bytes", "finish_phase", "dyn_motion", "dyn_timestamp",
+                  "dyn_quant_lo", "dyn_trbf_alive")
 
 
 def check_layout() -> None:
@@ -221,28 +218,21 @@ def _finish(s, sp, stream, bufs, n_sums, C, N, height, width, tile_height, tile_
     render_colors = empty((C, height, width, 3), dtype=f32, device=dev)
     render_alphas = empty((C, height, width, 1), dtype=f32, device=dev)
     last_ids = empty((C, height, width), dtype=i32, device=dev)
-    fill = None
+    grad_rows = None
     if needs_bwd:
-        extra = prefill.floats() if prefill is not None else 0
-        if extra:
-            extra += 64  # slack behind the last piece (a multi-GPU reduction rounds the span of all pieces up into it)
-        fill = empty(n_elems * 16 + extra, dtype=f32, device=dev)
-        if extra:
-            prefill.carve(fill, n_elems * 16)
-        else:
-            prefill = None
+        fill, grad_rows, _, prefill = W._grad_fill(n_elems, 3, prefill, dev)
+        grad_rows = grad_rows.view(C, N, 16)
+        s.zero_fill, s.zero_fill_bytes = ptr(fill), fill.numel() * 4
     else:
         prefill = None
     s.render_colors, s.render_alphas, s.last_ids = ptr(render_colors), ptr(render_alphas), ptr(last_ids)
-    if fill is not None:
-        s.zero_fill, s.zero_fill_bytes = ptr(fill), fill.numel() * 4
     plan, sbytes = W._raster_plan(C * tile_height * tile_width, n_isects, 3, forward_only=not needs_bwd)
     ctypes.memmove(ctypes.addressof(s.plan), plan, 64)
     scratch = empty(sbytes, dtype=u8, device=dev)
     s.scratch = ptr(scratch)
     s.finish_phase = 2
     B.call("gs_step_fwd_finish", sp, stream)
-    return offsets, isect_ids, flatten_ids, render_colors, render_alphas, last_ids, fill, prefill, scratch, plan
+    return offsets, isect_ids, flatten_ids, render_colors, render_alphas, last_ids, grad_rows, prefill, scratch, plan
 
 
 _ISECT_CAP: dict = {}  # (device, C, N, tile grid) -> capacity for the next call's intersection buffers (last count + 3 %)
@@ -250,6 +240,9 @@ _PREALLOC = os.environ.get("GS_ISECT_PREALLOC", "1") != "0"
 
 
 class _StepProject(torch.autograd.Function):
+    INPUTS = ("means", "covars", "quats", "scales", "viewmats", None, "opacities", "colors", "sh", "sh_rest", "mask_logits", None, None, None,
+              "motion", "omega", "trbf_center", "trbf_scale", None)
+
     @staticmethod
     def forward(ctx, means, covars, quats, scales, viewmats, Ks, opacities, colors, sh_coeffs, sh_rest, mask_logits, backgrounds, cfg, hand,
                 dyn_motion=None, dyn_omega=None, dyn_center=None, dyn_tscale=None, dyn=None):
@@ -260,10 +253,7 @@ class _StepProject(torch.autograd.Function):
         viewmats, Ks, opacities, colors = _c(viewmats), _c(Ks), _c(opacities), _c(colors)
         sh_coeffs, sh_rest, backgrounds = _c(sh_coeffs), _c(sh_rest), _c(backgrounds)
         C, N = viewmats.shape[0], means.shape[0]
-        n_elems = C * N
         dev = means.device
-        i32, i64, f32, u8 = torch.int32, torch.int64, torch.float32, torch.uint8
-        empty = torch.empty
         s = _Step()
         s.C, s.N = C, N
         ptr = B.ptr
@@ -277,7 +267,7 @@ class _StepProject(torch.autograd.Function):
         cm = W._CAMERA_MODELS[camera_model]
         s.camera_model, s.antialiased = cm, int(antialiased)
         s.tile_size, s.tile_width, s.tile_height = tile_size, tile_width, tile_height
-        ctx.dyn, ctx.dyn_first = None, 14
+        dyn_ctx = None
         if dyn is not None:  # dynamic splats: the slice (+ activations / round quantizer) inside the projection kernel
             dt = dyn.bind(quats, scales, opacities, colors, dyn_motion, dyn_omega, dyn_center, dyn_tscale)
             (s.dyn_motion, s.dyn_omega, s.dyn_trbf_center, s.dyn_trbf_scale, s.dyn_timestamp, s.dyn_raw_params, s.dyn_quant_mask,
@@ -286,7 +276,7 @@ class _StepProject(torch.autograd.Function):
             for dst, src in ((s.dyn_quant_lo, dyn._tables[0]), (s.dyn_quant_hi, dyn._tables[1]), (s.dyn_quant_range, dyn._tables[2]),
                              (s.dyn_quant_step_norm, dyn._tables[3])):
                 dst[:] = src[:]
-            ctx.dyn = (dyn, dt)
+            dyn_ctx = (dyn, dt)
         n_sums = C * ((N + 255) // 256)  # gs_projection_rows_blocks(N) per camera: the projection counts the tiles itself
         bufs = _phase1(s, C, N, dev, n_sums)
         radii, depths, rows, tiles_per_gauss = bufs["radii"], bufs["depths"], bufs["rows"], bufs["tiles_per_gauss"]
@@ -296,30 +286,24 @@ class _StepProject(torch.autograd.Function):
         if needs_bwd and W.PREFILL_ENABLED:
             # the per-gaussian gradients the backward returns live behind the gradient rows in ONE zero-filled buffer
             # (_wrapper.GradPrefill: the compositing forward zero-fills it as a side job)
-            need = ctx.needs_input_grad
             prefill = W.GradPrefill()
-            prefill.request = W.prefill_request((
-                ("means", means, need[0]), ("covars", covars, need[1]), ("quats", quats, need[2]), ("scales", scales, need[3]),
-                ("opacities", opacities, need[6]), ("colors", colors, need[7]), ("sh", sh_coeffs, need[8]), ("sh_rest", sh_rest, need[9]))
-                + (W.dyn_prefill_items(ctx.dyn, need, 14) if ctx.dyn is not None else ()))
+            prefill.request = W.prefill_request(W._prefill_table(W._needs(ctx, _StepProject.INPUTS), means, covars, quats, scales, opacities,
+                                                                 colors, sh_coeffs, sh_rest, dyn_ctx))
         try:
             with torch.cuda.device(dev):
                 B.call("gs_step_fwd_begin", sp, stream)
-                (offsets, isect_ids, flatten_ids, render_colors, render_alphas, last_ids, fill, prefill, scratch, plan) = _finish(
+                (offsets, isect_ids, flatten_ids, render_colors, render_alphas, last_ids, grad_rows, prefill, scratch, plan) = _finish(
                     s, sp, stream, bufs, n_sums, C, N, height, width, tile_height, tile_width, dev, needs_bwd, prefill)
         except BaseException:
             _drop_pinned(bufs, n_sums)  # (an error between the two calls: the count kernel may still be storing into it)
             raise
         # ---- node 2's share
         hand.render_colors, hand.render_alphas, hand.last_ids, hand.scratch, hand.plan = render_colors, render_alphas, last_ids, scratch, plan
-        hand.grad_rows = fill[:n_elems * 16].view(C, N, 16) if fill is not None else None
-        hand.offsets, hand.flatten_ids = offsets, flatten_ids
-        # ---- this node's backward is _ProjectRows.backward: same saved tensors, same attributes
-        ctx.save_for_backward(means, covars, quats, scales, viewmats, Ks, opacities, radii, rows, sh_coeffs, sh_rest)
-        ctx.width, ctx.height, ctx.eps2d, ctx.cm, ctx.antialiased = width, height, eps2d, cm, bool(antialiased)
-        ctx.has_colors, ctx.sh_degree = colors is not None, (int(sh_degree) if sh_coeffs is not None else None)
-        ctx.prefill = prefill
-        ctx.mask = (mask_logits, float(mask_cfg[0]), bool(mask_cfg[1])) if mask_logits is not None else None
+        hand.grad_rows, hand.offsets, hand.flatten_ids = grad_rows, offsets, flatten_ids
+        # ---- this node's backward is the operator path's (_wrapper._project_rows_bwd)
+        W._save_projection(ctx, means, covars, quats, scales, viewmats, Ks, opacities, radii, rows, sh_coeffs, sh_rest, colors, width, height,
+                           eps2d, cm, antialiased, sh_degree,
+                           (mask_logits, float(mask_cfg[0]), bool(mask_cfg[1])) if mask_logits is not None else None, prefill, dyn_ctx)
         ctx.mark_non_differentiable(radii, rows, tiles_per_gauss, isect_ids, flatten_ids, offsets)
         ctx.set_materialize_grads(False)
         R = W
@@ -328,28 +312,23 @@ class _StepProject(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_radii, v_means2d, v_depths, v_conics, v_opac, v_colors, v_rows, *_ints):
-        g = W._ProjectRows.backward(ctx, v_radii, v_means2d, v_depths, v_conics, v_opac, v_colors, v_rows)
-        # _ProjectRows' inputs: means, covars, quats, scales, viewmats, Ks, opacities, colors, sh_coeffs, sh_rest, ...
-        head = (g[0], g[1], g[2], g[3], g[4], None, g[6], g[7], g[8], g[9], g[10], None, None, None)
-        return head + tuple(g[22:27]) if ctx.dyn is not None else head
+        g = W._project_rows_bwd(ctx, W._needs(ctx, _StepProject.INPUTS), v_means2d, v_depths, v_conics, v_opac, v_colors)
+        return W._in_order(g, ctx, _StepProject.INPUTS)
 
 
 class _StepComposite(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, cfg, hand):
         width, height, tile_size, absgrad = cfg
-        ctx.grad_rows = hand.grad_rows
-        ctx.plan, ctx.strides = hand.plan, _ROW_STRIDES
-        ctx.save_for_backward(means2d, conics, colors, opacities, backgrounds, None, hand.offsets, hand.flatten_ids, hand.render_alphas,
-                              hand.last_ids, hand.scratch, hand.render_colors)
-        ctx.width, ctx.height, ctx.tile_size, ctx.absgrad, ctx.deterministic = width, height, tile_size, absgrad, False
+        W._save_composite(ctx, means2d, conics, colors, opacities, backgrounds, hand.offsets, hand.flatten_ids, hand.render_colors,
+                          hand.render_alphas, hand.last_ids, hand.scratch, hand.plan, _ROW_STRIDES, hand.grad_rows, width, height, tile_size,
+                          absgrad)
         ctx.set_materialize_grads(False)
         return hand.render_colors, hand.render_alphas
 
     @staticmethod
     def backward(ctx, v_render_colors, v_render_alphas):
-        g = W._RasterizeToPixels.backward(ctx, v_render_colors, v_render_alphas)
-        return (g[0], g[1], g[2], g[3], g[4], None, None)
+        return W._rasterize_bwd(ctx, v_render_colors, v_render_alphas) + (None, None)
 
 
 class _RowsState:
@@ -402,7 +381,7 @@ def rows_abandon(st: Optional[_RowsState]) -> None:
 
 class _StepRowsComposite(torch.autograd.Function):
     """Second half over rows: host sync -> emit + pair sort + offsets -> compositing forward; backward =
-    ``_RasterizeToPixels.backward`` (the gradient rows feed the exchange's backward)."""
+    ``_wrapper._rasterize_bwd`` (the gradient rows feed the exchange's backward)."""
 
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, cfg, st, prefill):
@@ -412,16 +391,13 @@ class _StepRowsComposite(torch.autograd.Function):
         backgrounds = _c(backgrounds)
         s.backgrounds = B.ptr(backgrounds)
         s.width, s.height = width, height
-        needs_bwd = any(ctx.needs_input_grad[:5])
+        needs_bwd = any(W._needs(ctx, W._COMPOSITE_INPUTS).values())
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
-            (offsets, isect_ids, flatten_ids, render_colors, render_alphas, last_ids, fill, prefill, scratch, plan) = _finish(
+            (offsets, isect_ids, flatten_ids, render_colors, render_alphas, last_ids, grad_rows, _, scratch, plan) = _finish(
                 s, ctypes.addressof(s), stream, st.bufs, st.n_sums, C, N, height, width, tile_height, tile_width, dev, needs_bwd, prefill)
-        ctx.grad_rows = fill[:C * N * 16].view(C, N, 16) if fill is not None else None
-        ctx.plan, ctx.strides = plan, _ROW_STRIDES
-        ctx.save_for_backward(means2d, conics, colors, opacities, backgrounds, None, offsets, flatten_ids, render_alphas, last_ids, scratch,
-                              render_colors)
-        ctx.width, ctx.height, ctx.tile_size, ctx.absgrad, ctx.deterministic = width, height, tile_size, absgrad, False
+        W._save_composite(ctx, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, render_colors, render_alphas, last_ids,
+                          scratch, plan, _ROW_STRIDES, grad_rows, width, height, tile_size, absgrad)
         tiles_per_gauss = st.bufs["tiles_per_gauss"]
         ctx.mark_non_differentiable(tiles_per_gauss, isect_ids, flatten_ids, offsets)
         ctx.set_materialize_grads(False)
@@ -430,8 +406,7 @@ class _StepRowsComposite(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_render_colors, v_render_alphas, *_ints):
-        g = W._RasterizeToPixels.backward(ctx, v_render_colors, v_render_alphas)
-        return (g[0], g[1], g[2], g[3], g[4], None, None, None)
+        return W._rasterize_bwd(ctx, v_render_colors, v_render_alphas) + (None, None, None)
 
 
 def rows_composite(st: _RowsState, means2d, conics, colors, opacities, backgrounds, width, height, absgrad, prefill):

@@ -889,8 +889,8 @@ class GradPrefill:
     __slots__ = ("request", "parts")
 
     def __init__(self):
-        self.request = []  # [(key, shape)] filled by _ProjectRows.forward
-        self.parts = {}  # key -> zero-filled tensor, made by _RasterizeToPixels.forward
+        self.request = []  # [(key, shape)] filled by the projection node's forward
+        self.parts = {}  # key -> zero-filled tensor, made by the compositing node's forward (_grad_fill)
 
     def floats(self) -> int:
         return sum(_pad64(math.prod(shape)) for _, shape in self.request)
@@ -994,8 +994,8 @@ def project_rows(
 
 
 def _grad_rows_of(parts, shape, device):
-    """The [C,N,16] gradient-row buffer behind the gradients autograd hands to ``_ProjectRows.backward``.  ``parts`` =
-    [(gradient or None, first column, width)].  When they are the column views ``_RasterizeToPixels.backward`` returns (one
+    """The [C,N,16] gradient-row buffer behind the gradients autograd hands to ``_project_rows_bwd``.  ``parts`` =
+    [(gradient or None, first column, width)].  When they are the column views ``_rasterize_bwd`` returns (one
     buffer, splat-row columns) that buffer is used IN PLACE; anything else (a loss on meta["means2d"] itself, gradients
     autograd had to add up, missing ones) is assembled into a fresh zero-filled buffer."""
     base = None
@@ -1038,45 +1038,127 @@ def _grad_rows_of(parts, shape, device):
     return G.data_ptr(), G
 
 
-def dyn_prefill_items(dyn_ctx, need, first: int):
-    """(key, tensor, wanted) of the four extra inputs of the dynamic route (motion, omega, trbf_center, trbf_scale) for GradPrefill."""
-    _, dt = dyn_ctx
-    return (("motion", dt[0], need[first]), ("omega", dt[1], need[first + 1]), ("trbf_center", dt[2], need[first + 2]),
-            ("trbf_scale", dt[3], need[first + 3]))
+def _needs(ctx, names) -> dict:
+    """{input name: gradient wanted} of an autograd Function whose inputs ``names`` lists in order (None: not differentiable,
+    never looked up)."""
+    return dict(zip(names, ctx.needs_input_grad))
 
 
-def _project_rows_dyn_bwd(ctx, dyn_ctx, need, out, prefilled, g_ptr, g_keep, v_depths):
-    """``_ProjectRows.backward`` of the dynamic route: gs_projection_rows_dyn_bwd = the projection VJP + the slice / activation /
-    STE VJPs for the gaussians some camera saw; returns the gradient tuple in the order of ``_ProjectRows.forward``'s inputs."""
+def _in_order(grads: dict, ctx, names) -> tuple:
+    """Gradients by input name -> the tuple a Function's backward returns, in its own input order."""
+    return tuple(map(grads.get, names[:len(ctx.needs_input_grad)]))
+
+
+def _prefill_table(need, means, covars, quats, scales, opacities, colors, sh_coeffs, sh_rest, dyn) -> list:
+    """(key, tensor or None, wanted) of every per-gaussian gradient a projection-rows node returns, in PREFILL_ORDER: its forward
+    requests the wanted ones (GradPrefill.request), its backward takes them only when it got all of them."""
+    tensors = (means, covars, quats, scales, opacities, colors, sh_coeffs, sh_rest) + (dyn[1] if dyn is not None else ())
+    return [(k, t, need[k]) for k, t in zip(PREFILL_ORDER, tensors)]  # (the four dynamic inputs: only with a dynamic slice)
+
+
+def _save_projection(ctx, means, covars, quats, scales, viewmats, Ks, opacities, radii, rows, sh_coeffs, sh_rest, colors, width, height,
+                     eps2d, cm, antialiased, sh_degree, mask, prefill, dyn) -> None:
+    """The state ``_project_rows_bwd`` reads, for both projection-rows nodes (_ProjectRows and the step driver's _StepProject).
+    ``mask`` = (mask_logits, temperature, binary) or None; ``dyn`` = (DynamicSlice, its bound tensors) or None."""
+    ctx.save_for_backward(means, covars, quats, scales, viewmats, Ks, opacities, radii, rows, sh_coeffs, sh_rest)
+    ctx.width, ctx.height, ctx.eps2d, ctx.cm, ctx.antialiased = width, height, eps2d, cm, bool(antialiased)
+    ctx.has_colors, ctx.sh_degree = colors is not None, (int(sh_degree) if sh_coeffs is not None else None)
+    ctx.mask, ctx.prefill, ctx.dyn = mask, prefill, dyn
+
+
+def _project_rows_bwd(ctx, need, v_means2d, v_depths, v_conics, v_opac_cn, v_colors_cn) -> dict:
+    """Backward of a projection-rows node (the state of ``_save_projection``): the projection VJP (+ the SH VJP, or on the dynamic
+    route the slice / activation / STE VJPs) -> {input name: gradient}.  ``need`` = {input name: gradient wanted}."""
     means, covars, quats, scales, viewmats, Ks, opacities, radii, rows, sh_coeffs, sh_rest = ctx.saved_tensors
-    dyn, dt = dyn_ctx
-    motion, omega, center, tscale = dt
     C, N = viewmats.shape[0], means.shape[0]
-    f = ctx.dyn_first
-    if need[4]:
-        raise RuntimeError("rasterization(dynamic=...): camera-pose gradients are not available on the fused dynamic route")
+    dev = means.device
+    parts = [(v_means2d, ROW_MEAN2D, 2), (v_conics, ROW_CONIC, 3), (v_opac_cn, ROW_OPACITY, 1)]
+    if ctx.has_colors or sh_coeffs is not None:
+        parts.append((v_colors_cn, ROW_COLOR, 3))
+    g_ptr, g_keep = _grad_rows_of(parts, (C, N), dev)
+    # outputs the compositing forward allocated and zero-filled for this node (GradPrefill): all of them or none
+    pre = ctx.prefill.take() if ctx.prefill is not None else {}
+    want = [k for k, t, w in _prefill_table(need, means, covars, quats, scales, opacities, True if ctx.has_colors else None, sh_coeffs,
+                                            sh_rest, ctx.dyn) if t is not None and w]
+    prefilled = bool(pre) and all(k in pre for k in want) and (sh_coeffs is None or (need["sh"] and (sh_rest is None or need["sh_rest"])))
+    if not prefilled:
+        pre = {}
+
+    def out(key, like):
+        return pre[key] if prefilled else torch.empty_like(like)
+
+    if ctx.dyn is not None:
+        # gs_projection_rows_dyn_bwd: the projection VJP + the slice / activation / STE VJPs for the gaussians some camera saw
+        dyn, dt = ctx.dyn
+        if need["viewmats"]:
+            raise RuntimeError("rasterization(dynamic=...): camera-pose gradients are not available on the fused dynamic route")
+        v_depths = _f32c(v_depths) if v_depths is not None else None
+        g = {k: out(k, t) if need[k] else None for k, t in (("means", means), ("quats", quats), ("scales", scales), ("opacities", opacities))
+             + tuple(zip(("motion", "omega", "trbf_center", "trbf_scale"), dt))}
+        g["colors"] = (pre["colors"] if prefilled else torch.empty((N, 3), dtype=torch.float32, device=dev)) \
+            if (ctx.has_colors and need["colors"]) else None
+        with _device_of(means):
+            B.call("gs_projection_rows_dyn_bwd", C, N, B.ptr(means), B.ptr(quats), B.ptr(scales), *dyn.c_args(dt), B.ptr(viewmats), B.ptr(Ks),
+                   int(ctx.width), int(ctx.height), float(ctx.eps2d), ctx.cm, B.ptr(radii), B.ptr(rows), g_ptr, B.ptr(v_depths), B.ptr(opacities),
+                   int(ctx.antialiased), B.ptr(g["means"]), B.ptr(g["quats"]), B.ptr(g["scales"]), B.ptr(g["motion"]), B.ptr(g["omega"]),
+                   B.ptr(g["trbf_center"]), B.ptr(g["trbf_scale"]), B.ptr(g["opacities"]), B.ptr(g["colors"]), int(prefilled), _stream(means))
+        del g_keep
+        return g
+
+    v_sh = v_rest = v_means_add = v_mask = None
+    mask = ctx.mask
+    mask_args = (None, 1.0, 0, None)
+    sh_args = (None, None, 0, 0, None, None)
+    if sh_coeffs is not None:
+        # the colour columns of the gradient rows go back through the SH evaluation (clamp gate from the colours in the
+        # rows); its d/d means (view directions) is added to v_means.  Vectorisable rows and fixed poses: inside the
+        # projection backward's own pass (one launch, one pass over radii / means / the two row buffers); otherwise by
+        # gs_sh_view_bwd first, whose v_means the projection kernel then adds while it writes its own
+        K = sh_coeffs.shape[1] + (sh_rest.shape[1] if sh_rest is not None else 0)
+        v_sh = out("sh", sh_coeffs)
+        v_rest = out("sh_rest", sh_rest) if sh_rest is not None else None
+        fused = (_FUSE_SH_BWD and (3 * K) % 4 == 0 and not need["viewmats"] and v_sh.data_ptr() % 16 == 0
+                 and (v_rest is None or v_rest.data_ptr() % 16 == 0) and (sh_rest is not None or sh_coeffs.data_ptr() % 16 == 0))
+        if mask is not None:
+            if not fused:
+                raise RuntimeError("project_rows: the fused shN mask needs the fused SH backward (3 K % 4 == 0, aligned rows, fixed poses)")
+            if need["mask_logits"] and not mask[2]:
+                v_mask = torch.empty_like(mask[0])
+            mask_args = (B.ptr(mask[0]), mask[1], int(mask[2]), B.ptr(v_mask))
+        if fused:
+            sh_args = (B.ptr(sh_coeffs), B.ptr(sh_rest), K, ctx.sh_degree, B.ptr(v_sh), B.ptr(v_rest))
+        else:
+            v_means_add = torch.empty_like(means) if need["means"] else None
+            with _device_of(means):
+                B.call("gs_sh_view_bwd", C, N, K, ctx.sh_degree, B.ptr(means), B.ptr(viewmats), 1, B.ptr(sh_coeffs), B.ptr(sh_rest),
+                       B.ptr(radii), rows.data_ptr() + 4 * ROW_COLOR, ROW, g_ptr + 4 * ROW_COLOR, ROW, B.ptr(v_sh), B.ptr(v_rest),
+                       B.ptr(v_means_add), None, 0, None, int(prefilled), _stream(means))
     v_depths = _f32c(v_depths) if v_depths is not None else None
-    v_means = out("means", means) if need[0] else None
-    v_quats = out("quats", quats) if need[2] else None
-    v_scales = out("scales", scales) if need[3] else None
-    v_opac = out("opacities", opacities) if need[6] else None
-    v_colors = (out("colors", torch.empty(0)) if prefilled else torch.empty((N, 3), dtype=torch.float32, device=means.device)) \
-        if (ctx.has_colors and need[7]) else None
-    v_motion = out("motion", motion) if need[f] else None
-    v_omega = out("omega", omega) if need[f + 1] else None
-    v_center = out("trbf_center", center) if need[f + 2] else None
-    v_tscale = out("trbf_scale", tscale) if need[f + 3] else None
+    # rows are fully written by the kernel -> empty, not zeros (prefilled: only the visible gaussians' rows are)
+    g = {"means": out("means", means) if need["means"] else None,
+         "covars": out("covars", covars) if (covars is not None and need["covars"]) else None,
+         "quats": out("quats", quats) if (quats is not None and need["quats"]) else None,
+         "scales": out("scales", scales) if (scales is not None and need["scales"]) else None,
+         "viewmats": torch.zeros_like(viewmats) if need["viewmats"] else None,
+         "opacities": out("opacities", opacities) if need["opacities"] else None,
+         "colors": (pre["colors"] if prefilled else torch.empty((N, 3), dtype=torch.float32, device=dev))
+         if (ctx.has_colors and need["colors"]) else None,
+         "sh": v_sh if need["sh"] else None, "sh_rest": v_rest if need["sh_rest"] else None, "mask_logits": v_mask}
     with _device_of(means):
-        B.call("gs_projection_rows_dyn_bwd", C, N, B.ptr(means), B.ptr(quats), B.ptr(scales), *dyn.c_args(dt), B.ptr(viewmats), B.ptr(Ks),
-               int(ctx.width), int(ctx.height), float(ctx.eps2d), ctx.cm, B.ptr(radii), B.ptr(rows), g_ptr, B.ptr(v_depths), B.ptr(opacities),
-               int(ctx.antialiased), B.ptr(v_means), B.ptr(v_quats), B.ptr(v_scales), B.ptr(v_motion), B.ptr(v_omega), B.ptr(v_center),
-               B.ptr(v_tscale), B.ptr(v_opac), B.ptr(v_colors), int(prefilled), _stream(means))
+        B.call("gs_projection_rows_bwd", C, N, B.ptr(means), B.ptr(covars), B.ptr(quats), B.ptr(scales),
+               B.ptr(viewmats), B.ptr(Ks), int(ctx.width), int(ctx.height), float(ctx.eps2d), ctx.cm,
+               B.ptr(radii), B.ptr(rows), g_ptr, B.ptr(v_depths), B.ptr(opacities), int(ctx.antialiased),
+               B.ptr(g["means"]), B.ptr(g["covars"]), B.ptr(g["quats"]), B.ptr(g["scales"]), B.ptr(g["viewmats"]), B.ptr(g["opacities"]),
+               B.ptr(g["colors"]), B.ptr(v_means_add) if g["means"] is not None else None, *sh_args, *mask_args, int(prefilled),
+               _stream(means))
     del g_keep
-    return (v_means, None, v_quats, v_scales, None, None, v_opac, v_colors, None, None, None) + (None,) * 11 + (
-        v_motion, v_omega, v_center, v_tscale, None)
+    return g
 
 
 class _ProjectRows(torch.autograd.Function):
+    INPUTS = ("means", "covars", "quats", "scales", "viewmats", None, "opacities", "colors", "sh", "sh_rest", "mask_logits") + (None,) * 11 \
+        + ("motion", "omega", "trbf_center", "trbf_scale", None)
+
     @staticmethod
     def forward(ctx, means, covars, quats, scales, viewmats, Ks, opacities, colors, sh_coeffs, sh_rest, mask_logits, width, height,
                 eps2d, near_plane, far_plane, radius_clip, antialiased, camera_model="pinhole", sh_degree=None, prefill=None,
@@ -1093,7 +1175,7 @@ class _ProjectRows(torch.autograd.Function):
         depths = torch.empty((C, N), dtype=torch.float32, device=dev)
         rows = torch.empty((C, N, ROW), dtype=torch.float32, device=dev)  # (torch's allocator aligns to 512 bytes)
         cm = _CAMERA_MODELS[camera_model]
-        ctx.dyn = None
+        dyn_ctx = None
         if dyn is not None:
             # dynamic splats: quantizer -> activation -> temporal slice in the projection's load phase (csrc/projection_dyn.hip)
             dtens = dyn.bind(quats, scales, opacities, colors, dyn_motion, dyn_omega, dyn_center, dyn_tscale)
@@ -1102,7 +1184,7 @@ class _ProjectRows(torch.autograd.Function):
                        B.ptr(Ks), int(width), int(height), float(eps2d), float(near_plane), float(far_plane), float(radius_clip), cm,
                        B.ptr(opacities), B.ptr(colors), int(bool(antialiased)), 0, 0, 0, None, None, B.ptr(radii), B.ptr(depths),
                        B.ptr(rows), _stream(means))
-            ctx.dyn = (dyn, dtens)
+            dyn_ctx = (dyn, dtens)
         else:
           with _device_of(means):
             B.call("gs_projection_rows_fwd", C, N, B.ptr(means), B.ptr(covars), B.ptr(quats), B.ptr(scales),
@@ -1110,21 +1192,15 @@ class _ProjectRows(torch.autograd.Function):
                    float(far_plane), float(radius_clip), cm, B.ptr(opacities), B.ptr(colors), int(bool(antialiased)),
                    B.ptr(sh_coeffs), B.ptr(sh_rest), sh_K, int(sh_degree or 0), B.ptr(mask_logits), float(m_temp), int(m_bin),
                    0, 0, 0, None, None, B.ptr(radii), B.ptr(depths), B.ptr(rows), _stream(means))
-        ctx.save_for_backward(means, covars, quats, scales, viewmats, Ks, opacities, radii, rows, sh_coeffs, sh_rest)
-        ctx.mask = (mask_logits, float(m_temp), bool(m_bin)) if mask_logits is not None else None
-        ctx.width, ctx.height, ctx.eps2d, ctx.cm, ctx.antialiased = width, height, eps2d, cm, bool(antialiased)
-        ctx.has_colors, ctx.sh_degree = colors is not None, (int(sh_degree) if sh_coeffs is not None else None)
-        ctx.prefill = None
-        ctx.dyn_first = 22  # position of dyn_motion among this Function's inputs (_StepProject overrides it)
-        need = ctx.needs_input_grad
-        if prefill is not None and (any(need[:10]) or (dyn is not None and any(need[22:26]))) and not need[4] and N > 0:
+        need = _needs(ctx, _ProjectRows.INPUTS)
+        if prefill is not None and not need["viewmats"] and N > 0:
             # what the backward will return per gaussian, for the compositing forward to allocate and zero-fill
-            req = prefill_request((("means", means, need[0]), ("covars", covars, need[1]), ("quats", quats, need[2]),
-                                   ("scales", scales, need[3]), ("opacities", opacities, need[6]), ("colors", colors, need[7]),
-                                   ("sh", sh_coeffs, need[8]), ("sh_rest", sh_rest, need[9]))
-                                  + (dyn_prefill_items(ctx.dyn, need, 22) if ctx.dyn is not None else ()))
-            prefill.request = req
-            ctx.prefill = prefill
+            prefill.request = prefill_request(_prefill_table(need, means, covars, quats, scales, opacities, colors, sh_coeffs, sh_rest, dyn_ctx))
+        else:
+            prefill = None
+        _save_projection(ctx, means, covars, quats, scales, viewmats, Ks, opacities, radii, rows, sh_coeffs, sh_rest, colors, width, height,
+                         eps2d, cm, antialiased, sh_degree, (mask_logits, float(m_temp), bool(m_bin)) if mask_logits is not None else None,
+                         prefill, dyn_ctx)
         ctx.mark_non_differentiable(radii, rows)
         ctx.set_materialize_grads(False)  # unused outputs (depths in RGB mode, ...) arrive as None, not as zero tensors
         has_col = colors is not None or sh_coeffs is not None
@@ -1133,84 +1209,8 @@ class _ProjectRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, v_radii, v_means2d, v_depths, v_conics, v_opac_cn, v_colors_cn, v_rows):
-        means, covars, quats, scales, viewmats, Ks, opacities, radii, rows, sh_coeffs, sh_rest = ctx.saved_tensors
-        C, N = viewmats.shape[0], means.shape[0]
-        dev = means.device
-        parts = [(v_means2d, ROW_MEAN2D, 2), (v_conics, ROW_CONIC, 3), (v_opac_cn, ROW_OPACITY, 1)]
-        if ctx.has_colors or sh_coeffs is not None:
-            parts.append((v_colors_cn, ROW_COLOR, 3))
-        g_ptr, g_keep = _grad_rows_of(parts, (C, N), dev)
-        need = ctx.needs_input_grad
-        # outputs the compositing forward allocated and zero-filled for this node (GradPrefill): all of them or none
-        pre = ctx.prefill.take() if ctx.prefill is not None else {}
-        want = [k for k, t, f in (("means", means, need[0]), ("covars", covars, need[1]), ("quats", quats, need[2]),
-                                  ("scales", scales, need[3]), ("opacities", opacities, need[6]),
-                                  ("colors", True if ctx.has_colors else None, need[7]), ("sh", sh_coeffs, need[8]),
-                                  ("sh_rest", sh_rest, need[9])) if t is not None and f]
-        dyn = getattr(ctx, "dyn", None)
-        if dyn is not None:
-            want += [k for k, t, f in dyn_prefill_items(dyn, need, ctx.dyn_first) if f]
-        prefilled = bool(pre) and all(k in pre for k in want) and (sh_coeffs is None or (need[8] and (sh_rest is None or need[9])))
-        if not prefilled:
-            pre = {}
-
-        def out(key, like):
-            return pre[key] if prefilled else torch.empty_like(like)
-
-        if dyn is not None:
-            return _project_rows_dyn_bwd(ctx, dyn, need, out, prefilled, g_ptr, g_keep, v_depths)
-
-        v_sh = v_rest = v_means_add = v_mask = None
-        mask = getattr(ctx, "mask", None)
-        mask_args = (None, 1.0, 0, None)
-        sh_args = (None, None, 0, 0, None, None)
-        if sh_coeffs is not None:
-            # the colour columns of the gradient rows go back through the SH evaluation (clamp gate from the colours in the
-            # rows); its d/d means (view directions) is added to v_means.  Vectorisable rows and fixed poses: inside the
-            # projection backward's own pass (one launch, one pass over radii / means / the two row buffers); otherwise by
-            # gs_sh_view_bwd first, whose v_means the projection kernel then adds while it writes its own
-            K = sh_coeffs.shape[1] + (sh_rest.shape[1] if sh_rest is not None else 0)
-            v_sh = out("sh", sh_coeffs)
-            v_rest = out("sh_rest", sh_rest) if sh_rest is not None else None
-            fused = (_FUSE_SH_BWD and (3 * K) % 4 == 0 and not need[4] and v_sh.data_ptr() % 16 == 0 and (v_rest is None or v_rest.data_ptr() % 16 == 0)
-                     and (sh_rest is not None or sh_coeffs.data_ptr() % 16 == 0))
-            if mask is not None:
-                if not fused:
-                    raise RuntimeError("project_rows: the fused shN mask needs the fused SH backward (3 K % 4 == 0, aligned rows, fixed poses)")
-                if need[10] and not mask[2]:
-                    v_mask = torch.empty_like(mask[0])
-                mask_args = (B.ptr(mask[0]), mask[1], int(mask[2]), B.ptr(v_mask))
-            if fused:
-                sh_args = (B.ptr(sh_coeffs), B.ptr(sh_rest), K, ctx.sh_degree, B.ptr(v_sh), B.ptr(v_rest))
-            else:
-                v_means_add = torch.empty_like(means) if need[0] else None
-                with _device_of(means):
-                    B.call("gs_sh_view_bwd", C, N, K, ctx.sh_degree, B.ptr(means), B.ptr(viewmats), 1, B.ptr(sh_coeffs), B.ptr(sh_rest),
-                           B.ptr(radii), rows.data_ptr() + 4 * ROW_COLOR, ROW, g_ptr + 4 * ROW_COLOR, ROW, B.ptr(v_sh), B.ptr(v_rest),
-                           B.ptr(v_means_add), None, 0, None, int(prefilled), _stream(means))
-        v_depths = _f32c(v_depths) if v_depths is not None else None
-        # rows are fully written by the kernel -> empty, not zeros (prefilled: only the visible gaussians' rows are)
-        v_means = out("means", means) if need[0] else None
-        v_covars = out("covars", covars) if (covars is not None and need[1]) else None
-        v_quats = out("quats", quats) if (quats is not None and need[2]) else None
-        v_scales = out("scales", scales) if (scales is not None and need[3]) else None
-        v_viewmats = torch.zeros_like(viewmats) if need[4] else None
-        v_opac = out("opacities", opacities) if need[6] else None
-        v_colors = (pre["colors"] if prefilled else torch.empty((N, 3), dtype=torch.float32, device=dev)) if (ctx.has_colors and need[7]) else None
-        with _device_of(means):
-            B.call("gs_projection_rows_bwd", C, N, B.ptr(means), B.ptr(covars), B.ptr(quats), B.ptr(scales),
-                   B.ptr(viewmats), B.ptr(Ks), int(ctx.width), int(ctx.height), float(ctx.eps2d), ctx.cm,
-                   B.ptr(radii), B.ptr(rows), g_ptr, B.ptr(v_depths), B.ptr(opacities), int(ctx.antialiased),
-                   B.ptr(v_means), B.ptr(v_covars), B.ptr(v_quats), B.ptr(v_scales), B.ptr(v_viewmats), B.ptr(v_opac),
-                   B.ptr(v_colors), B.ptr(v_means_add) if v_means is not None else None, *sh_args, *mask_args, int(prefilled),
-                   _stream(means))
-        if sh_coeffs is not None:
-            if not need[8]:
-                v_sh = None
-            if not need[9]:
-                v_rest = None
-        del g_keep
-        return (v_means, v_covars, v_quats, v_scales, v_viewmats, None, v_opac, v_colors, v_sh, v_rest, v_mask) + (None,) * 11
+        g = _project_rows_bwd(ctx, _needs(ctx, _ProjectRows.INPUTS), v_means2d, v_depths, v_conics, v_opac_cn, v_colors_cn)
+        return _in_order(g, ctx, _ProjectRows.INPUTS)
 
 
 class _FullyFusedProjectionPacked(torch.autograd.Function):
@@ -1847,6 +1847,43 @@ def rasterize_to_pixels(
     )
 
 
+_COMPOSITE_INPUTS = ("means2d", "conics", "colors", "opacities", "backgrounds")  # the leading inputs of every compositing node
+
+
+def _grad_fill(n_elems: int, channels: int, prefill: Optional[GradPrefill], dev):
+    """The one buffer a compositing forward zero-fills as the side job of its tile workgroups (``zero_fill`` of gs_rasterize_fwd):
+    the packed gradient rows [n_elems,16] of its backward; 5..32 channels: the colour gradients [n_elems, channels] behind them
+    (the geometry gradients keep their 16-float rows, which the projection backward reads in place); then the per-gaussian
+    gradients the projection node asked for (GradPrefill) -> (fill, grad_rows, grad_colors or None, the carved prefill or None), the
+    two gradient blocks as flat slices of ``fill`` for the caller to shape."""
+    extra = prefill.floats() if prefill is not None else 0
+    if extra:
+        extra += 64  # slack behind the last piece (a multi-GPU reduction rounds the span of all pieces up into it)
+    wide = _pad64(n_elems * channels) if channels > 4 else 0
+    fill = torch.empty(n_elems * 16 + wide + extra, dtype=torch.float32, device=dev)
+    grad_colors = fill[n_elems * 16:n_elems * 16 + n_elems * channels] if wide else None
+    if extra:
+        prefill.carve(fill, n_elems * 16 + wide)
+    return fill, fill[:n_elems * 16], grad_colors, prefill if extra else None
+
+
+def _save_composite(ctx, means2d, conics, colors, opacities, backgrounds, isect_offsets, flatten_ids, render_colors, render_alphas, last_ids,
+                    scratch, plan, strides, grad_rows, width, height, tile_size, absgrad, grad_colors=None, deterministic=False,
+                    masks=None) -> None:
+    """The state ``_rasterize_bwd`` reads, for every compositing node (_RasterizeToPixels, _StepComposite, _StepRowsComposite).
+    ``grad_rows`` / ``grad_colors`` (zero-filled by the forward, ``_grad_fill``) are consumed by the first backward; a repeated
+    one (retain_graph) fills its own.  ``plan`` / ``strides``: host structs, the backward runs under the forward's plan and
+    layout.  ``scratch`` carries the forward checkpoints of the depth-segmented backward, which rebuilds "colour behind the
+    segment" from the FINAL render (B = v_out . (colour_final - colour_ckpt)), so the output is saved through
+    save_for_backward: autograd then version-checks it and an in-place edit of the returned image before backward() raises
+    instead of silently corrupting the gradients (the reference does not need its output in the backward, so this is the one
+    place where in-place post-processing must become out-of-place)."""
+    ctx.save_for_backward(means2d, conics, colors, opacities, backgrounds, masks, isect_offsets, flatten_ids, render_alphas, last_ids,
+                          scratch, render_colors)
+    ctx.plan, ctx.strides, ctx.grad_rows, ctx.grad_colors = plan, strides, grad_rows, grad_colors
+    ctx.width, ctx.height, ctx.tile_size, ctx.absgrad, ctx.deterministic = width, height, tile_size, absgrad, bool(deterministic)
+
+
 class _RasterizeToPixels(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, masks, width, height, tile_size,
@@ -1868,28 +1905,18 @@ class _RasterizeToPixels(torch.autograd.Function):
         # 1080p): only ask for them when a backward can follow
         # (ctx.needs_input_grad says True for parameters even under torch.no_grad(), where no backward can follow: the caller's
         # grad mode comes along as an argument -- inside forward() it always reads False)
-        needs_bwd = bool(grad_mode) and any(ctx.needs_input_grad[:5])
+        needs_bwd = bool(grad_mode) and any(_needs(ctx, _COMPOSITE_INPUTS).values())
         with _device_of(means2d):
             plan, sb = _raster_plan(C * tile_height * tile_width, n_isects, channels, forward_only=not needs_bwd)
             scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
             # the packed gradient rows of the backward ([n_elems,16], accumulated with atomics) are zero-filled by THIS
             # launch, as a side job of the tile workgroups: no fill pass in the backward
-            grad_rows = fill = None
-            ctx.grad_colors = None
+            grad_rows = grad_colors = fill = None
             if needs_bwd and channels <= _FAST_MAX_CHANNELS and n_elems > 0:
-                # (+ the per-gaussian gradient tensors the projection node asked for, GradPrefill: one buffer, one fill)
-                extra = prefill.floats() if prefill is not None else 0
-                if extra:
-                    extra += 64  # slack behind the last piece (a multi-GPU reduction rounds the span of all pieces up into it)
-                # 5..32 channels: the geometry gradients keep their 16-float rows (the projection backward reads them in
-                # place), the colour gradients get a dense [n_elems, channels] array behind them -- same buffer, same fill
-                wide = _pad64(n_elems * channels) if channels > 4 else 0
-                fill = torch.empty(n_elems * 16 + wide + extra, dtype=torch.float32, device=dev)
-                grad_rows = fill[:n_elems * 16].view(opacities.shape + (16,))
-                if wide:
-                    ctx.grad_colors = fill[n_elems * 16:n_elems * 16 + n_elems * channels].view(opacities.shape + (channels,))
-                if extra:
-                    prefill.carve(fill, n_elems * 16 + wide)
+                fill, grad_rows, grad_colors, _ = _grad_fill(n_elems, channels, prefill, dev)
+                grad_rows = grad_rows.view(opacities.shape + (16,))
+                if grad_colors is not None:
+                    grad_colors = grad_colors.view(opacities.shape + (channels,))
             B.call("gs_rasterize_fwd", C, n_elems, n_isects, channels, B.ptr(means2d), B.ptr(conics), B.ptr(colors),
                    B.ptr(opacities), ctypes.addressof(strides) if strides is not None else None, B.ptr(backgrounds), B.ptr(m8),
                    width, height, tile_size, tile_width,
@@ -1897,80 +1924,77 @@ class _RasterizeToPixels(torch.autograd.Function):
                    B.ptr(render_alphas), B.ptr(last_ids), ctypes.addressof(plan) if plan is not None else None,
                    B.ptr(scratch) if plan is not None else None,
                    B.ptr(fill), fill.numel() * 4 if fill is not None else 0, _stream(means2d))
-        ctx.grad_rows = grad_rows  # consumed by the first backward; a repeated one (retain_graph) fills its own
-        ctx.plan, ctx.strides = plan, strides  # host structs: the backward runs under the forward's plan and layout
-        # scratch carries the forward checkpoints of the depth-segmented backward.  The segmented backward rebuilds
-        # "colour behind the segment" from the FINAL render (B = v_out . (colour_final - colour_ckpt)), so the output is
-        # saved through save_for_backward: autograd then version-checks it and an in-place edit of the returned image
-        # before backward() raises instead of silently corrupting the gradients (the reference does not need its
-        # output in the backward, so this is the one place where in-place post-processing must become out-of-place).
-        ctx.save_for_backward(means2d, conics, colors, opacities, backgrounds, masks, isect_offsets, flatten_ids,
-                              render_alphas, last_ids, scratch, render_colors)
-        ctx.width, ctx.height, ctx.tile_size, ctx.absgrad = width, height, tile_size, absgrad
         if deterministic and channels > 4:
             raise RuntimeError("rasterize_to_pixels(deterministic=True) supports up to 4 channels")
-        ctx.deterministic = bool(deterministic)
+        _save_composite(ctx, means2d, conics, colors, opacities, backgrounds, isect_offsets, flatten_ids, render_colors, render_alphas, last_ids,
+                        scratch, plan, strides, grad_rows, width, height, tile_size, absgrad, grad_colors, deterministic, masks)
         ctx.set_materialize_grads(False)
         return render_colors, render_alphas
 
     @staticmethod
     def backward(ctx, v_render_colors: Tensor, v_render_alphas: Tensor):
-        (means2d, conics, colors, opacities, backgrounds, masks, isect_offsets, flatten_ids, render_alphas,
-         last_ids, scratch, render_colors) = ctx.saved_tensors
-        C, tile_height, tile_width = isect_offsets.shape
-        channels = colors.shape[-1]
-        n_elems = opacities.numel()
-        n_isects = flatten_ids.shape[0]
-        # undefined upstream gradients arrive as None (set_materialize_grads(False) in forward): the kernel takes a
-        # NULL v_render_alphas, which saves a [C,H,W] zero-fill and one of the 12 per-pixel loads of every work item
-        if v_render_colors is None:
-            v_render_colors = torch.zeros_like(render_colors)
-        v_render_colors, vrc_pix, vrc_ch = _pixel_strided(v_render_colors)
-        v_render_alphas = _f32c(v_render_alphas) if v_render_alphas is not None else None
-        # accumulated with atomics -> zero-filled.  Up to 4 channels: ONE packed [n_elems,16] buffer
-        # (64-byte row per splat: vx vy | ca cb cc | o | c0..c3 | ax ay) so that a splat's whole
-        # gradient is one L2 request; the tensors handed to autograd are views of it.
-        packed = channels <= _FAST_MAX_CHANNELS
-        # deterministic mode: fixed-point sums in an int64 buffer of their own; the float rows are then WRITTEN by a second kernel
-        det = torch.zeros((n_elems, 2, 12), dtype=torch.int64, device=means2d.device) if (ctx.deterministic and n_elems > 0) else None
-        if packed:
-            P, ctx.grad_rows = ctx.grad_rows, None
-            if P is None:
-                # (the deterministic route's finalize kernel WRITES every row -- except when there is nothing to composite:
-                # gs_rasterize_bwd returns before it with n_isects == 0, and the rows must then be zeros, not stale memory)
-                P = (torch.empty if (det is not None and n_isects > 0) else torch.zeros)(
-                    opacities.shape + (16,), dtype=torch.float32, device=means2d.device)
-            v_means2d, v_conics, v_opacities = P[..., 0:2], P[..., 2:5], P[..., 5]
-            v_means2d_abs = P[..., 10:12] if ctx.absgrad else None
-            if channels <= 4:
-                v_colors = P[..., 6:6 + channels]
-                out_ptrs = (B.ptr(P) if ctx.absgrad else None, B.ptr(P), None, None, None)
-            else:  # geometry rows + the colour gradients in their own dense array (packed16 = 2)
-                v_colors, ctx.grad_colors = ctx.grad_colors, None
-                if v_colors is None:
-                    v_colors = torch.zeros(opacities.shape + (channels,), dtype=torch.float32, device=means2d.device)
-                out_ptrs = (B.ptr(P) if ctx.absgrad else None, B.ptr(P), None, B.ptr(v_colors), None)
-        else:
-            v_means2d = torch.zeros_like(means2d)
-            v_conics = torch.zeros_like(conics)
-            v_colors = torch.zeros_like(colors)
-            v_opacities = torch.zeros_like(opacities)
-            v_means2d_abs = torch.zeros_like(means2d) if ctx.absgrad else None
-            out_ptrs = (B.ptr(v_means2d_abs), B.ptr(v_means2d), B.ptr(v_conics), B.ptr(v_colors), B.ptr(v_opacities))
-        m8 = masks.view(torch.uint8) if masks is not None else None
-        plan, strides = ctx.plan, ctx.strides
-        with _device_of(means2d):
-            B.call("gs_rasterize_bwd", C, n_elems, n_isects, channels, B.ptr(means2d), B.ptr(conics), B.ptr(colors),
-                   B.ptr(opacities), ctypes.addressof(strides) if strides is not None else None, B.ptr(backgrounds), B.ptr(m8),
-                   ctx.width, ctx.height, ctx.tile_size,
-                   tile_width, tile_height, B.ptr(isect_offsets), B.ptr(flatten_ids), B.ptr(render_colors),
-                   B.ptr(render_alphas), B.ptr(last_ids), B.ptr(v_render_colors), B.ptr(v_render_alphas), vrc_pix, vrc_ch, *out_ptrs,
-                   (1 if channels <= 4 else 2) if packed else 0, B.ptr(det), ctypes.addressof(plan) if plan is not None else None,
-                   B.ptr(scratch) if plan is not None else None, _stream(means2d))
-        if ctx.absgrad:
-            means2d.absgrad = v_means2d_abs
-        if ctx.needs_input_grad[4]:
-            v_backgrounds = (v_render_colors * (1.0 - render_alphas).float()).sum(dim=(1, 2))
-        else:
-            v_backgrounds = None
-        return (v_means2d, v_conics, v_colors, v_opacities, v_backgrounds) + (None,) * 10
+        return _rasterize_bwd(ctx, v_render_colors, v_render_alphas) + (None,) * 10
+
+
+def _rasterize_bwd(ctx, v_render_colors: Optional[Tensor], v_render_alphas: Optional[Tensor]):
+    """Backward of a compositing node (the state of ``_save_composite``) -> (v_means2d, v_conics, v_colors, v_opacities,
+    v_backgrounds)."""
+    (means2d, conics, colors, opacities, backgrounds, masks, isect_offsets, flatten_ids, render_alphas,
+     last_ids, scratch, render_colors) = ctx.saved_tensors
+    C, tile_height, tile_width = isect_offsets.shape
+    channels = colors.shape[-1]
+    n_elems = opacities.numel()
+    n_isects = flatten_ids.shape[0]
+    # undefined upstream gradients arrive as None (set_materialize_grads(False) in forward): the kernel takes a
+    # NULL v_render_alphas, which saves a [C,H,W] zero-fill and one of the 12 per-pixel loads of every work item
+    if v_render_colors is None:
+        v_render_colors = torch.zeros_like(render_colors)
+    v_render_colors, vrc_pix, vrc_ch = _pixel_strided(v_render_colors)
+    v_render_alphas = _f32c(v_render_alphas) if v_render_alphas is not None else None
+    # accumulated with atomics -> zero-filled.  Up to 4 channels: ONE packed [n_elems,16] buffer
+    # (64-byte row per splat: vx vy | ca cb cc | o | c0..c3 | ax ay) so that a splat's whole
+    # gradient is one L2 request; the tensors handed to autograd are views of it.
+    packed = channels <= _FAST_MAX_CHANNELS
+    # deterministic mode: fixed-point sums in an int64 buffer of their own; the float rows are then WRITTEN by a second kernel
+    det = torch.zeros((n_elems, 2, 12), dtype=torch.int64, device=means2d.device) if (ctx.deterministic and n_elems > 0) else None
+    if packed:
+        P, ctx.grad_rows = ctx.grad_rows, None
+        if P is None:
+            # (the deterministic route's finalize kernel WRITES every row -- except when there is nothing to composite:
+            # gs_rasterize_bwd returns before it with n_isects == 0, and the rows must then be zeros, not stale memory)
+            P = (torch.empty if (det is not None and n_isects > 0) else torch.zeros)(
+                opacities.shape + (16,), dtype=torch.float32, device=means2d.device)
+        v_means2d, v_conics, v_opacities = P[..., 0:2], P[..., 2:5], P[..., 5]
+        v_means2d_abs = P[..., 10:12] if ctx.absgrad else None
+        if channels <= 4:
+            v_colors = P[..., 6:6 + channels]
+            out_ptrs = (B.ptr(P) if ctx.absgrad else None, B.ptr(P), None, None, None)
+        else:  # geometry rows + the colour gradients in their own dense array (packed16 = 2)
+            v_colors, ctx.grad_colors = ctx.grad_colors, None
+            if v_colors is None:
+                v_colors = torch.zeros(opacities.shape + (channels,), dtype=torch.float32, device=means2d.device)
+            out_ptrs = (B.ptr(P) if ctx.absgrad else None, B.ptr(P), None, B.ptr(v_colors), None)
+    else:
+        v_means2d = torch.zeros_like(means2d)
+        v_conics = torch.zeros_like(conics)
+        v_colors = torch.zeros_like(colors)
+        v_opacities = torch.zeros_like(opacities)
+        v_means2d_abs = torch.zeros_like(means2d) if ctx.absgrad else None
+        out_ptrs = (B.ptr(v_means2d_abs), B.ptr(v_means2d), B.ptr(v_conics), B.ptr(v_colors), B.ptr(v_opacities))
+    m8 = masks.view(torch.uint8) if masks is not None else None
+    plan, strides = ctx.plan, ctx.strides
+    with _device_of(means2d):
+        B.call("gs_rasterize_bwd", C, n_elems, n_isects, channels, B.ptr(means2d), B.ptr(conics), B.ptr(colors),
+               B.ptr(opacities), ctypes.addressof(strides) if strides is not None else None, B.ptr(backgrounds), B.ptr(m8),
+               ctx.width, ctx.height, ctx.tile_size,
+               tile_width, tile_height, B.ptr(isect_offsets), B.ptr(flatten_ids), B.ptr(render_colors),
+               B.ptr(render_alphas), B.ptr(last_ids), B.ptr(v_render_colors), B.ptr(v_render_alphas), vrc_pix, vrc_ch, *out_ptrs,
+               (1 if channels <= 4 else 2) if packed else 0, B.ptr(det), ctypes.addressof(plan) if plan is not None else None,
+               B.ptr(scratch) if plan is not None else None, _stream(means2d))
+    if ctx.absgrad:
+        means2d.absgrad = v_means2d_abs
+    if _needs(ctx, _COMPOSITE_INPUTS)["backgrounds"]:
+        v_backgrounds = (v_render_colors * (1.0 - render_alphas).float()).sum(dim=(1, 2))
+    else:
+        v_backgrounds = None
+    return v_means2d, v_conics, v_colors, v_opacities, v_backgrounds

@@ -3,13 +3,13 @@
 // One rasterization() forward + backward of the common training case (unpacked batch, quats + scales or covars, shared SH
 // coefficients or [N,3] colours, RGB) is ~30 launches through nine operator entry points; driven from Python that is ~0.6 ms
 // of host work per step (argument marshalling of seven ctypes calls, two autograd nodes, ~20 tensor allocations) against
-// ~0.75 ms of GPU work -- and the multi-GPU modes, which add collectives, are host-bound.  The three functions here issue
-// the SAME launches through the SAME entry points from ONE descriptor the caller fills once (`gs_step`: host struct, device
-// pointers; every buffer caller-owned, sizes from the gs_*_bytes helpers): the host side of a step becomes three calls.
+// ~0.75 ms of GPU work -- and the multi-GPU modes, which add collectives, are host-bound.  The two functions here issue
+// the forward's launches through the SAME entry points from ONE descriptor the caller fills once (`gs_step`: host struct, device
+// pointers; every buffer caller-owned, sizes from the gs_*_bytes helpers): the host side of a forward becomes two calls.
 //   gs_step_fwd_begin   projection into splat rows (+ SH colours) -> splitters -> count + depth keys -> depth pre-sort
 //                       [the caller waits for block_sums (pinned), adds them up = n_isects, allocates the phase-2 buffers]
 //   gs_step_fwd_finish  emit -> pair sort -> offsets -> compositing forward (+ zero-fill side job)
-//   gs_step_bwd         compositing backward -> projection (+ SH) backward
+// The backward is the operator path's (gs_rasterize_bwd, then gs_projection_rows_bwd / _dyn_bwd).
 // Nothing is computed here that the operator entry points do not compute: results are identical by construction
 // (tests/test_gpu_step.py compares them bit for bit).  The operators stay the drop-in boundary (reference csrc/ext.cpp);
 // this is the executor around them, the counterpart of the Python orchestration in gsplat/rendering.py:28-582.
@@ -37,10 +37,8 @@ extern "C" uint32_t gs_step_layout(uint64_t *out, uint32_t n) {
                           offsetof(gs_step, sh_mask_logits), offsetof(gs_step, rows_ready), offsetof(gs_step, backgrounds),
                           offsetof(gs_step, radii), offsetof(gs_step, sort_temp_bytes), offsetof(gs_step, block_sums),
                           offsetof(gs_step, n_isects), offsetof(gs_step, n_kept_host), offsetof(gs_step, work_bytes), offsetof(gs_step, plan), offsetof(gs_step, scratch),
-                          offsetof(gs_step, zero_fill_bytes), offsetof(gs_step, v_render_colors), offsetof(gs_step, vrc_pixel_stride),
-                          offsetof(gs_step, grad_rows), offsetof(gs_step, v_sh_rest), offsetof(gs_step, absgrad),
-                          offsetof(gs_step, finish_phase), offsetof(gs_step, dyn_motion), offsetof(gs_step, dyn_timestamp),
-                          offsetof(gs_step, dyn_quant_lo), offsetof(gs_step, v_dyn_motion)};
+                          offsetof(gs_step, zero_fill_bytes), offsetof(gs_step, finish_phase), offsetof(gs_step, dyn_motion),
+                          offsetof(gs_step, dyn_timestamp), offsetof(gs_step, dyn_quant_lo), offsetof(gs_step, dyn_trbf_alive)};
     const uint32_t m = (uint32_t)(sizeof(v) / sizeof(v[0]));
     for (uint32_t i = 0; out != nullptr && i < n && i < m; ++i) out[i] = v[i];
     return m;
@@ -126,32 +124,5 @@ extern "C" int32_t gs_step_fwd_finish(gs_step *s, gs_stream_t stream) {
                                  s->rows + GS_ROW_OPACITY, strides, s->backgrounds, nullptr, (uint32_t)s->width, (uint32_t)s->height, s->tile_size,
                                  s->tile_width, s->tile_height, s->offsets, s->flatten_ids, s->render_colors, s->render_alphas, s->last_ids,
                                  s->scratch ? &s->plan : nullptr, s->scratch, s->zero_fill, (size_t)s->zero_fill_bytes, stream));
-    return 0;
-}
-
-extern "C" int32_t gs_step_bwd(gs_step *s, gs_stream_t stream) {
-    GS_CHECK_ARG(s != nullptr, "null descriptor");
-    GS_CHECK_ARG(s->grad_rows && s->v_render_colors, "the gradient rows and the image gradient are required");
-    const uint32_t n_elems = s->C * s->N;
-    const uint32_t strides[4] = {GS_ROW_FLOATS, GS_ROW_FLOATS, GS_ROW_FLOATS, GS_ROW_FLOATS};
-    GS_STEP_TRY(gs_rasterize_bwd(s->C, n_elems, (uint32_t)s->n_isects, 3, s->rows + GS_ROW_MEAN2D, s->rows + GS_ROW_CONIC, s->rows + GS_ROW_COLOR,
-                                 s->rows + GS_ROW_OPACITY, strides, s->backgrounds, nullptr, (uint32_t)s->width, (uint32_t)s->height, s->tile_size,
-                                 s->tile_width, s->tile_height, s->offsets, s->flatten_ids, s->render_colors, s->render_alphas, s->last_ids,
-                                 s->v_render_colors, s->v_render_alphas, s->vrc_pixel_stride, s->vrc_channel_stride,
-                                 s->absgrad ? s->grad_rows : nullptr, s->grad_rows, nullptr, nullptr, nullptr, 1, nullptr,
-                                 s->scratch ? &s->plan : nullptr, s->scratch, stream));
-    if (!s->skip_projection_bwd && s->dyn_motion != nullptr)
-        GS_STEP_TRY(gs_projection_rows_dyn_bwd(s->C, s->N, s->means, s->quats, s->scales, s->dyn_motion, s->dyn_omega, s->dyn_trbf_center,
-                                               s->dyn_trbf_scale, s->dyn_timestamp, s->dyn_raw_params, s->dyn_quant_mask, s->dyn_quant_lo,
-                                               s->dyn_quant_hi, s->dyn_quant_range, s->dyn_quant_step_norm, s->viewmats, s->Ks, s->width, s->height,
-                                               s->eps2d, s->camera_model, s->radii, s->rows, s->grad_rows, s->v_depths, s->opacities, s->antialiased,
-                                               s->v_means, s->v_quats, s->v_scales, s->v_dyn_motion, s->v_dyn_omega, s->v_dyn_trbf_center,
-                                               s->v_dyn_trbf_scale, s->v_opacities, s->v_colors, s->outputs_prefilled, stream));
-    else if (!s->skip_projection_bwd)
-        GS_STEP_TRY(gs_projection_rows_bwd(s->C, s->N, s->means, s->covars, s->quats, s->scales, s->viewmats, s->Ks, s->width, s->height, s->eps2d,
-                                           s->camera_model, s->radii, s->rows, s->grad_rows, s->v_depths, s->opacities, s->antialiased, s->v_means,
-                                           s->v_covars, s->v_quats, s->v_scales, nullptr, s->v_opacities, s->v_colors, nullptr, s->sh_coeffs,
-                                           s->sh_rest, s->sh_K, s->sh_degree, s->v_sh, s->v_sh_rest, s->sh_mask_logits, s->sh_mask_temperature,
-                                           s->sh_mask_binary, s->v_sh_mask_logits, s->outputs_prefilled, stream));
     return 0;
 }

@@ -35,11 +35,11 @@ extern "C" {
 
 /* Bumped whenever an exported signature or the meaning of an argument changes (1: round 1; 2: the round-2 additions to
  * gs_rasterize_fwd, gs_isect_count_keys, gs_sort_pairs_u64_i32_drop, gs_projection_bwd; 3: round 3 -- the splat-row layout,
- * gs_raster_plan, gs_kmeans_decode's bounds; 4: round 4 -- the shN mask entry points, gs_isect_count_keys' bucket_splitters, the bucketed pre-sort; 5: round 6 -- gs_projection_rows_dyn_*, the dyn_* fields of gs_step, gs_accumulate_*, gs_quantize_round_multi_*, the scratch behind gs_presort_split's table).  A binding must refuse a library whose gs_version() differs from the
+ * gs_raster_plan, gs_kmeans_decode's bounds; 4: round 4 -- the shN mask entry points, gs_isect_count_keys' bucket_splitters, the bucketed pre-sort; 5: round 6 -- gs_projection_rows_dyn_*, the dyn_* fields of gs_step, gs_accumulate_*, gs_quantize_round_multi_*, the scratch behind gs_presort_split's table; 6: the step driver's backward entry point and the backward fields of gs_step removed).  A binding must refuse a library whose gs_version() differs from the
  * GS_ABI_VERSION of the header it was generated from, and SHOULD also compare gs_header_hash() (the first 8 bytes of the
  * SHA-256 of the header file the library was compiled against, big-endian) with the hash of its own copy: ctypes / cgo call
  * through shifted argument lists silently otherwise. */
-#define GS_ABI_VERSION 5
+#define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
 #define GS_CAMERA_PINHOLE 0
@@ -1047,10 +1047,10 @@ int32_t gs_dp_reduce_rows(uint64_t n_recv, uint32_t width, uint32_t world, const
                           int32_t *inv, float *acc, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
- * Native step driver (round 4): the launches of one rasterization() forward + backward of the common training case --
+ * Native step driver (round 4): the launches of one rasterization() forward of the common training case --
  * unpacked batch, quats + scales or covars, shared SH coefficients (contiguous or split) or [N,3] colours, three render
- * channels, fixed camera poses -- issued from ONE descriptor in three calls instead of nine operator calls from the host
- * language.  Every launch goes through the operator entry points above: identical results; the operators stay the drop-in
+ * channels, fixed camera poses -- issued from ONE descriptor in two calls instead of seven operator calls from the host
+ * language (the backward goes through gs_rasterize_bwd and gs_projection_rows_bwd / _dyn_bwd directly).  Every launch goes through the operator entry points above: identical results; the operators stay the drop-in
  * boundary, this is the executor around them (the counterpart of gsplat/rendering.py:28-582's orchestration).
  *   gs_step_fwd_begin   gs_projection_rows_fwd (gs_projection_rows_dyn_fwd with dyn_motion) -> [gs_presort_split] -> gs_isect_count_keys -> gs_presort_buckets |
  *                       gs_sort_pairs_u64_i32_drop [-> gs_cumsum_i32 when group_prefix is given]
@@ -1058,7 +1058,6 @@ int32_t gs_dp_reduce_rows(uint64_t n_recv, uint32_t width, uint32_t world, const
  *    n_kept_host to the sums of its even / odd entries, sizes the phase-2 buffers with gs_isect_finish_work_bytes /
  *    gs_rasterize_plan and allocates them)
  *   gs_step_fwd_finish  gs_isect_finish_presorted -> gs_rasterize_fwd (zero-filling zero_fill as its side job)
- *   gs_step_bwd         gs_rasterize_bwd (packed gradient rows) -> gs_projection_rows_bwd
  * With rows_ready the first call starts at gs_isect_count_keys (binning + compositing of rows some other producer wrote).
  * All pointers are device pointers except block_sums (pinned host).  Buffers: radii i32 [C,N], depths [C,N], rows [C,N,16]
  * (64-byte aligned), tiles_per_gauss i32 [C,N], depth_keys i64 [C N], depth_vals i32 [C N] (radix pre-sort only), sort_temp
@@ -1067,8 +1066,7 @@ int32_t gs_dp_reduce_rows(uint64_t n_recv, uint32_t width, uint32_t world, const
  * + cumsum_scratch (both or neither), block_sums i32 [C * gs_projection_rows_blocks(N)][2] ([gs_isect_count_blocks(C N)][2] with rows_ready); isect_ids i64 / flatten_ids i32
  * [n_isects], offsets i32 [C, tile_height, tile_width], work (gs_isect_finish_work_bytes), render_colors [C,H,W,3],
  * render_alphas [C,H,W,1], last_ids i32 [C,H,W], scratch (plan.scratch_bytes; NULL: no checkpoints), zero_fill: the gradient rows
- * [C N,16] (+ whatever else the caller wants zeroed behind them); backward: grad_rows = that zero-filled buffer, v_* outputs as
- * in gs_projection_rows_bwd (NULL: not wanted). */
+ * [C N,16] (+ whatever else the caller wants zeroed behind them). */
 typedef struct gs_step {
     uint32_t C, N;
     const float *means, *covars, *quats, *scales, *viewmats, *Ks, *opacities, *colors, *sh_coeffs, *sh_rest;
@@ -1081,7 +1079,6 @@ typedef struct gs_step {
     uint32_t lds_capacity;
     int32_t sh_mask_binary;
     const float *sh_mask_logits; /* the shN mask fused into the SH evaluation (split rows), or NULL */
-    float *v_sh_mask_logits;     /* backward: [N] or NULL */
     float sh_mask_temperature;
     uint32_t rows_ready; /* != 0: rows / radii / depths are inputs (e.g. received through the gaussian-sharded exchange): no projection,
                           * gs_isect_count_keys counts the tiles; block_sums then has gs_isect_count_blocks(C N) entries */
@@ -1114,13 +1111,6 @@ typedef struct gs_step {
     gs_raster_plan plan;
     void *scratch, *zero_fill;
     uint64_t zero_fill_bytes;
-    /* backward */
-    const float *v_render_colors, *v_render_alphas;
-    int64_t vrc_pixel_stride, vrc_channel_stride;
-    float *grad_rows;
-    const float *v_depths;
-    float *v_means, *v_covars, *v_quats, *v_scales, *v_opacities, *v_colors, *v_sh, *v_sh_rest;
-    int32_t absgrad, outputs_prefilled, skip_projection_bwd;
     int32_t finish_phase; /* gs_step_fwd_finish: 0 = binning + compositing, 1 = binning only, 2 = compositing only */
     /* dynamic splats (round 6): dyn_motion != NULL routes the projection through gs_projection_rows_dyn_fwd / _bwd (no SH, no covars;
      * quats / scales / opacities / colors are then written when dyn_quant_mask clamps a parameter) */
@@ -1129,20 +1119,18 @@ typedef struct gs_step {
     uint32_t dyn_raw_params, dyn_quant_mask;
     float dyn_min_trbf; /* < 0: no temporal culling */
     float dyn_quant_lo[4], dyn_quant_hi[4], dyn_quant_range[4], dyn_quant_step_norm[4];
-    float *v_dyn_motion, *v_dyn_omega, *v_dyn_trbf_center, *v_dyn_trbf_scale;
     uint8_t *dyn_trbf_alive; /* [N] or NULL */
 } gs_step;
 /* Layout guard for bindings that mirror the host structs by hand (ctypes, cgo, JNA ...): writes up to n entries --
  * sizeof(struct), then offsetof of the listed fields in this order -- and returns how many the list has.
  *   gs_step:       C, sh_K, eps2d, tile_size, sh_mask_logits, rows_ready, backgrounds, radii, sort_temp_bytes, block_sums, n_isects,
- *                  n_kept_host, work_bytes, plan, scratch, zero_fill_bytes, v_render_colors, vrc_pixel_stride, grad_rows, v_sh_rest, absgrad,
- *                  finish_phase, dyn_motion, dyn_timestamp, dyn_quant_lo, v_dyn_motion
+ *                  n_kept_host, work_bytes, plan, scratch, zero_fill_bytes, finish_phase, dyn_motion, dyn_timestamp, dyn_quant_lo,
+ *                  dyn_trbf_alive
  *   gs_quant_desc: n, x, out, v_out, v_x, lo, q_step, activation, philox_offset */
 uint32_t gs_step_layout(uint64_t *out, uint32_t n);
 uint32_t gs_quant_desc_layout(uint64_t *out, uint32_t n);
 int32_t gs_step_fwd_begin(gs_step *step, gs_stream_t stream);
 int32_t gs_step_fwd_finish(gs_step *step, gs_stream_t stream);
-int32_t gs_step_bwd(gs_step *step, gs_stream_t stream);
 
 #ifdef __cplusplus
 }

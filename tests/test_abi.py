@@ -27,11 +27,12 @@ def test_library_exports_every_declared_symbol():
     assert exported == set(protos), exported ^ set(protos)
 
 
-def test_version_and_error_string():
+def test_abi_v6_version_and_error_string():
+    """ABI 6: gs_step without the backward half (gs_step_bwd and the fields only it read are gone)."""
     from gscodec_studio_amd import _backend as B
 
     L = B.lib()
-    assert L.gs_version() == B.header_abi_version() == 5
+    assert L.gs_version() == B.header_abi_version() == 6
     assert L.gs_header_hash() == B.header_hash()  # the library was compiled against THIS header
     assert isinstance(L.gs_last_error(), bytes)
     assert B.query("gs_sort_temp_bytes", 1000) >= 1000 * 12
