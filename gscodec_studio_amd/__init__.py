@@ -2,7 +2,8 @@
 
 Public surface (mirrors the reference's ``gsplat`` package for this path only):
   rendering.rasterization, the operator functions of ``_wrapper`` and
-  ``compression_simulation.{CompressionSimulation, STGCompressionSimulation, fake_quantize_ste, STE}``.
+  ``compression_simulation.{CompressionSimulation, STGCompressionSimulation, fake_quantize_ste, STE}`` and
+  ``optimizers.{Adam, SelectiveAdam, step_all, visibility_mask}``.
 """
 from ._wrapper import (
     accumulate,
@@ -14,6 +15,7 @@ from ._wrapper import (
     quat_scale_to_covar_preci,
     rasterize_to_indices_in_range,
     rasterize_to_pixels,
+    selective_adam_update,
     spherical_harmonics,
     spherical_harmonics_shared,
     world_to_cam,
@@ -33,5 +35,5 @@ def __getattr__(name):  # (lazy: the codec module is not on the training path)
 __all__ = [
     "rasterization", "fully_fused_projection", "spherical_harmonics", "spherical_harmonics_shared",
     "isect_tiles", "isect_offset_encode", "rasterize_to_pixels", "quat_scale_to_covar_preci", "proj", "persp_proj",
-    "world_to_cam", "rasterize_to_indices_in_range", "accumulate", "PngCompression", "__version__",
+    "world_to_cam", "rasterize_to_indices_in_range", "accumulate", "selective_adam_update", "PngCompression", "__version__",
 ]

@@ -5,9 +5,10 @@ native surface is "an object with these attributes" (``gsplat/cuda/csrc/ext.cpp:
 subset -- every name the hot path and the reference's ``tests/test_basic.py`` use -- with the reference's POSITIONAL
 torch-tensor signatures and return tuples (``gsplat/cuda/include/bindings.h:34-330``): assigning it in the reference's
 ``_backend.py`` (``_C = gscodec_studio_amd._c_adapter._C``) lets the reference's own ``_wrapper.py`` -- its autograd
-Functions, asserts and ``.contiguous()`` calls -- run unmodified on MI355X.  Out of scope, like everything 2DGS / MCMC /
-optimizer in SURVEY section 2: ``*_2dgs``, ``compute_relocation``, ``selective_adam_update`` (AttributeError, as for any
-name the module does not have).
+Functions, asserts and ``.contiguous()`` calls -- run unmodified on MI355X.  ``selective_adam_update`` is there too (the
+``gs_adam_multi`` kernel in selective mode), so the reference's ``gsplat/optimizers/selective_adam.py`` runs unmodified through
+``_C`` as well.  Out of scope, like everything 2DGS / MCMC in SURVEY section 2: ``*_2dgs``, ``compute_relocation``
+(AttributeError, as for any name the module does not have).
 
 What the adapter cannot do better than the signatures allow:
 * ``rasterize_to_pixels_bwd`` has no place for the forward's checkpoints, so it runs the plain (unsegmented) backward; the
@@ -342,6 +343,12 @@ class HipBackend:
                                                    image_height, tile_size, tile_offsets, flatten_ids)
         # the native function returns the pixel id INCLUDING the camera (the reference's Python splits it, _wrapper.py:636-643)
         return gaussian_ids, camera_ids * (image_width * image_height) + pixel_ids
+
+    @staticmethod
+    def selective_adam_update(param, param_grad, exp_avg, exp_avg_sq, tiles_touched, lr, b1, b2, eps, N, M):
+        from ._wrapper import selective_adam_update as _sau
+
+        _sau(param, param_grad, exp_avg, exp_avg_sq, tiles_touched, lr, b1, b2, eps, N, M)
 
 
 _C = HipBackend()

@@ -1998,3 +1998,90 @@ def _rasterize_bwd(ctx, v_render_colors: Optional[Tensor], v_render_alphas: Opti
     else:
         v_backgrounds = None
     return v_means2d, v_conics, v_colors, v_opacities, v_backgrounds
+
+
+# ---------------------------------------------------------------------------
+# Adam / SelectiveAdam step  (reference _wrapper.py:19-34, csrc/adam.cu; torch.optim.adam._single_tensor_adam)
+# ---------------------------------------------------------------------------
+ADAM_DENSE, ADAM_SELECTIVE = 0, 1
+
+
+class _AdamDesc(ctypes.Structure):  # gs_adam_desc of include/gsplat_hip.h
+    _fields_ = [("n", ctypes.c_uint64), ("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
+                ("exp_avg_sq", ctypes.c_void_p), ("visibility", ctypes.c_void_p), ("rows", ctypes.c_uint32),
+                ("row_width", ctypes.c_uint32), ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
+                ("eps", ctypes.c_float), ("one_minus_beta1", ctypes.c_float), ("one_minus_beta2", ctypes.c_float),
+                ("step_size", ctypes.c_float), ("bias_correction2_sqrt", ctypes.c_float), ("mode", ctypes.c_int32)]
+
+
+_ADAM_DESC_CHECKED = [False]
+
+
+def check_adam_desc_layout() -> None:
+    """``_AdamDesc`` against the library's ``sizeof`` / ``offsetof`` of ``gs_adam_desc``."""
+    want = (ctypes.c_uint64 * 16)()
+    m = int(B.query("gs_adam_desc_layout", want, 16))
+    mine = [ctypes.sizeof(_AdamDesc)] + [getattr(_AdamDesc, f).offset for f in ("n", "param", "grad", "exp_avg", "exp_avg_sq", "visibility",
+                                                                                 "rows", "row_width", "lr", "step_size", "mode")]
+    if m != len(mine) or list(want[:m]) != mine:
+        raise ImportError(f"gs_adam_desc: the ctypes mirror in _wrapper.py does not match the library's struct layout ({list(want[:m])} vs {mine})")
+    _ADAM_DESC_CHECKED[0] = True
+
+
+def adam_dense_scalars(lr: float, beta1: float, beta2: float, step: float) -> Tuple[float, float, float, float]:
+    """(1 - beta1, 1 - beta2, step_size, bias_correction2_sqrt) of torch's non-capturable Adam at ``step`` (already advanced), in
+    double as torch computes them (``_single_tensor_adam``); the descriptor rounds them to float as torch's kernels do."""
+    bias_correction1 = 1 - beta1 ** step
+    bias_correction2 = 1 - beta2 ** step
+    return 1 - beta1, 1 - beta2, lr / bias_correction1, bias_correction2 ** 0.5
+
+
+def adam_desc(mode: int, param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, lr: float, beta1: float, beta2: float,
+              eps: float, step: float = 0.0, visibility: Optional[Tensor] = None, rows: int = 0, row_width: int = 0,
+              n: Optional[int] = None) -> _AdamDesc:
+    """One ``gs_adam_desc``: dense (``step`` = the advanced step counter) or selective (``visibility`` [rows], n = rows * row_width)."""
+    d = _AdamDesc()
+    d.n = param.numel() if n is None else n
+    d.param, d.grad, d.exp_avg, d.exp_avg_sq = param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr()
+    d.lr, d.beta1, d.beta2, d.eps = lr, beta1, beta2, eps
+    d.mode = mode
+    if mode == ADAM_SELECTIVE:
+        d.visibility, d.rows, d.row_width = visibility.data_ptr(), rows, row_width
+    else:
+        d.one_minus_beta1, d.one_minus_beta2, d.step_size, d.bias_correction2_sqrt = adam_dense_scalars(lr, beta1, beta2, step)
+    return d
+
+
+def adam_multi(descs, like: Tensor) -> None:
+    """Launch ``gs_adam_multi`` over ``descs`` (a list of ``_AdamDesc``, tensors on ``like``'s device) on the current stream."""
+    if not descs:
+        return
+    if not _ADAM_DESC_CHECKED[0]:
+        check_adam_desc_layout()
+    table = (_AdamDesc * len(descs))(*descs)
+    with _device_of(like):
+        B.call("gs_adam_multi", len(descs), ctypes.addressof(table), _stream(like))
+
+
+def _adam_operand(t: Tensor, what: str, n: int) -> None:
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= n):
+        raise RuntimeError(f"selective_adam_update: {what} must be a contiguous float32 GPU tensor of at least {n} elements "
+                           f"(got {t.dtype}, {tuple(t.shape)} on {t.device}, contiguous={t.is_contiguous()})")
+
+
+def selective_adam_update(param: Tensor, param_grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, tiles_touched: Tensor, lr: float,
+                          b1: float, b2: float, eps: float, N: int, M: int) -> None:
+    """Reference ``selective_adam_update`` (``gsplat/cuda/_wrapper.py:19-34``, kernel ``csrc/adam.cu:14-42``): in place, for the
+    first N * M elements, only the rows n < N with ``tiles_touched[n]`` set (bool / uint8 [N]); the other rows are neither read
+    nor written.  One ``gs_adam_multi`` descriptor in selective mode."""
+    N, M = int(N), int(M)
+    if N <= 0 or M <= 0:
+        return
+    for t, what in ((param, "param"), (param_grad, "param_grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _adam_operand(t, what, N * M)
+    if not (tiles_touched.device == param.device and tiles_touched.dtype in (torch.bool, torch.uint8) and tiles_touched.is_contiguous()
+            and tiles_touched.numel() == N):
+        raise RuntimeError(f"selective_adam_update: tiles_touched must be a contiguous bool / uint8 tensor of N = {N} elements on "
+                           f"{param.device} (got {tiles_touched.dtype}, {tuple(tiles_touched.shape)} on {tiles_touched.device})")
+    adam_multi([adam_desc(ADAM_SELECTIVE, param, param_grad, exp_avg, exp_avg_sq, float(lr), float(b1), float(b2), float(eps),
+                          visibility=tiles_touched, rows=N, row_width=M, n=N * M)], param)

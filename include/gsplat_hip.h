@@ -38,7 +38,9 @@ extern "C" {
  * gs_raster_plan, gs_kmeans_decode's bounds; 4: round 4 -- the shN mask entry points, gs_isect_count_keys' bucket_splitters, the bucketed pre-sort; 5: round 6 -- gs_projection_rows_dyn_*, the dyn_* fields of gs_step, gs_accumulate_*, gs_quantize_round_multi_*, the scratch behind gs_presort_split's table; 6: the step driver's backward entry point and the backward fields of gs_step removed).  A binding must refuse a library whose gs_version() differs from the
  * GS_ABI_VERSION of the header it was generated from, and SHOULD also compare gs_header_hash() (the first 8 bytes of the
  * SHA-256 of the header file the library was compiled against, big-endian) with the hash of its own copy: ctypes / cgo call
- * through shifted argument lists silently otherwise. */
+ * through shifted argument lists silently otherwise.
+ * ABI 6 later gained the optimizer entries (gs_adam_desc, gs_adam_multi, gs_adam_multi_max, gs_adam_desc_layout): additive, no
+ * existing signature changed. */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -1045,6 +1047,43 @@ int32_t gs_dp_plan(uint32_t world, uint32_t rank, uint32_t n_pad, uint32_t block
 int32_t gs_dp_reduce_rows(uint64_t n_recv, uint32_t width, uint32_t world, const float *wire, const int64_t *chunk_starts,
                           const int32_t *map, int32_t map_offset, uint64_t umax, uint32_t n_valid, const int32_t *uidx, float scale,
                           int32_t *inv, float *acc, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * O1  Adam / SelectiveAdam over several tensors in ONE launch (the optimizer step after the render backward: one
+ * torch.optim.Adam per splat attribute in the trainers, gsplat/optimizers/selective_adam.py with --visible_adam).  descs: HOST
+ * array; more than GS_ADAM_MULTI_MAX descriptors are split over several launches on the same stream.  Every float array is
+ * fp32, contiguous, 4-byte aligned, n floats; param, exp_avg and exp_avg_sq are updated in place.  Descriptors with n == 0 are
+ * skipped.  No atomics: the results are bit-identical from run to run and do not depend on the grid.
+ *   GS_ADAM_DENSE:     torch.optim.adam._single_tensor_adam (non-capturable, no weight decay / amsgrad / maximize), in its order
+ *                      of operations: m = lerp(m, g, one_minus_beta1) (ATen's two-branch lerp); v = v * beta2;
+ *                      v = v + (one_minus_beta2 * g) * g; p = p + (-step_size) * (m / (sqrt(v) / bias_correction2_sqrt + eps)).
+ *                      The caller computes one_minus_beta1 = 1 - beta1, one_minus_beta2 = 1 - beta2, step_size = lr / (1 - beta1^step)
+ *                      and bias_correction2_sqrt = (1 - beta2^step)^0.5 in double and rounds them to float, as torch does; it
+ *                      also advances its step counter.  lr, rows, row_width and visibility are not read.
+ *   GS_ADAM_SELECTIVE: gsplat/cuda/csrc/adam.cu:31-40 as written (no bias correction): m = beta1 * m + (1 - beta1) * g;
+ *                      v = beta2 * v + ((1 - beta2) * g) * g; p += (-lr * m) / (sqrt(v) + eps), only for the elements e with
+ *                      visibility[e / row_width] != 0 (uint8 / bool [rows]); the elements of the other rows are neither read nor
+ *                      written.  n == rows * row_width < 2^32, row_width < 2^31.  one_minus_*, step_size and
+ *                      bias_correction2_sqrt are not read. */
+#define GS_ADAM_DENSE 0
+#define GS_ADAM_SELECTIVE 1
+#define GS_ADAM_MULTI_MAX 16
+typedef struct gs_adam_desc {
+    uint64_t n;                  /* floats in each of the four arrays (0: skipped) */
+    float *param;                /* updated in place */
+    const float *grad;
+    float *exp_avg, *exp_avg_sq; /* updated in place */
+    const uint8_t *visibility;   /* selective: [rows]; dense: not read */
+    uint32_t rows, row_width;    /* selective: n = rows * row_width */
+    float lr, beta1, beta2, eps;
+    float one_minus_beta1, one_minus_beta2, step_size, bias_correction2_sqrt; /* dense */
+    int32_t mode;                /* GS_ADAM_DENSE / GS_ADAM_SELECTIVE */
+} gs_adam_desc;
+uint32_t gs_adam_multi_max(void);
+/* layout guard (see gs_step_layout): sizeof, then offsetof n, param, grad, exp_avg, exp_avg_sq, visibility, rows, row_width, lr,
+ * step_size, mode */
+uint32_t gs_adam_desc_layout(uint64_t *out, uint32_t n);
+int32_t gs_adam_multi(uint32_t n_tensors, const gs_adam_desc *descs, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Native step driver (round 4): the launches of one rasterization() forward of the common training case --
