@@ -3,7 +3,7 @@
 Public surface (mirrors the reference's ``gsplat`` package for this path only):
   rendering.rasterization, the operator functions of ``_wrapper`` and
   ``compression_simulation.{CompressionSimulation, STGCompressionSimulation, fake_quantize_ste, STE}`` and
-  ``optimizers.{Adam, SelectiveAdam, step_all, visibility_mask}``.
+  ``optimizers.{Adam, SelectiveAdam, step_all, visibility_mask}`` and ``losses.{fused_ssim, photometric_loss}``.
 """
 from ._wrapper import (
     accumulate,

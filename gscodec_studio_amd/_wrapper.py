@@ -2085,3 +2085,55 @@ def selective_adam_update(param: Tensor, param_grad: Tensor, exp_avg: Tensor, ex
                            f"{param.device} (got {tiles_touched.dtype}, {tuple(tiles_touched.shape)} on {tiles_touched.device})")
     adam_multi([adam_desc(ADAM_SELECTIVE, param, param_grad, exp_avg, exp_avg_sq, float(lr), float(b1), float(b2), float(eps),
                           visibility=tiles_touched, rows=N, row_width=M, n=N * M)], param)
+
+
+# ---------------------------------------------------------------------------
+# SSIM / L1 photometric loss  (the fused_ssim package's fused_ssim; csrc/loss.hip)
+# ---------------------------------------------------------------------------
+SSIM_PADDING = {"same": 0, "valid": 1}
+
+
+def _strides4(strides) -> ctypes.Array:
+    return (ctypes.c_int64 * 4)(*[int(s) for s in strides])
+
+
+def ssim_window() -> Tuple[float, ...]:
+    """The 11 weights of the SSIM window as the kernels use them (``gs_ssim_window``)."""
+    out = (ctypes.c_float * 11)()
+    n = int(B.query("gs_ssim_window", ctypes.addressof(out), 11))
+    return tuple(out[:n])
+
+
+def ssim_work_bytes(shape, train: bool) -> int:
+    b, c, h, w = (int(v) for v in shape)
+    return int(B.query("gs_ssim_work_bytes", b, c, h, w, int(bool(train))))
+
+
+def ssim_fwd(x: Tensor, x_strides, y: Tensor, y_strides, shape, padding: str, train: bool, ssim_lambda: float = 0.0,
+             want_l1: bool = False, want_loss: bool = False) -> Tuple[Tensor, Optional[Tensor], Optional[Tensor], Tensor]:
+    """``gs_ssim_fwd`` on the logical ``[B, C, H, W]`` ``shape`` of x / y read through the given element strides, on the current
+    stream.  Returns (mean SSIM, mean |x - y| or None, weighted loss or None, work area) as 0-d device tensors; the work area
+    holds the backward's coefficient maps when ``train``."""
+    b, c, h, w = (int(v) for v in shape)
+    work = torch.empty(ssim_work_bytes(shape, train), dtype=torch.uint8, device=x.device)
+    out_s = torch.empty((), dtype=torch.float32, device=x.device)
+    out_l = torch.empty((), dtype=torch.float32, device=x.device) if want_l1 else None
+    out_loss = torch.empty((), dtype=torch.float32, device=x.device) if want_loss else None
+    xs, ys = _strides4(x_strides), _strides4(y_strides)
+    with _device_of(x):
+        B.call("gs_ssim_fwd", x.data_ptr(), ctypes.addressof(xs), y.data_ptr(), ctypes.addressof(ys), b, c, h, w, SSIM_PADDING[padding],
+               int(bool(train)), float(ssim_lambda), work.data_ptr(), work.numel(), out_s.data_ptr(), B.ptr(out_l), B.ptr(out_loss),
+               _stream(x))
+    return out_s, out_l, out_loss, work
+
+
+def ssim_bwd(x: Tensor, x_strides, y: Tensor, y_strides, shape, padding: str, work: Tensor, grad_ssim: Optional[Tensor], w_ssim: float,
+             grad_l1: Optional[Tensor], w_l1: float, dx: Tensor, dx_strides) -> None:
+    """``gs_ssim_bwd``: writes dx (through ``dx_strides``) = w_ssim * grad_ssim * d(mean SSIM)/dx + w_l1 * grad_l1 * d(mean L1)/dx;
+    the upstream gradients are 0-d float32 device tensors (None with a zero weight)."""
+    b, c, h, w = (int(v) for v in shape)
+    xs, ys, ds = _strides4(x_strides), _strides4(y_strides), _strides4(dx_strides)
+    with _device_of(x):
+        B.call("gs_ssim_bwd", x.data_ptr(), ctypes.addressof(xs), y.data_ptr(), ctypes.addressof(ys), b, c, h, w, SSIM_PADDING[padding],
+               work.data_ptr(), work.numel(), B.ptr(grad_ssim), float(w_ssim), B.ptr(grad_l1), float(w_l1), dx.data_ptr(),
+               ctypes.addressof(ds), _stream(x))

@@ -39,8 +39,8 @@ extern "C" {
  * GS_ABI_VERSION of the header it was generated from, and SHOULD also compare gs_header_hash() (the first 8 bytes of the
  * SHA-256 of the header file the library was compiled against, big-endian) with the hash of its own copy: ctypes / cgo call
  * through shifted argument lists silently otherwise.
- * ABI 6 later gained the optimizer entries (gs_adam_desc, gs_adam_multi, gs_adam_multi_max, gs_adam_desc_layout): additive, no
- * existing signature changed. */
+ * ABI 6 later gained the optimizer entries (gs_adam_desc, gs_adam_multi, gs_adam_multi_max, gs_adam_desc_layout) and the loss
+ * entries (gs_ssim_fwd, gs_ssim_bwd, gs_ssim_work_bytes, gs_ssim_window): additive, no existing signature changed. */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -1084,6 +1084,32 @@ uint32_t gs_adam_multi_max(void);
  * step_size, mode */
 uint32_t gs_adam_desc_layout(uint64_t *out, uint32_t n);
 int32_t gs_adam_multi(uint32_t n_tensors, const gs_adam_desc *descs, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * L1  The trainers' photometric loss: the 3DGS SSIM of the fused_ssim package (11-tap separable Gaussian window, sigma 1.5,
+ * zero padding, C1 = 0.01^2, C2 = 0.03^2; sigma_x^2 = E[x^2] - mu_x^2 ...) and the L1 term, forward and backward.
+ * x, y: fp32 logical [B, C, H, W] with element strides {b, c, h, w} (HOST arrays of 4; any layout, NHWC views included),
+ * B * C * H * W < 2^31, B <= 65535.  padding: GS_SSIM_SAME averages the SSIM map over every position, GS_SSIM_VALID over
+ * [5, H-5) x [5, W-5) (H > 10 and W > 10).  The L1 term is always the mean of |x - y| over every element.
+ * work: caller-owned device memory, 16-byte aligned, of gs_ssim_work_bytes(B, C, H, W, train) bytes: the per-block partial
+ * sums and, with train, the three coefficient maps the backward reads (3 * B * C * H * W floats).
+ * gs_ssim_fwd: one pass over x and y, then a one-block reduction in a fixed order (no atomics: bit-identical from run to run,
+ * and between layouts of the same values).  Writes, to the non-null DEVICE pointers among them, out_ssim = mean SSIM,
+ * out_l1 = mean |x - y| and out_loss = out_l1 * (1 - ssim_lambda) + (1 - out_ssim) * ssim_lambda.
+ * gs_ssim_bwd: dx (its own strides) = w_ssim * grad_ssim[0] * d(mean SSIM)/dx + w_l1 * grad_l1[0] * sign(x - y) / (B C H W),
+ * grad_ssim / grad_l1 DEVICE scalars (null allowed where the weight is 0); work is that of a train forward of the same x, y.
+ * Neither function synchronises with the host.  gs_ssim_window writes the 11 window weights (float32 roundings of
+ * exp(-(i-5)^2 / 4.5) / sum) to a HOST array of n and returns 11. */
+#define GS_SSIM_SAME 0
+#define GS_SSIM_VALID 1
+uint32_t gs_ssim_window(float *out, uint32_t n);
+uint64_t gs_ssim_work_bytes(uint32_t B, uint32_t C, uint32_t H, uint32_t W, int32_t train);
+int32_t gs_ssim_fwd(const float *x, const int64_t *x_strides, const float *y, const int64_t *y_strides, uint32_t B, uint32_t C,
+                    uint32_t H, uint32_t W, int32_t padding, int32_t train, float ssim_lambda, void *work, uint64_t work_bytes,
+                    float *out_ssim, float *out_l1, float *out_loss, gs_stream_t stream);
+int32_t gs_ssim_bwd(const float *x, const int64_t *x_strides, const float *y, const int64_t *y_strides, uint32_t B, uint32_t C,
+                    uint32_t H, uint32_t W, int32_t padding, const void *work, uint64_t work_bytes, const float *grad_ssim,
+                    float w_ssim, const float *grad_l1, float w_l1, float *dx, const int64_t *dx_strides, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Native step driver (round 4): the launches of one rasterization() forward of the common training case --
