@@ -7,8 +7,8 @@ torch-tensor signatures and return tuples (``gsplat/cuda/include/bindings.h:34-3
 ``_backend.py`` (``_C = gscodec_studio_amd._c_adapter._C``) lets the reference's own ``_wrapper.py`` -- its autograd
 Functions, asserts and ``.contiguous()`` calls -- run unmodified on MI355X.  ``selective_adam_update`` is there too (the
 ``gs_adam_multi`` kernel in selective mode), so the reference's ``gsplat/optimizers/selective_adam.py`` runs unmodified through
-``_C`` as well.  Out of scope, like everything 2DGS / MCMC in SURVEY section 2: ``*_2dgs``, ``compute_relocation``
-(AttributeError, as for any name the module does not have).
+``_C`` as well, and ``compute_relocation`` (the ``gs_relocation`` kernel) serves ``gsplat/relocation.py``.  Not provided, like
+everything 2DGS in SURVEY section 2: ``*_2dgs`` (AttributeError, as for any name the module does not have).
 
 What the adapter cannot do better than the signatures allow:
 * ``rasterize_to_pixels_bwd`` has no place for the forward's checkpoints, so it runs the plain (unsegmented) backward; the
@@ -349,6 +349,13 @@ class HipBackend:
         from ._wrapper import selective_adam_update as _sau
 
         _sau(param, param_grad, exp_avg, exp_avg_sq, tiles_touched, lr, b1, b2, eps, N, M)
+
+    # ---- MCMC relocation (bindings.h; compute_relocation.cu:40-74)
+    @staticmethod
+    def compute_relocation(opacities: Tensor, scales: Tensor, ratios: Tensor, binoms: Tensor, n_max: int):
+        from .relocation import relocation_native
+
+        return relocation_native(opacities, scales, ratios, binoms, int(n_max))
 
 
 _C = HipBackend()

@@ -40,7 +40,8 @@ extern "C" {
  * SHA-256 of the header file the library was compiled against, big-endian) with the hash of its own copy: ctypes / cgo call
  * through shifted argument lists silently otherwise.
  * ABI 6 later gained the optimizer entries (gs_adam_desc, gs_adam_multi, gs_adam_multi_max, gs_adam_desc_layout) and the loss
- * entries (gs_ssim_fwd, gs_ssim_bwd, gs_ssim_work_bytes, gs_ssim_window): additive, no existing signature changed. */
+ * entries (gs_ssim_fwd, gs_ssim_bwd, gs_ssim_work_bytes, gs_ssim_window): additive, no existing signature changed.  The
+ * densification-strategy entries (gs_relocation, gs_inject_noise, gs_densify_stats) are additive in the same way. */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -1110,6 +1111,36 @@ int32_t gs_ssim_fwd(const float *x, const int64_t *x_strides, const float *y, co
 int32_t gs_ssim_bwd(const float *x, const int64_t *x_strides, const float *y, const int64_t *y_strides, uint32_t B, uint32_t C,
                     uint32_t H, uint32_t W, int32_t padding, const void *work, uint64_t work_bytes, const float *grad_ssim,
                     float w_ssim, const float *grad_l1, float w_l1, float *dx, const int64_t *dx_strides, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * D1  The densification strategies (gsplat/strategy/default.py, mcmc.py, ops.py; gsplat/relocation.py).  One thread per
+ * gaussian (or per packed row), fp32 arrays, contiguous unless a stride is given, no host synchronisation; N == 0 (and, for the
+ * packed statistics, nnz == 0) is a no-op that returns success.
+ * gs_relocation: equation 9 of "3D Gaussian Splatting as Markov Chain Monte Carlo" (csrc/compute_relocation.cu:6-38).
+ *   opacities [N], scales [N,3], ratios int32 [N] with values in [1, n_max] (values outside are clamped by the kernel),
+ *   binoms [n_max, n_max] (binoms[n, k] = C(n, k)), n_max >= 1 -> new_opacities [N], new_scales [N,3]:
+ *   x = 1 - (1 - o)^(1/n); new_scale = scale * o / sum_{i=1..n} sum_{k<i} binoms[i-1, k] (-1)^k / sqrt(k+1) * x^(k+1).
+ *   Evaluated in double (x through expm1 / log1p, running powers, the sum by columns of binoms) and rounded once to float.
+ * gs_inject_noise: the per-step perturbation of the MCMC strategy (ops.py:360-385) from the RAW parameters, in place:
+ *   means[n] += Sigma_n * (noise[n] * g(1 - sigmoid(opacities[n])) * scaler), g(x) = 1 / (1 + exp(-100 (x - 0.995))),
+ *   Sigma = R diag(exp(scales))^2 R^T, R the rotation of quats[n] (wxyz, normalised as gs_quat_scale_to_covar_preci_fwd does).
+ *   means, scales (logs), noise [N,3]; quats [N,4]; opacities (logits) [N].  No [N,3,3] temporary.
+ * gs_densify_stats: the running statistics of DefaultStrategy (default.py:203-261).  grad: rows of 2 floats, grad_row_stride
+ *   floats apart (2: contiguous; 16: the means2d columns of the compositing backward's gradient rows), scaled by sx, sy.
+ *   gaussian_ids == NULL (unpacked): grad [C,N] rows, radii int32 [C,N]; for every camera c with radii[c,n] > 0, in ascending c:
+ *     grad2d[n] += hypot(gx * sx, gy * sy); count[n] += 1; radii_state[n] = max(radii_state[n], radii[c,n] / extent).
+ *     One thread per gaussian, no atomics: bit-identical from run to run.  nnz is not read.
+ *   gaussian_ids int64 [nnz] (packed): grad [nnz] rows, radii int32 [nnz]; the same per row with radii > 0 and an id < N, through
+ *     float atomic adds and an integer atomic max on the bit pattern of the non-negative radii_state.  C >= 1 is still required.
+ *   radii_state may be NULL.  With several cameras radii_state is the TRUE maximum (the reference's indexed assignment keeps
+ *   whichever duplicate index the scatter writes last; for C == 1 the two agree). */
+int32_t gs_relocation(uint32_t N, const float *opacities, const float *scales, const int32_t *ratios, const float *binoms,
+                      uint32_t n_max, float *new_opacities, float *new_scales, gs_stream_t stream);
+int32_t gs_inject_noise(uint32_t N, float *means, const float *quats, const float *scales, const float *opacities,
+                        const float *noise, float scaler, gs_stream_t stream);
+int32_t gs_densify_stats(uint32_t C, uint32_t N, uint64_t nnz, const float *grad, uint64_t grad_row_stride, const int32_t *radii,
+                         const int64_t *gaussian_ids, float sx, float sy, float extent, float *grad2d, float *count,
+                         float *radii_state, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Native step driver (round 4): the launches of one rasterization() forward of the common training case --
