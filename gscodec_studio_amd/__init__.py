@@ -4,7 +4,7 @@ Public surface (mirrors the reference's ``gsplat`` package for this path only):
   rendering.rasterization, the operator functions of ``_wrapper`` and
   ``compression_simulation.{CompressionSimulation, STGCompressionSimulation, fake_quantize_ste, STE}`` and
   ``optimizers.{Adam, SelectiveAdam, step_all, visibility_mask}`` and ``losses.{fused_ssim, photometric_loss}`` and
-  ``strategy.{Strategy, DefaultStrategy, MCMCStrategy}`` (``from gscodec_studio_amd.strategy import ...``, as in the reference) with
+  ``strategy.{Strategy, DefaultStrategy, MCMCStrategy, STG_Strategy, Modified_STG_Strategy}`` (``from gscodec_studio_amd.strategy import ...``, as in the reference) with
   ``relocation.compute_relocation``.
 """
 from ._wrapper import (

@@ -4,11 +4,14 @@
 //                   of every gaussian, in one launch instead of clone / scale / nonzero / gather / norm / index_add / scatter.
 // gs_inject_noise   MCMCStrategy's per-step perturbation of the means, from the raw parameters, in one launch.
 // gs_relocation     equation 9 of the MCMC paper (the opacity and scale of a gaussian that stands for n copies of itself).
+// gs_stg_omega_mask   STG_Strategy._zero_omegabymotion: which gaussians keep a trainable omega, and omega with the others zeroed.
+// gs_stg_freeze_grads STG_Strategy's per-step freeze: omega.grad *= mask, quats.grad *= !mask, both in place in one launch.
 //
-// All three are one thread per gaussian (or per packed row) in GS_BLOCK-thread blocks.  The two per-step kernels are streaming
+// All of them are one thread per gaussian (or per packed row) in GS_BLOCK-thread blocks.  The two per-step kernels are streaming
 // kernels; their minimum traffic per gaussian is 12 C + 8 bytes (+ 8 with the radii state) for the unpacked statistics (8 C of
 // them the gradient, of which a 64-byte-strided gradient row costs a whole 64-byte sector per camera instead) and 68 bytes for the
-// noise (14 floats read, 3 written).
+// noise (14 floats read, 3 written).  The freeze moves 65 bytes per gaussian (two 16-byte rows read and written, one mask byte), the
+// mask build 61 (3 of the motion row's floats -- whole sectors of it in practice --, 3 + 1 + 4 floats read, 4 floats + 1 byte written).
 #include "gs_common.h"
 
 namespace {
@@ -147,6 +150,62 @@ __global__ void __launch_bounds__(GS_BLOCK) relocation_kernel(uint32_t N, const 
     new_scales[b + 2] = (float)(coeff * (double)scales[b + 2]);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// gs_stg_omega_mask / gs_stg_freeze_grads
+// ---------------------------------------------------------------------------------------------------------------------------------
+template <bool VEC4>
+GS_DEV float4 load_row4(const float *p, uint64_t n) {
+    if (VEC4) return reinterpret_cast<const float4 *>(p)[n];
+    return make_float4(p[4 * n], p[4 * n + 1], p[4 * n + 2], p[4 * n + 3]);
+}
+
+template <bool VEC4>
+GS_DEV void store_row4(float *p, uint64_t n, float4 v) {
+    if (VEC4) {
+        reinterpret_cast<float4 *>(p)[n] = v;
+    } else {
+        p[4 * n] = v.x; p[4 * n + 1] = v.y; p[4 * n + 2] = v.z; p[4 * n + 3] = v.w;
+    }
+}
+
+// torch's operations in torch's order, uncontracted: sum(abs(motion[:, 0:3]), 1), max(exp(scales), 1), sigmoid = 1 / (1 + exp(-x))
+template <bool VEC4>
+__global__ void __launch_bounds__(GS_BLOCK) stg_omega_mask_kernel(uint32_t N, const float *__restrict__ motion, uint64_t motion_stride,
+                                                                  const float *__restrict__ scales, const float *__restrict__ opacities,
+                                                                  const float *__restrict__ omega, float motion_min, float scale_min,
+                                                                  float scale_max, float opacity_min, uint8_t *__restrict__ mask,
+                                                                  float *__restrict__ omega_new) {
+    GS_FP_STRICT;
+    const uint32_t n = blockIdx.x * GS_BLOCK + threadIdx.x;
+    if (n >= N) return;
+    const float *m = motion + (uint64_t)n * motion_stride;
+    const float moved = (fabsf(m[0]) + fabsf(m[1])) + fabsf(m[2]);
+    const uint64_t b = 3ull * n;
+    const float size = fmaxf(fmaxf(expf(scales[b]), expf(scales[b + 1])), expf(scales[b + 2]));
+    const float opacity = gs_mask_sigmoid(opacities[n]);
+    // (a NaN anywhere compares false, as in torch: the gaussian is frozen)
+    const bool keep = moved > motion_min && size > scale_min && size < scale_max && opacity > opacity_min;
+    const float k = keep ? 1.f : 0.f;  // mask.float() * omega: a non-finite omega under a zero mask stays non-finite
+    float4 o = load_row4<VEC4>(omega, n);
+    o.x *= k; o.y *= k; o.z *= k; o.w *= k;
+    mask[n] = keep ? 1 : 0;
+    store_row4<VEC4>(omega_new, n, o);
+}
+
+template <bool VEC4>
+__global__ void __launch_bounds__(GS_BLOCK) stg_freeze_grads_kernel(uint32_t N, const uint8_t *__restrict__ mask,
+                                                                    float *__restrict__ omega_grad, float *__restrict__ quats_grad) {
+    const uint32_t n = blockIdx.x * GS_BLOCK + threadIdx.x;
+    if (n >= N) return;
+    const bool keep = mask[n] != 0;
+    const float ko = keep ? 1.f : 0.f, kq = keep ? 0.f : 1.f;  // multiplied, not selected: NaN * 0 = NaN as in grad * mask
+    float4 o = load_row4<VEC4>(omega_grad, n), q = load_row4<VEC4>(quats_grad, n);
+    o.x *= ko; o.y *= ko; o.z *= ko; o.w *= ko;
+    q.x *= kq; q.y *= kq; q.z *= kq; q.w *= kq;
+    store_row4<VEC4>(omega_grad, n, o);
+    store_row4<VEC4>(quats_grad, n, q);
+}
+
 }  // namespace
 
 extern "C" int32_t gs_relocation(uint32_t N, const float *opacities, const float *scales, const int32_t *ratios, const float *binoms,
@@ -210,6 +269,43 @@ extern "C" int32_t gs_densify_stats(uint32_t C, uint32_t N, uint64_t nnz, const 
             hipLaunchKernelGGL(densify_stats_kernel<false>, grid, block, 0, st, C, N, grad, grad_row_stride, radii, sx, sy, extent, grad2d,
                                count, radii_state);
     }
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int32_t gs_stg_omega_mask(uint32_t N, const float *motion, uint64_t motion_row_stride, const float *scales,
+                                     const float *opacities, const float *omega, float motion_min, float scale_min, float scale_max,
+                                     float opacity_min, uint8_t *mask, float *omega_new, gs_stream_t stream) {
+    GS_CHECK_ARG(motion_row_stride >= 3, "motion_row_stride must be at least 3 floats");
+    if (N == 0) return 0;
+    GS_CHECK_ARG(motion && scales && opacities && omega, "null input");
+    GS_CHECK_ARG(mask && omega_new, "null mask / omega_new");
+    GS_CHECK_ARG(((uintptr_t)motion | (uintptr_t)scales | (uintptr_t)opacities | (uintptr_t)omega | (uintptr_t)omega_new) % 4 == 0,
+                 "float arrays must be 4-byte aligned");
+    const dim3 grid(gs_div_up(N, GS_BLOCK)), block(GS_BLOCK);
+    const hipStream_t st = (hipStream_t)stream;
+    if (((uintptr_t)omega | (uintptr_t)omega_new) % 16 == 0)
+        hipLaunchKernelGGL(stg_omega_mask_kernel<true>, grid, block, 0, st, N, motion, motion_row_stride, scales, opacities, omega,
+                           motion_min, scale_min, scale_max, opacity_min, mask, omega_new);
+    else
+        hipLaunchKernelGGL(stg_omega_mask_kernel<false>, grid, block, 0, st, N, motion, motion_row_stride, scales, opacities, omega,
+                           motion_min, scale_min, scale_max, opacity_min, mask, omega_new);
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int32_t gs_stg_freeze_grads(uint32_t N, const uint8_t *mask, float *omega_grad, float *quats_grad, gs_stream_t stream) {
+    if (N == 0) return 0;
+    GS_CHECK_ARG(mask, "null mask");
+    GS_CHECK_ARG(omega_grad && quats_grad, "null omega_grad / quats_grad");
+    GS_CHECK_ARG(omega_grad != quats_grad, "omega_grad and quats_grad must be different arrays");
+    GS_CHECK_ARG(((uintptr_t)omega_grad | (uintptr_t)quats_grad) % 4 == 0, "float arrays must be 4-byte aligned");
+    const dim3 grid(gs_div_up(N, GS_BLOCK)), block(GS_BLOCK);
+    const hipStream_t st = (hipStream_t)stream;
+    if (((uintptr_t)omega_grad | (uintptr_t)quats_grad) % 16 == 0)
+        hipLaunchKernelGGL(stg_freeze_grads_kernel<true>, grid, block, 0, st, N, mask, omega_grad, quats_grad);
+    else
+        hipLaunchKernelGGL(stg_freeze_grads_kernel<false>, grid, block, 0, st, N, mask, omega_grad, quats_grad);
     GS_CHECK_LAUNCH();
     return 0;
 }

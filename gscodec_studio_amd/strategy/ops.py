@@ -1,8 +1,9 @@
 """The operations the densification strategies are made of (counterpart of the reference's ``gsplat/strategy/ops.py``).
 
-Two of them run on every training step and are one HIP launch each: ``densify_stats`` (``DefaultStrategy._update_state``,
-``gs_densify_stats``) and ``inject_noise_to_position`` (``MCMCStrategy``, ``gs_inject_noise``).  ``relocate`` / ``sample_add``
-go through ``relocation.compute_relocation`` (``gs_relocation``).  The others change the SET of gaussians every hundred steps or
+Three of them run on every training step and are one HIP launch each: ``densify_stats`` (``DefaultStrategy._update_state``,
+``gs_densify_stats``), ``inject_noise_to_position`` (``MCMCStrategy``, ``gs_inject_noise``) and ``stg_freeze_grads``
+(``STG_Strategy``'s omega / rotation freeze, ``gs_stg_freeze_grads``).  ``stg_omega_mask`` (``gs_stg_omega_mask``) builds the mask the
+freeze applies.  ``relocate`` / ``sample_add`` go through ``relocation.compute_relocation`` (``gs_relocation``).  The others change the SET of gaussians every hundred steps or
 so and are torch indexing: one gather / ``cat`` per tensor.
 
 All of them replace ``params[name]`` by a new ``Parameter`` and move the optimizer's state to it, for ``torch.optim.Adam``,
@@ -25,7 +26,8 @@ from ..relocation import compute_relocation
 
 Params = Union[Dict[str, torch.nn.Parameter], torch.nn.ParameterDict]
 
-__all__ = ["duplicate", "split", "remove", "reset_opa", "relocate", "sample_add", "inject_noise_to_position", "densify_stats"]
+__all__ = ["duplicate", "split", "remove", "reset_opa", "relocate", "sample_add", "inject_noise_to_position", "densify_stats",
+           "stg_omega_mask", "stg_freeze_grads"]
 
 
 @torch.no_grad()
@@ -306,3 +308,60 @@ def densify_stats(grad: Tensor, radii: Tensor, gaussian_ids: Optional[Tensor], w
     with _device_of(grad):
         B.call("gs_densify_stats", C, N, nnz, B.ptr(src), stride, B.ptr(radii), B.ptr(gaussian_ids), width / 2.0 * n_cameras,
                height / 2.0 * n_cameras, float(max(width, height)), B.ptr(grad2d), B.ptr(count), B.ptr(radii_state), _stream(grad))
+
+
+@torch.no_grad()
+def stg_omega_mask(motion: Tensor, scales: Tensor, opacities: Tensor, omega: Tensor, motion_min: float = 0.3, scale_min: float = 0.2,
+                   scale_max: float = 0.6, opacity_min: float = 0.7):
+    """The mask of ``STG_Strategy._zero_omegabymotion`` and the masked omega, from the raw parameters in one ``gs_stg_omega_mask``
+    launch: ``mask = sum|motion[:, 0:3]| > motion_min & scale_min < max exp(scales) < scale_max & sigmoid(opacities) > opacity_min``
+    (bool ``[N, 1]``) and ``omega_new = mask.float() * omega`` (``[N, 4]``).  ``motion`` is ``[N, M >= 3]`` and read in place through
+    its row stride; ``opacities`` is ``[N]`` or ``[N, 1]``."""
+    what = "strategy.ops.stg_omega_mask"
+    _require_gpu(omega, what)
+    motion, scales, opacities, omega = motion.detach(), scales.detach(), opacities.detach(), omega.detach()
+    N = omega.shape[0]
+    if motion.dim() != 2 or motion.shape[0] != N or motion.shape[1] < 3:
+        raise RuntimeError(f"{what}: motion is {tuple(motion.shape)}, expected [{N}, >= 3]")
+    for t, name, shape in ((scales, "scales", (N, 3)), (omega, "omega", (N, 4))):
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"{what}: {name} is {tuple(t.shape)}, expected {shape}")
+    if opacities.numel() != N:
+        raise RuntimeError(f"{what}: opacities is {tuple(opacities.shape)}, expected [{N}] or [{N}, 1]")
+    for t, name in ((motion, "motion"), (scales, "scales"), (opacities, "opacities"), (omega, "omega")):
+        _as_f32(t, what, name)
+        if t.device != omega.device:
+            raise RuntimeError(f"{what}: {name} is on {t.device}, omega on {omega.device}")
+    if motion.stride(1) != 1 or (N > 1 and motion.stride(0) < 3):
+        motion = motion.contiguous()
+    stride = motion.stride(0) if N > 1 else motion.shape[1]
+    scales, opacities, omega = scales.contiguous(), opacities.reshape(N).contiguous(), omega.contiguous()
+    mask = torch.empty((N, 1), dtype=torch.bool, device=omega.device)
+    omega_new = torch.empty_like(omega)
+    with _device_of(omega):
+        B.call("gs_stg_omega_mask", N, B.ptr(motion), int(stride), B.ptr(scales), B.ptr(opacities), B.ptr(omega), float(motion_min),
+               float(scale_min), float(scale_max), float(opacity_min), B.ptr(mask), B.ptr(omega_new), _stream(omega))
+    return mask, omega_new
+
+
+@torch.no_grad()
+def stg_freeze_grads(mask: Tensor, omega_grad: Tensor, quats_grad: Tensor) -> None:
+    """``omega_grad *= mask`` and ``quats_grad *= ~mask`` row by row, IN PLACE, in one ``gs_stg_freeze_grads`` launch: no allocation,
+    no host synchronisation.  ``mask``: bool (or uint8 0 / 1) ``[N]`` / ``[N, 1]``; the gradients: contiguous float32 ``[N, 4]``.
+    The rows are multiplied by 0.0 or 1.0, so a non-finite gradient stays non-finite under a zero, as in ``grad * mask``."""
+    what = "strategy.ops.stg_freeze_grads"
+    for t, name in ((omega_grad, "omega.grad"), (quats_grad, "quats.grad")):
+        if not isinstance(t, Tensor):  # (what the reference's `None * mask` raises)
+            raise TypeError(f"{what}: {name} is {type(t).__name__}, not a tensor -- the freeze runs after backward()")
+    _require_gpu(omega_grad, what)
+    N = omega_grad.shape[0]
+    if mask.dtype not in (torch.bool, torch.uint8) or mask.numel() != N or mask.device != omega_grad.device or not mask.is_contiguous():
+        raise RuntimeError(f"{what}: mask must be a contiguous bool / uint8 tensor of {N} elements on {omega_grad.device}, got "
+                           f"{mask.dtype} {tuple(mask.shape)} on {mask.device}")
+    for t, name in ((omega_grad, "omega.grad"), (quats_grad, "quats.grad")):
+        _as_f32(t, what, name)
+        if tuple(t.shape) != (N, 4) or not t.is_contiguous() or t.device != omega_grad.device:
+            raise RuntimeError(f"{what}: {name} must be a contiguous [{N}, 4] tensor on {omega_grad.device} (it is scaled in place), "
+                               f"got {tuple(t.shape)} on {t.device}")
+    with _device_of(omega_grad):
+        B.call("gs_stg_freeze_grads", N, B.ptr(mask), B.ptr(omega_grad), B.ptr(quats_grad), _stream(omega_grad))

@@ -41,7 +41,8 @@ extern "C" {
  * through shifted argument lists silently otherwise.
  * ABI 6 later gained the optimizer entries (gs_adam_desc, gs_adam_multi, gs_adam_multi_max, gs_adam_desc_layout) and the loss
  * entries (gs_ssim_fwd, gs_ssim_bwd, gs_ssim_work_bytes, gs_ssim_window): additive, no existing signature changed.  The
- * densification-strategy entries (gs_relocation, gs_inject_noise, gs_densify_stats) are additive in the same way. */
+ * densification-strategy entries (gs_relocation, gs_inject_noise, gs_densify_stats) are additive in the same way, and so are
+ * the two of the spacetime strategies (gs_stg_omega_mask, gs_stg_freeze_grads). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -1133,7 +1134,15 @@ int32_t gs_ssim_bwd(const float *x, const int64_t *x_strides, const float *y, co
  *   gaussian_ids int64 [nnz] (packed): grad [nnz] rows, radii int32 [nnz]; the same per row with radii > 0 and an id < N, through
  *     float atomic adds and an integer atomic max on the bit pattern of the non-negative radii_state.  C >= 1 is still required.
  *   radii_state may be NULL.  With several cameras radii_state is the TRUE maximum (the reference's indexed assignment keeps
- *   whichever duplicate index the scatter writes last; for C == 1 the two agree). */
+ *   whichever duplicate index the scatter writes last; for C == 1 the two agree).
+ * gs_stg_omega_mask: STG_Strategy._zero_omegabymotion (STG_Strategy.py:326-359) from the RAW parameters.  motion: rows of
+ *   motion_row_stride >= 3 floats, the first three read; scales (logs) [N,3]; opacities (logits) [N]; omega [N,4].
+ *   mask[n] (one byte, 0 / 1) = |m0| + |m1| + |m2| > motion_min && scale_min < max_k exp(scales[n,k]) < scale_max &&
+ *   1 / (1 + exp(-opacities[n])) > opacity_min (the reference's constants: 0.3, 0.2, 0.6, 0.7); omega_new[n,:] = omega[n,:] * mask[n].
+ *   IEEE operations in torch's order, no fma contraction.  omega_new is a different array than omega.
+ * gs_stg_freeze_grads: the per-step freeze (STG_Strategy.py:105-110, 131-136), in place: omega_grad[n,:] *= mask[n] and
+ *   quats_grad[n,:] *= !mask[n], both [N,4]; a multiplication by 0.0f / 1.0f (a non-finite gradient under a zero stays
+ *   non-finite, as in grad * mask).  16-byte rows when both arrays are 16-byte aligned. */
 int32_t gs_relocation(uint32_t N, const float *opacities, const float *scales, const int32_t *ratios, const float *binoms,
                       uint32_t n_max, float *new_opacities, float *new_scales, gs_stream_t stream);
 int32_t gs_inject_noise(uint32_t N, float *means, const float *quats, const float *scales, const float *opacities,
@@ -1141,6 +1150,10 @@ int32_t gs_inject_noise(uint32_t N, float *means, const float *quats, const floa
 int32_t gs_densify_stats(uint32_t C, uint32_t N, uint64_t nnz, const float *grad, uint64_t grad_row_stride, const int32_t *radii,
                          const int64_t *gaussian_ids, float sx, float sy, float extent, float *grad2d, float *count,
                          float *radii_state, gs_stream_t stream);
+int32_t gs_stg_omega_mask(uint32_t N, const float *motion, uint64_t motion_row_stride, const float *scales, const float *opacities,
+                          const float *omega, float motion_min, float scale_min, float scale_max, float opacity_min, uint8_t *mask,
+                          float *omega_new, gs_stream_t stream);
+int32_t gs_stg_freeze_grads(uint32_t N, const uint8_t *mask, float *omega_grad, float *quats_grad, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Native step driver (round 4): the launches of one rasterization() forward of the common training case --
