@@ -5,7 +5,8 @@ Public surface (mirrors the reference's ``gsplat`` package for this path only):
   ``compression_simulation.{CompressionSimulation, STGCompressionSimulation, fake_quantize_ste, STE}`` and
   ``optimizers.{Adam, SelectiveAdam, step_all, visibility_mask}`` and ``losses.{fused_ssim, photometric_loss}`` and
   ``strategy.{Strategy, DefaultStrategy, MCMCStrategy, STG_Strategy, Modified_STG_Strategy}`` (``from gscodec_studio_amd.strategy import ...``, as in the reference) with
-  ``relocation.compute_relocation``.
+  ``relocation.compute_relocation``, and ``bilagrid.{BilateralGrid, slice, slice_image, total_variation_loss,
+  color_affine_transform}`` (``from gscodec_studio_amd.bilagrid import ...`` in place of ``from lib_bilagrid import ...``).
 """
 from ._wrapper import (
     accumulate,

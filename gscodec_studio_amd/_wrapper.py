@@ -2137,3 +2137,61 @@ def ssim_bwd(x: Tensor, x_strides, y: Tensor, y_strides, shape, padding: str, wo
         B.call("gs_ssim_bwd", x.data_ptr(), ctypes.addressof(xs), y.data_ptr(), ctypes.addressof(ys), b, c, h, w, SSIM_PADDING[padding],
                work.data_ptr(), work.numel(), B.ptr(grad_ssim), float(w_ssim), B.ptr(grad_l1), float(w_l1), dx.data_ptr(),
                ctypes.addressof(ds), _stream(x))
+
+
+# ---------------------------------------------------------------------------
+# Bilateral-grid colour correction  (examples/lib_bilagrid.py's slice / total_variation_loss; csrc/bilagrid.hip)
+# ---------------------------------------------------------------------------
+def _bilagrid_geo(grids: Tensor, shape, xy: Optional[Tensor], xy_strides, rgb: Tensor, rgb_strides, idx: Optional[Tensor], idx_stride: int):
+    n, _, l, h, w = (int(v) for v in grids.shape)
+    b, d1, d2 = (int(v) for v in shape)
+    xs = _strides4(xy_strides) if xy is not None else None
+    rs = _strides4(rgb_strides)
+    args = (grids.data_ptr(), n, l, h, w, b, d1, d2, B.ptr(xy), ctypes.addressof(xs) if xs is not None else None, rgb.data_ptr(),
+            ctypes.addressof(rs), B.ptr(idx), int(idx_stride))
+    return args, (xs, rs)  # the stride arrays stay alive until the call returns
+
+
+def bilagrid_slice_fwd(grids: Tensor, shape, xy: Optional[Tensor], xy_strides, rgb: Tensor, rgb_strides, idx: Optional[Tensor],
+                       idx_stride: int, want_rgb: bool = True, want_affine: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """``gs_bilagrid_slice_fwd`` over the logical ``[B, D1, D2]`` point ``shape``: (rgb_out ``[B, D1, D2, 3]`` or None, the sliced
+    3x4 matrices ``[B, D1, D2, 12]`` or None), contiguous, on the current stream.  ``grids`` is a contiguous ``[N, 12, L, H, W]``;
+    ``xy`` None means the pixel centres; ``idx`` is an int64 device tensor read at ``b * idx_stride`` (None: grid b)."""
+    out_rgb = torch.empty((*shape, 3), dtype=torch.float32, device=grids.device) if want_rgb else None
+    out_aff = torch.empty((*shape, 12), dtype=torch.float32, device=grids.device) if want_affine else None
+    args, keep = _bilagrid_geo(grids, shape, xy, xy_strides, rgb, rgb_strides, idx, idx_stride)
+    with _device_of(grids):
+        B.call("gs_bilagrid_slice_fwd", *args, B.ptr(out_rgb), B.ptr(out_aff), _stream(grids))
+    del keep
+    return out_rgb, out_aff
+
+
+def bilagrid_slice_bwd(grids: Tensor, shape, xy: Optional[Tensor], xy_strides, rgb: Tensor, rgb_strides, idx: Optional[Tensor],
+                       idx_stride: int, v_out_rgb: Optional[Tensor], v_out_affine: Optional[Tensor], want_grids: bool = True,
+                       want_rgb: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """``gs_bilagrid_slice_bwd``: (v_grids like ``grids`` or None, v_rgb ``[B, D1, D2, 3]`` contiguous or None) from the contiguous
+    upstream gradients of rgb_out and / or of the matrices."""
+    v_grids = torch.empty_like(grids) if want_grids else None  # cleared by the entry point
+    v_rgb = torch.empty((*shape, 3), dtype=torch.float32, device=grids.device) if want_rgb else None
+    args, keep = _bilagrid_geo(grids, shape, xy, xy_strides, rgb, rgb_strides, idx, idx_stride)
+    with _device_of(grids):
+        B.call("gs_bilagrid_slice_bwd", *args, B.ptr(v_out_rgb), B.ptr(v_out_affine), B.ptr(v_grids), B.ptr(v_rgb), _stream(grids))
+    del keep
+    return v_grids, v_rgb
+
+
+def bilagrid_tv_fwd(x: Tensor) -> Tensor:
+    """``gs_bilagrid_tv_fwd`` of a contiguous float32 ``[N, C, L, H, W]``: the total variation as a 0-d device tensor."""
+    work = torch.empty(int(B.query("gs_bilagrid_tv_work_bytes")), dtype=torch.uint8, device=x.device)
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    with _device_of(x):
+        B.call("gs_bilagrid_tv_fwd", x.data_ptr(), *(int(v) for v in x.shape), work.data_ptr(), work.numel(), out.data_ptr(), _stream(x))
+    return out
+
+
+def bilagrid_tv_bwd(x: Tensor, grad: Tensor) -> Tensor:
+    """``gs_bilagrid_tv_bwd``: grad (a 0-d float32 device tensor) times the gradient of the total variation, shaped like x."""
+    v_x = torch.empty_like(x)
+    with _device_of(x):
+        B.call("gs_bilagrid_tv_bwd", x.data_ptr(), *(int(v) for v in x.shape), grad.data_ptr(), v_x.data_ptr(), _stream(x))
+    return v_x

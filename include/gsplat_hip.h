@@ -42,7 +42,8 @@ extern "C" {
  * ABI 6 later gained the optimizer entries (gs_adam_desc, gs_adam_multi, gs_adam_multi_max, gs_adam_desc_layout) and the loss
  * entries (gs_ssim_fwd, gs_ssim_bwd, gs_ssim_work_bytes, gs_ssim_window): additive, no existing signature changed.  The
  * densification-strategy entries (gs_relocation, gs_inject_noise, gs_densify_stats) are additive in the same way, and so are
- * the two of the spacetime strategies (gs_stg_omega_mask, gs_stg_freeze_grads). */
+ * the two of the spacetime strategies (gs_stg_omega_mask, gs_stg_freeze_grads), and the bilateral-grid entries
+ * (gs_bilagrid_slice_fwd / _bwd, gs_bilagrid_tv_fwd / _bwd, gs_bilagrid_tv_work_bytes). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -1112,6 +1113,41 @@ int32_t gs_ssim_fwd(const float *x, const int64_t *x_strides, const float *y, co
 int32_t gs_ssim_bwd(const float *x, const int64_t *x_strides, const float *y, const int64_t *y_strides, uint32_t B, uint32_t C,
                     uint32_t H, uint32_t W, int32_t padding, const void *work, uint64_t work_bytes, const float *grad_ssim,
                     float w_ssim, const float *grad_l1, float w_l1, float *dx, const int64_t *dx_strides, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * B1  The trainers' bilateral-grid colour correction (examples/lib_bilagrid.py: slice, BilateralGrid.forward,
+ * total_variation_loss), forward and backward.  No host synchronisation.
+ * grids: fp32 [N, 12, L, H, W] contiguous (12 L H W < 2^31).  Points: a logical [B, D1, D2] array (B D1 D2 < 2^31): an image
+ * batch [B, Himg, Wimg], rays [B, 1, P] or [B, 1, 1].  rgb: fp32 read through rgb_strides = element strides {b, i, j, channel}
+ * (HOST array of 4; columns 0-2 of a 4-channel render work without a copy).  xy: fp32 read through xy_strides in the same
+ * way (a b stride of 0 broadcasts one coordinate image), values in [0, 1]; NULL: the pixel centres x = (j + 0.5) / D2,
+ * y = (i + 0.5) / D1.  grid_idx: DEVICE int64, entry b reads grid grid_idx[b * idx_stride] clamped to [0, N - 1]; NULL: grid
+ * min(b, N - 1).
+ * Per point: z = 2 (0.299 r + 0.587 g + 0.114 b) - 1, x, y <- 2 (xy - 0.5); F.grid_sample's align_corners=True,
+ * padding_mode="border" trilinear interpolation ((c + 1) / 2 (size - 1) clamped to [0, size - 1]) of 12 values A, a row-major
+ * 3x4 matrix; rgb_out = A[:, :3] rgb + A[:, 3].
+ * gs_bilagrid_slice_fwd writes out_rgb [B, D1, D2, 3] and / or out_affine [B, D1, D2, 12] (16-byte aligned), contiguous.
+ * gs_bilagrid_slice_bwd: from v_out_rgb [B, D1, D2, 3] and / or v_out_affine [B, D1, D2, 12] (contiguous; NULL: zero) writes
+ * v_rgb [B, D1, D2, 3] (contiguous; the guidance term is 0 where z was clamped, as torch's) and v_grids [N, 12, L, H, W], which
+ * it clears first; either may be NULL.  xy gets no gradient.  The grid gradient is summed per workgroup in LDS and added once
+ * per workgroup with float atomics: v_grids can differ in its last bits from run to run, v_rgb cannot.
+ * gs_bilagrid_tv_fwd: out[0] (DEVICE) = total_variation_loss(x) for fp32 x [N, C, L, H, W] contiguous (N C L H W < 2^31):
+ * (1 / N) sum over the axes L, H, W of sum (x[i+1] - x[i])^2 / max(elements per batch entry of the differenced tensor, 1); an
+ * axis of size 1 contributes 0.  Summed in double in a fixed order: bit-identical from run to run.  work: caller-owned device
+ * memory, 8-byte aligned, of gs_bilagrid_tv_work_bytes() bytes.  gs_bilagrid_tv_bwd: v_x = grad[0] * d out / d x (grad a
+ * DEVICE scalar), a gather over the <= 6 neighbours of each element. */
+int32_t gs_bilagrid_slice_fwd(const float *grids, uint32_t N, uint32_t L, uint32_t H, uint32_t W, uint32_t B, uint32_t D1,
+                              uint32_t D2, const float *xy, const int64_t *xy_strides, const float *rgb, const int64_t *rgb_strides,
+                              const int64_t *grid_idx, int64_t idx_stride, float *out_rgb, float *out_affine, gs_stream_t stream);
+int32_t gs_bilagrid_slice_bwd(const float *grids, uint32_t N, uint32_t L, uint32_t H, uint32_t W, uint32_t B, uint32_t D1,
+                              uint32_t D2, const float *xy, const int64_t *xy_strides, const float *rgb, const int64_t *rgb_strides,
+                              const int64_t *grid_idx, int64_t idx_stride, const float *v_out_rgb, const float *v_out_affine,
+                              float *v_grids, float *v_rgb, gs_stream_t stream);
+uint64_t gs_bilagrid_tv_work_bytes(void);
+int32_t gs_bilagrid_tv_fwd(const float *x, uint32_t N, uint32_t C, uint32_t L, uint32_t H, uint32_t W, void *work,
+                           uint64_t work_bytes, float *out, gs_stream_t stream);
+int32_t gs_bilagrid_tv_bwd(const float *x, uint32_t N, uint32_t C, uint32_t L, uint32_t H, uint32_t W, const float *grad,
+                           float *v_x, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * D1  The densification strategies (gsplat/strategy/default.py, mcmc.py, ops.py; gsplat/relocation.py).  One thread per
