@@ -451,7 +451,6 @@ class _SphericalHarmonics(torch.autograd.Function):
 # unfused public ops: world_to_cam, proj / persp_proj, rasterize_to_indices_in_range
 # (reference _wrapper.py:118-200, 571-643, 709-772)
 # ---------------------------------------------------------------------------
-_CAMERA_MODELS = {"pinhole": 0, "ortho": 1, "fisheye": 2}
 
 
 def world_to_cam(
@@ -859,7 +858,11 @@ _FUSE_SH_BWD = os.environ.get("GS_FUSE_SH_BWD", "1") == "1"  # (A/B switch: 0 = 
 PREFILL_ENABLED = os.environ.get("GS_GRAD_PREFILL", "1") != "0"
 
 
-_FAST_MAX_CHANNELS = 32  # channel counts the tile forward / segmented backward cover (csrc/rasterize.hip: FAST_MAX_CHANNELS)
+def _grad_layout(channels: int) -> Tuple[int, bool]:
+    """(``packed16`` of gs_rasterize_bwd, does the forward zero-fill the gradients on the side): 1..4 channels all in [n_elems,16] rows (1), up
+    to csrc/rasterize.hip's FAST_MAX_CHANNELS geometry rows + dense colour gradients (2), beyond separate arrays the backward fills (0)."""
+    packed16 = 1 if channels <= 4 else 2 if channels <= 32 else 0
+    return packed16, packed16 != 0
 
 
 # The order in which the per-gaussian gradients of ONE rasterization() call are carved out of their common buffer (GradPrefill.carve).
@@ -1859,7 +1862,7 @@ def _grad_fill(n_elems: int, channels: int, prefill: Optional[GradPrefill], dev)
     extra = prefill.floats() if prefill is not None else 0
     if extra:
         extra += 64  # slack behind the last piece (a multi-GPU reduction rounds the span of all pieces up into it)
-    wide = _pad64(n_elems * channels) if channels > 4 else 0
+    wide = _pad64(n_elems * channels) if _grad_layout(channels)[0] == 2 else 0
     fill = torch.empty(n_elems * 16 + wide + extra, dtype=torch.float32, device=dev)
     grad_colors = fill[n_elems * 16:n_elems * 16 + n_elems * channels] if wide else None
     if extra:
@@ -1912,7 +1915,7 @@ class _RasterizeToPixels(torch.autograd.Function):
             # the packed gradient rows of the backward ([n_elems,16], accumulated with atomics) are zero-filled by THIS
             # launch, as a side job of the tile workgroups: no fill pass in the backward
             grad_rows = grad_colors = fill = None
-            if needs_bwd and channels <= _FAST_MAX_CHANNELS and n_elems > 0:
+            if needs_bwd and _grad_layout(channels)[1] and n_elems > 0:
                 fill, grad_rows, grad_colors, _ = _grad_fill(n_elems, channels, prefill, dev)
                 grad_rows = grad_rows.view(opacities.shape + (16,))
                 if grad_colors is not None:
@@ -1954,10 +1957,10 @@ def _rasterize_bwd(ctx, v_render_colors: Optional[Tensor], v_render_alphas: Opti
     # accumulated with atomics -> zero-filled.  Up to 4 channels: ONE packed [n_elems,16] buffer
     # (64-byte row per splat: vx vy | ca cb cc | o | c0..c3 | ax ay) so that a splat's whole
     # gradient is one L2 request; the tensors handed to autograd are views of it.
-    packed = channels <= _FAST_MAX_CHANNELS
+    packed16, _ = _grad_layout(channels)
     # deterministic mode: fixed-point sums in an int64 buffer of their own; the float rows are then WRITTEN by a second kernel
     det = torch.zeros((n_elems, 2, 12), dtype=torch.int64, device=means2d.device) if (ctx.deterministic and n_elems > 0) else None
-    if packed:
+    if packed16:
         P, ctx.grad_rows = ctx.grad_rows, None
         if P is None:
             # (the deterministic route's finalize kernel WRITES every row -- except when there is nothing to composite:
@@ -1966,10 +1969,10 @@ def _rasterize_bwd(ctx, v_render_colors: Optional[Tensor], v_render_alphas: Opti
                 opacities.shape + (16,), dtype=torch.float32, device=means2d.device)
         v_means2d, v_conics, v_opacities = P[..., 0:2], P[..., 2:5], P[..., 5]
         v_means2d_abs = P[..., 10:12] if ctx.absgrad else None
-        if channels <= 4:
+        if packed16 == 1:
             v_colors = P[..., 6:6 + channels]
             out_ptrs = (B.ptr(P) if ctx.absgrad else None, B.ptr(P), None, None, None)
-        else:  # geometry rows + the colour gradients in their own dense array (packed16 = 2)
+        else:  # geometry rows + the colour gradients in their own dense array
             v_colors, ctx.grad_colors = ctx.grad_colors, None
             if v_colors is None:
                 v_colors = torch.zeros(opacities.shape + (channels,), dtype=torch.float32, device=means2d.device)
@@ -1989,7 +1992,7 @@ def _rasterize_bwd(ctx, v_render_colors: Optional[Tensor], v_render_alphas: Opti
                ctx.width, ctx.height, ctx.tile_size,
                tile_width, tile_height, B.ptr(isect_offsets), B.ptr(flatten_ids), B.ptr(render_colors),
                B.ptr(render_alphas), B.ptr(last_ids), B.ptr(v_render_colors), B.ptr(v_render_alphas), vrc_pix, vrc_ch, *out_ptrs,
-               (1 if channels <= 4 else 2) if packed else 0, B.ptr(det), ctypes.addressof(plan) if plan is not None else None,
+               packed16, B.ptr(det), ctypes.addressof(plan) if plan is not None else None,
                B.ptr(scratch) if plan is not None else None, _stream(means2d))
     if ctx.absgrad:
         means2d.absgrad = v_means2d_abs

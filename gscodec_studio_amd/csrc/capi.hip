@@ -93,7 +93,7 @@ extern "C" int32_t gs_rasterize_fwd(
             { gs_set_error("rasterize: zero fill failed"); return 1; }
         return 0;
     }
-    int32_t rc = raster_wave_fwd(a, plan, scratch, zero_fill, zero_fill_bytes, (hipStream_t)stream);
+    int32_t rc = raster_dispatch_fwd(a, plan, scratch, zero_fill, zero_fill_bytes, (hipStream_t)stream);
     if (rc) return rc;
     GS_CHECK_LAUNCH();
     return 0;
@@ -144,7 +144,7 @@ extern "C" int32_t gs_rasterize_bwd(
     GS_CHECK_ARG(plan == nullptr || raster_plan_ok(plan, C * tile_width * tile_height, n_isects, channels),
                  "plan was not made by gs_rasterize_plan for this (tile count, n_isects, channels)");
     if (C == 0 || image_width == 0 || image_height == 0 || n_isects == 0) return 0;
-    int32_t rc = raster_wave_bwd(a, ga, render_colors, plan, scratch, (hipStream_t)stream);
+    int32_t rc = raster_dispatch_bwd(a, ga, render_colors, plan, scratch, (hipStream_t)stream);
     if (rc) return rc;
     GS_CHECK_LAUNCH();
     return 0;

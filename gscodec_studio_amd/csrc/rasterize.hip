@@ -778,13 +778,12 @@ __global__ void __launch_bounds__(ORDER_THREADS) tile_order_kernel(uint32_t n_ti
 }
 
 template <int CDIM>
-void launch_tile_fwd(const RasterArgs &a, float *ckpt, int32_t seg, int32_t solo_min, uint32_t *cost_head, uint32_t *cost_body,
-                     uint32_t *body_tile, uint32_t *class_count, ZeroFill zf, hipStream_t st, uint32_t ch_off = 0u, uint32_t cnt = (uint32_t)CDIM) {
+void launch_tile_fwd(const RasterArgs &a, const RasterScratch &v, int32_t solo_min, ZeroFill zf, hipStream_t st, uint32_t ch_off, uint32_t cnt) {
     dim3 grid(a.C * a.tile_width * a.tile_height);
-    if (ckpt != nullptr)
-        hipLaunchKernelGGL((raster_tile_fwd_kernel<CDIM, true>), grid, dim3(256), 0, st, a, ckpt, seg, solo_min, cost_head, cost_body, body_tile, class_count, zf, ch_off, cnt);
+    if (v.ckpt != nullptr)
+        hipLaunchKernelGGL((raster_tile_fwd_kernel<CDIM, true>), grid, dim3(256), 0, st, a, v.ckpt, v.seg, solo_min, v.cost_head, v.cost_body, v.body_tile, v.class_count, zf, ch_off, cnt);
     else
-        hipLaunchKernelGGL((raster_tile_fwd_kernel<CDIM, false>), grid, dim3(256), 0, st, a, ckpt, seg, solo_min, cost_head, cost_body, body_tile, class_count, zf, ch_off, cnt);
+        hipLaunchKernelGGL((raster_tile_fwd_kernel<CDIM, false>), grid, dim3(256), 0, st, a, v.ckpt, v.seg, solo_min, v.cost_head, v.cost_body, v.body_tile, v.class_count, zf, ch_off, cnt);
 }
 
 // ---------------------------------------------------------------------------
@@ -1356,8 +1355,8 @@ __global__ void __launch_bounds__(GS_WAVE, GS_SEG_WAVES) raster_seg_bwd_kernel(R
 
 // segmented launch: one wave per (tile, segment) item, 4 pixels per lane
 template <int CDIM>
-void launch_bwd_seg(const RasterArgs &a, const RasterGradArgs &ga, uint32_t max_items, int use_va, const SegArgs &sg, hipStream_t st) {
-    dim3 grid(max_items, 1);
+void launch_bwd_seg(const RasterArgs &a, const RasterGradArgs &ga, int use_va, const SegArgs &sg, hipStream_t st) {
+    dim3 grid(sg.max_items, 1);
     const bool abs = ga.v_means2d_abs != nullptr, det = ga.det != nullptr;
     if (abs && det) hipLaunchKernelGGL((raster_seg_bwd_kernel<CDIM, true, true>), grid, dim3(GS_WAVE), 0, st, a, ga, use_va, sg);
     else if (abs) hipLaunchKernelGGL((raster_seg_bwd_kernel<CDIM, true, false>), grid, dim3(GS_WAVE), 0, st, a, ga, use_va, sg);
@@ -1449,13 +1448,8 @@ __global__ void __launch_bounds__(GS_BLOCK) raster_det_finalize_kernel(uint32_t 
 
 // ---------------------------------------------------------------------------
 // host side
-// scratch layout (the SAME buffer and the SAME plan must be handed to gs_rasterize_fwd and to the matching
-// gs_rasterize_bwd; the buffer's contents must be preserved in between):
-//   [0, 256)                      item counters of the 32 cost classes (uint32) + padding
-//   [256, 256 + items)            (tile, k) work items of the segmented backward (uint2), one region per cost class
-//   [.., .. + cost)               cost of every work item as counted by the forward ([tile][4] + [boundary][4] uint32)
-//                                 and the owner tile of every list boundary
-//   [.., .. + ckpt)               forward checkpoints, (n_isects / seg + 2) x (channels + 1) x 256 floats
+// The SAME scratch buffer and the SAME plan must be handed to gs_rasterize_fwd and to the matching gs_rasterize_bwd, the
+// buffer's contents preserved in between; its regions: RasterScratch (rasterize_common.h), laid out by scratch_view.
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -1470,38 +1464,57 @@ namespace {
 //   xcd_fwd / xcd_bwd   work items per XCD group (xcd_remap).  16 tiles / 16 segment items.
 constexpr uint32_t PLAN_MAGIC = 0x47535033u; // "GSP3"
 
-struct ScratchLayout {
-    size_t off_items, off_cost_head, off_cost_body, off_body_tile, off_ckpt, off_order, total;
-    uint32_t max_items, n_bounds;
-};
-
 // channel counts the tile forward / segmented backward cover: 1..4 in one launch, 5..16 in one launch of the wide instances,
 // 17..32 as two launches over halves (rasterize_wide.hip)
 constexpr uint32_t FAST_MAX_CHANNELS = 32;
 
-ScratchLayout scratch_layout(uint32_t n_tiles_all, uint32_t n_isects, uint32_t channels, int32_t seg) {
-    ScratchLayout L;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t o = 256;
-    L.n_bounds = (seg > 0 ? n_isects / (uint32_t)seg : 0) + 2; // list boundaries k * seg, k < n_bounds
-    L.max_items = n_tiles_all + L.n_bounds;
-    L.off_items = o;
-    if (seg > 0 && channels <= FAST_MAX_CHANNELS) o += up((size_t)COST_CLASSES * L.max_items * sizeof(uint2));
-    L.off_cost_head = o; // per (tile, quadrant wave): cost of the tile's first backward segment
-    o += up((size_t)n_tiles_all * 4 * sizeof(uint32_t));
-    L.off_cost_body = o; // per (segment boundary, quadrant wave): cost of the later segments
-    if (seg > 0 && channels <= FAST_MAX_CHANNELS) o += up((size_t)L.n_bounds * 4 * sizeof(uint32_t));
-    L.off_body_tile = o; // per segment boundary: the tile that owns it
-    if (seg > 0 && channels <= FAST_MAX_CHANNELS) o += up((size_t)L.n_bounds * sizeof(uint32_t));
-    L.off_ckpt = o;
-    if (seg > 0 && channels <= FAST_MAX_CHANNELS) o += up(((size_t)n_isects / seg + 2) * (channels + 1) * 256 * sizeof(float));
-    L.off_order = o; // the forward's tile order, heaviest lists first (tile_order_kernel)
-    if (channels <= FAST_MAX_CHANNELS) o += up((size_t)n_tiles_all * sizeof(uint32_t));
-    L.total = o;
-    return L;
+// The forward route: the tile kernel wherever an instance covers the channel count -- the wide instances only under a
+// caller's plan --, the generic kernel otherwise.
+RasterRoute raster_route_fwd(uint32_t channels, const gs_raster_plan *plan) {
+    if (channels <= 4u) return RasterRoute::TILE_NARROW;
+    return (channels <= FAST_MAX_CHANNELS && plan != nullptr) ? RasterRoute::TILE_WIDE : RasterRoute::WAVE_GENERIC;
 }
 
-ScratchLayout scratch_layout(const gs_raster_plan &p) { return scratch_layout(p.n_tiles_all, p.n_isects, p.channels, p.seg); }
+// Does the forward under this plan, handed the plan's scratch, leave checkpoints, costs and the work list behind?
+bool plan_has_ckpt(const gs_raster_plan &p) { return p.seg > 0 && raster_route_fwd(p.channels, &p) != RasterRoute::WAVE_GENERIC; }
+
+// The backward route: segmented only on top of what the forward of the SAME plan and scratch wrote (plan_has_ckpt) and the
+// final render, on the kernels of the forward's route; the generic kernel otherwise.  The wide kernel has no deterministic
+// mode, and absgrad is not linear in the image gradient: with it only what fits ONE launch goes the wide way.
+RasterRoute raster_route_bwd(uint32_t channels, const gs_raster_plan *plan, const void *scratch, const float *render_colors,
+                             const long long *det, bool absgrad) {
+    if (plan == nullptr || scratch == nullptr || !plan_has_ckpt(*plan) || render_colors == nullptr) return RasterRoute::WAVE_GENERIC;
+    const RasterRoute fwd = raster_route_fwd(channels, plan);
+    if (fwd == RasterRoute::TILE_WIDE && (det != nullptr || (absgrad && raster_wide_chunk(channels) < channels)))
+        return RasterRoute::WAVE_GENERIC;
+    return fwd;
+}
+
+// The scratch of plan `p` as typed pointers (scratch == NULL: all NULL; the sizes hold either way)
+RasterScratch scratch_view(const gs_raster_plan &p, void *scratch) {
+    const bool ckpt = plan_has_ckpt(p), tile = raster_route_fwd(p.channels, &p) != RasterRoute::WAVE_GENERIC;
+    size_t o = 256; // [0, 256): the class counters + padding; then the regions in this order, each padded to 256 bytes
+    auto take = [&](bool on, size_t bytes) -> void * {
+        void *r = (on && scratch != nullptr) ? (char *)scratch + o : nullptr;
+        if (on) o += (bytes + 255) & ~(size_t)255;
+        return r;
+    };
+    RasterScratch v;
+    v.seg = p.seg;
+    v.n_bounds = (ckpt ? p.n_isects / (uint32_t)p.seg : 0u) + 2u;
+    v.max_items = p.n_tiles_all + v.n_bounds;
+    v.class_count = (ckpt && scratch != nullptr) ? (uint32_t *)scratch : nullptr;
+    v.items = (uint2 *)take(ckpt, (size_t)COST_CLASSES * v.max_items * sizeof(uint2));
+    v.cost_head = (uint32_t *)take(true, (size_t)p.n_tiles_all * 4 * sizeof(uint32_t)); // (a region of every layout)
+    if (!ckpt) v.cost_head = nullptr;
+    v.cost_body = (uint32_t *)take(ckpt, (size_t)v.n_bounds * 4 * sizeof(uint32_t));
+    v.body_tile = (uint32_t *)take(ckpt, (size_t)v.n_bounds * sizeof(uint32_t));
+    v.ckpt = (float *)take(ckpt, (size_t)v.n_bounds * (p.channels + 1) * 256 * sizeof(float));
+    v.tile_order = (uint32_t *)take(tile, (size_t)p.n_tiles_all * sizeof(uint32_t)); // heaviest lists first (tile_order_kernel)
+    if (p.reserved[0] == 0u || p.n_tiles_all == 0u) v.tile_order = nullptr;
+    v.total = o;
+    return v;
+}
 
 } // namespace
 
@@ -1530,163 +1543,111 @@ int32_t raster_make_plan(uint32_t n_tiles_all, uint32_t n_isects, uint32_t chann
     plan->xcd_fwd = (uint32_t)xf;
     plan->xcd_bwd = (uint32_t)xb;
     plan->reserved[0] = (uint32_t)order; // forward: tiles with the longest lists first
-    plan->scratch_bytes = scratch_layout(*plan).total;
+    plan->scratch_bytes = scratch_view(*plan, nullptr).total;
     return 0;
 }
 
 bool raster_plan_ok(const gs_raster_plan *plan, uint32_t n_tiles_all, uint32_t n_isects, uint32_t channels) {
     return plan != nullptr && plan->magic == PLAN_MAGIC && plan->n_tiles_all == n_tiles_all && plan->n_isects == n_isects &&
            plan->channels == channels && plan->seg >= 0 && plan->seg % 64 == 0 &&
-           plan->scratch_bytes == scratch_layout(*plan).total;
+           plan->scratch_bytes == scratch_view(*plan, nullptr).total;
 }
 
-int32_t raster_wave_fwd(const RasterArgs &a_in, const gs_raster_plan *plan, void *scratch, void *zero_fill, size_t zero_fill_bytes,
-                        hipStream_t st) {
+// the plan a call runs under: the caller's, or (no plan means no scratch) the default launch geometry without checkpoints
+static gs_raster_plan plan_or_default(const RasterArgs &a, const gs_raster_plan *plan) {
+    gs_raster_plan p;
+    if (plan == nullptr) raster_make_plan(a.C * a.tile_width * a.tile_height, a.n_isects, a.channels, nullptr, &p);
+    return plan != nullptr ? *plan : p;
+}
+
+int32_t raster_dispatch_fwd(const RasterArgs &a_in, const gs_raster_plan *plan, void *scratch, void *zero_fill, size_t zero_fill_bytes,
+                            hipStream_t st) {
     RasterArgs a = a_in;
     const uint32_t n_tiles_all = a.C * a.tile_width * a.tile_height;
-    gs_raster_plan dflt; // no plan: default launch geometry, no checkpoints
-    if (plan == nullptr) {
-        raster_make_plan(n_tiles_all, a.n_isects, a.channels, nullptr, &dflt);
-        scratch = nullptr;
-    }
-    const gs_raster_plan &P = plan ? *plan : dflt;
-    const int32_t seg = P.seg;
-    const bool ckpt_on = a.channels <= FAST_MAX_CHANNELS && seg > 0 && scratch != nullptr;
+    const gs_raster_plan P = plan_or_default(a, plan);
+    const RasterRoute route = raster_route_fwd(a.channels, plan);
+    const RasterScratch v = scratch_view(P, scratch);
     // the side job: spread over the tile workgroups when each gets at most 256 KB of it, a plain fill otherwise
     ZeroFill zf = {nullptr, 0, 0u};
     if (zero_fill != nullptr && zero_fill_bytes > 0) {
         const size_t n16 = zero_fill_bytes / 16;
         const size_t per = (n16 + n_tiles_all - 1) / (n_tiles_all ? n_tiles_all : 1);
-        const bool in_kernel = ckpt_on && n_tiles_all > 0 && per <= 16384;
+        const bool in_kernel = v.ckpt != nullptr && n_tiles_all > 0 && per <= 16384;
         if (in_kernel) zf = {(float4 *)zero_fill, n16, (uint32_t)per};
         else if (hipMemsetAsync(zero_fill, 0, zero_fill_bytes, st) != hipSuccess) { gs_set_error("rasterize: zero fill failed"); return 1; }
     }
-    if (a.channels <= 4) {
-        // one 256-thread workgroup per tile; checkpoints for the segmented backward when the caller handed over scratch
-        const ScratchLayout L = scratch_layout(P);
-        float *ckpt = ckpt_on ? (float *)((char *)scratch + L.off_ckpt) : nullptr;
-        a.xcd_group = P.xcd_fwd;
-        a.tile_order = nullptr;
-        if (scratch != nullptr && P.reserved[0] != 0u && n_tiles_all > 0) {
-            uint32_t *order = (uint32_t *)((char *)scratch + L.off_order);
-            hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(ORDER_THREADS), 0, st, n_tiles_all, a.tile_offsets, a.n_isects, order);
-            a.tile_order = order;
+    if (route == RasterRoute::WAVE_GENERIC) {
+        // (no plan, or more than 32 channels) one quadrant per wave, exact chunks of 32 channels
+        a.xcd_group = P.xcd_fwd * 4u;
+        for (uint32_t off = 0; off < a.channels; off += 32) {
+            uint32_t cnt = min(32u, a.channels - off);
+            if (cnt <= 8) launch_fwd<8>(a, cnt, off, st);
+            else if (cnt <= 16) launch_fwd<16>(a, cnt, off, st);
+            else launch_fwd<32>(a, cnt, off, st);
         }
-        const int32_t solo = P.solo_min;
-        uint32_t *ch = ckpt ? (uint32_t *)((char *)scratch + L.off_cost_head) : nullptr;
-        uint32_t *cb = ckpt ? (uint32_t *)((char *)scratch + L.off_cost_body) : nullptr;
-        uint32_t *bt = ckpt ? (uint32_t *)((char *)scratch + L.off_body_tile) : nullptr;
-        uint32_t *cc = ckpt ? (uint32_t *)scratch : nullptr;
-        switch (a.channels) {
-            case 1: launch_tile_fwd<1>(a, ckpt, seg, solo, ch, cb, bt, cc, zf, st); break;
-            case 2: launch_tile_fwd<2>(a, ckpt, seg, solo, ch, cb, bt, cc, zf, st); break;
-            case 3: launch_tile_fwd<3>(a, ckpt, seg, solo, ch, cb, bt, cc, zf, st); break;
-            default: launch_tile_fwd<4>(a, ckpt, seg, solo, ch, cb, bt, cc, zf, st); break;
-        }
-        if (ckpt != nullptr) // the backward's work list, ordered by the costs just counted
-            hipLaunchKernelGGL(seg_items_build_kernel, dim3(gs_div_up(L.max_items, GS_BLOCK)), dim3(GS_BLOCK), 0, st, n_tiles_all, a.n_isects,
-                               a.tile_offsets, a.masks, seg, L.n_bounds, ch, cb, bt, cc, (uint2 *)((char *)scratch + L.off_items), L.max_items);
         return 0;
     }
-    if (a.channels <= FAST_MAX_CHANNELS && plan != nullptr) {
-        // 5..32 channels (round 5): the tile kernel with the colours in the LDS record; 17..32 as two launches over halves
-        const ScratchLayout L = scratch_layout(P);
-        float *ckpt = ckpt_on ? (float *)((char *)scratch + L.off_ckpt) : nullptr;
-        a.xcd_group = P.xcd_fwd;
-        a.tile_order = nullptr;
-        if (scratch != nullptr && P.reserved[0] != 0u && n_tiles_all > 0) {
-            uint32_t *order = (uint32_t *)((char *)scratch + L.off_order);
-            hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(ORDER_THREADS), 0, st, n_tiles_all, a.tile_offsets, a.n_isects, order);
-            a.tile_order = order;
+    // one 256-thread workgroup per tile, the colours in the LDS record (5..32 channels, round 5: the wide instances, 17..32 as
+    // two launches over halves); checkpoints for the segmented backward when the caller handed over scratch
+    a.xcd_group = P.xcd_fwd;
+    a.tile_order = v.tile_order;
+    if (v.tile_order != nullptr)
+        hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(ORDER_THREADS), 0, st, n_tiles_all, a.tile_offsets, a.n_isects, v.tile_order);
+    const uint32_t chunk = route == RasterRoute::TILE_NARROW ? a.channels : raster_wide_chunk(a.channels);
+    for (uint32_t off = 0; off < a.channels; off += chunk) {
+        const uint32_t cnt = min(chunk, a.channels - off);
+        const ZeroFill z = off == 0u ? zf : ZeroFill{nullptr, 0, 0u};
+        switch (route == RasterRoute::TILE_NARROW ? (int)cnt : raster_wide_instance(cnt)) {
+            case 1: launch_tile_fwd<1>(a, v, P.solo_min, z, st, off, cnt); break;
+            case 2: launch_tile_fwd<2>(a, v, P.solo_min, z, st, off, cnt); break;
+            case 3: launch_tile_fwd<3>(a, v, P.solo_min, z, st, off, cnt); break;
+            case 4: launch_tile_fwd<4>(a, v, P.solo_min, z, st, off, cnt); break;
+            case 8: launch_tile_fwd<8>(a, v, P.solo_min, z, st, off, cnt); break;
+            case 9: launch_tile_fwd<9>(a, v, P.solo_min, z, st, off, cnt); break;
+            case 12: launch_tile_fwd<12>(a, v, P.solo_min, z, st, off, cnt); break;
+            default: launch_tile_fwd<16>(a, v, P.solo_min, z, st, off, cnt); break;
         }
-        uint32_t *ch = ckpt ? (uint32_t *)((char *)scratch + L.off_cost_head) : nullptr;
-        uint32_t *cb = ckpt ? (uint32_t *)((char *)scratch + L.off_cost_body) : nullptr;
-        uint32_t *bt = ckpt ? (uint32_t *)((char *)scratch + L.off_body_tile) : nullptr;
-        uint32_t *cc = ckpt ? (uint32_t *)scratch : nullptr;
-        const uint32_t n_chunks = a.channels > 16u ? 2u : 1u, first = (a.channels + n_chunks - 1u) / n_chunks;
-        for (uint32_t off = 0; off < a.channels; off += first) {
-            const uint32_t cnt = min(first, a.channels - off);
-            const ZeroFill z = off == 0u ? zf : ZeroFill{nullptr, 0, 0u};
-            if (cnt <= 8u) launch_tile_fwd<8>(a, ckpt, seg, P.solo_min, ch, cb, bt, cc, z, st, off, cnt);
-            else if (cnt == 9u) launch_tile_fwd<9>(a, ckpt, seg, P.solo_min, ch, cb, bt, cc, z, st, off, cnt);
-            else if (cnt <= 12u) launch_tile_fwd<12>(a, ckpt, seg, P.solo_min, ch, cb, bt, cc, z, st, off, cnt);
-            else launch_tile_fwd<16>(a, ckpt, seg, P.solo_min, ch, cb, bt, cc, z, st, off, cnt);
-        }
-        if (ckpt != nullptr)
-            hipLaunchKernelGGL(seg_items_build_kernel, dim3(gs_div_up(L.max_items, GS_BLOCK)), dim3(GS_BLOCK), 0, st, n_tiles_all, a.n_isects,
-                               a.tile_offsets, a.masks, seg, L.n_bounds, ch, cb, bt, cc, (uint2 *)((char *)scratch + L.off_items), L.max_items);
-        return 0;
     }
-    // (no plan, or more than 32 channels) one quadrant per wave, exact chunks of 32 channels
-    a.xcd_group = P.xcd_fwd * 4u;
-    for (uint32_t off = 0; off < a.channels; off += 32) {
-        uint32_t cnt = min(32u, a.channels - off);
-        if (cnt <= 8) launch_fwd<8>(a, cnt, off, st);
-        else if (cnt <= 16) launch_fwd<16>(a, cnt, off, st);
-        else launch_fwd<32>(a, cnt, off, st);
-    }
+    if (v.ckpt != nullptr) // the backward's work list, ordered by the costs just counted
+        hipLaunchKernelGGL(seg_items_build_kernel, dim3(gs_div_up(v.max_items, GS_BLOCK)), dim3(GS_BLOCK), 0, st, n_tiles_all, a.n_isects,
+                           a.tile_offsets, a.masks, v.seg, v.n_bounds, v.cost_head, v.cost_body, v.body_tile, v.class_count, v.items, v.max_items);
     return 0;
 }
 
-int32_t raster_wave_bwd(const RasterArgs &a_in, const RasterGradArgs &ga, const float *render_colors, const gs_raster_plan *plan,
-                        void *scratch, hipStream_t st) {
+int32_t raster_dispatch_bwd(const RasterArgs &a_in, const RasterGradArgs &ga, const float *render_colors, const gs_raster_plan *plan,
+                            void *scratch, hipStream_t st) {
     RasterArgs a = a_in;
-    const uint32_t n_tiles_all = a.C * a.tile_width * a.tile_height;
-    gs_raster_plan dflt;
-    if (plan == nullptr) {
-        raster_make_plan(n_tiles_all, a.n_isects, a.channels, nullptr, &dflt);
-        scratch = nullptr;
-    }
-    const gs_raster_plan &P = plan ? *plan : dflt;
-    a.xcd_group = P.xcd_bwd;
+    const gs_raster_plan P = plan_or_default(a, plan);
     const int use_va = ga.v_render_alphas != nullptr;
     const uint32_t c = a.channels;
-    const int32_t seg = P.seg;
-    // Depth-segmented backward: needs the forward's checkpoints (same plan, same scratch) and the render.
-    if (seg > 0 && c <= 4 && scratch != nullptr && render_colors != nullptr) {
-        const ScratchLayout L = scratch_layout(P);
-        // the work list was built by gs_rasterize_fwd (seg_items_build_kernel): ONE launch here
-        SegArgs sg = {(const uint2 *)((char *)scratch + L.off_items), (const uint32_t *)scratch, L.max_items,
-                      (const float *)((char *)scratch + L.off_ckpt), render_colors, seg};
-        switch (c) {
-            case 1: launch_bwd_seg<1>(a, ga, L.max_items, use_va, sg, st); break;
-            case 2: launch_bwd_seg<2>(a, ga, L.max_items, use_va, sg, st); break;
-            case 3: launch_bwd_seg<3>(a, ga, L.max_items, use_va, sg, st); break;
-            default: launch_bwd_seg<4>(a, ga, L.max_items, use_va, sg, st); break;
-        }
-        if (ga.det != nullptr)
-            hipLaunchKernelGGL(raster_det_finalize_kernel, dim3(gs_div_up(a.n_elems, GS_BLOCK)), dim3(GS_BLOCK), 0, st, a.n_elems, c, ga.det, ga);
-        return 0;
-    }
-    // 5..32 channels: the wide segmented kernel (rasterize_wide.hip); absgrad is not linear in the image gradient, so with it
-    // only what fits ONE launch (<= 16 channels) goes this way
-    if (seg > 0 && c > 4 && c <= FAST_MAX_CHANNELS && scratch != nullptr && render_colors != nullptr && ga.det == nullptr &&
-        (c <= 16 || ga.v_means2d_abs == nullptr)) {
-        const ScratchLayout L = scratch_layout(P);
-        const uint32_t n_chunks = c > 16u ? 2u : 1u, first = (c + n_chunks - 1u) / n_chunks;
-        for (uint32_t off = 0; off < c; off += first)
-            raster_seg_bwd_wide(a, ga, L.max_items, (use_va && off == 0u) ? 1 : 0, (const char *)scratch + L.off_items, (const uint32_t *)scratch,
-                                (const float *)((char *)scratch + L.off_ckpt), render_colors, seg, off, min(first, c - off), st);
-        return 0;
-    }
-    // no checkpoints (forward ran without scratch, or segments are switched off) or more than 32 channels:
-    // one quadrant per wave walking the whole list back to front
-    a.xcd_group = P.xcd_bwd * 4u;
-    if (c <= 4) {
-        switch (c) {
-            case 1: launch_bwd<1, 0>(a, ga, 1, 0, use_va, st); break;
-            case 2: launch_bwd<2, 0>(a, ga, 2, 0, use_va, st); break;
-            case 3: launch_bwd<3, 0>(a, ga, 3, 0, use_va, st); break;
-            default: launch_bwd<4, 0>(a, ga, 4, 0, use_va, st); break;
-        }
-    } else if (c <= 8) {
-        launch_bwd<8, 1>(a, ga, c, 0, use_va, st);
-    } else if (c <= 16) {
-        launch_bwd<16, 1>(a, ga, c, 0, use_va, st);
-    } else if (c <= 32) {
-        launch_bwd<32, 1>(a, ga, c, 0, use_va, st);
+    const RasterRoute route = raster_route_bwd(c, plan, scratch, render_colors, ga.det, ga.v_means2d_abs != nullptr);
+    if (route == RasterRoute::WAVE_GENERIC) {
+        // no checkpoints (forward ran without scratch, or segments are switched off) or more than 32 channels:
+        // one quadrant per wave walking the whole list back to front
+        a.xcd_group = P.xcd_bwd * 4u;
+        if (c == 1) launch_bwd<1, 0>(a, ga, 1, 0, use_va, st);
+        else if (c == 2) launch_bwd<2, 0>(a, ga, 2, 0, use_va, st);
+        else if (c == 3) launch_bwd<3, 0>(a, ga, 3, 0, use_va, st);
+        else if (c == 4) launch_bwd<4, 0>(a, ga, 4, 0, use_va, st);
+        else if (c <= 8) launch_bwd<8, 1>(a, ga, c, 0, use_va, st);
+        else if (c <= 16) launch_bwd<16, 1>(a, ga, c, 0, use_va, st);
+        else if (c <= 32) launch_bwd<32, 1>(a, ga, c, 0, use_va, st);
+        else launch_bwd<1, 2>(a, ga, c, 0, use_va, st);
     } else {
-        launch_bwd<1, 2>(a, ga, c, 0, use_va, st);
+        // depth-segmented, ONE launch per chunk: the work list was built by gs_rasterize_fwd (seg_items_build_kernel)
+        const RasterScratch v = scratch_view(P, scratch);
+        a.xcd_group = P.xcd_bwd;
+        if (route == RasterRoute::TILE_WIDE) {
+            raster_seg_bwd_wide(a, ga, use_va, v, render_colors, st);
+        } else {
+            const SegArgs sg = seg_args(v, render_colors);
+            switch (c) {
+                case 1: launch_bwd_seg<1>(a, ga, use_va, sg, st); break;
+                case 2: launch_bwd_seg<2>(a, ga, use_va, sg, st); break;
+                case 3: launch_bwd_seg<3>(a, ga, use_va, sg, st); break;
+                default: launch_bwd_seg<4>(a, ga, use_va, sg, st); break;
+            }
+        }
     }
     if (ga.det != nullptr)
         hipLaunchKernelGGL(raster_det_finalize_kernel, dim3(gs_div_up(a.n_elems, GS_BLOCK)), dim3(GS_BLOCK), 0, st, a.n_elems, c, ga.det, ga);

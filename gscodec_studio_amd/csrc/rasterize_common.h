@@ -93,13 +93,36 @@ GS_DEV float wave_reduce_sum_dpp(float v) {
     return v;
 }
 
+// Host side (rasterize.hip; the wide backward's launcher in rasterize_wide.hip).  The kernels a call runs on: the tile forward /
+// depth-segmented backward of 1..4 channels, their wide instances (5..32 channels), or the generic one-quadrant-per-wave
+// kernels.  Decided by raster_route_fwd / raster_route_bwd only.
+enum class RasterRoute { TILE_NARROW, TILE_WIDE, WAVE_GENERIC };
+
+// A call's scratch buffer as typed pointers, built once per call from (plan, scratch): scratch_view.  A region the call has
+// no use for (no scratch, no segments, more channels than the tile kernels cover) is NULL.
+struct RasterScratch {
+    uint32_t *class_count;                      // [COST_CLASSES] work items per cost class
+    uint2 *items;                               // [COST_CLASSES][max_items] (tile, k), the segmented backward's work list
+    uint32_t *cost_head, *cost_body, *body_tile; // [tile][4], [boundary][4] costs counted by the forward; [boundary] owner tile
+    float *ckpt;                                // [boundary][channels + 1][256] forward checkpoints
+    uint32_t *tile_order;                       // [tile] the forward's tile order (NULL: unordered)
+    uint32_t max_items, n_bounds;               // length of an item region; list boundaries k * seg, k < n_bounds
+    int32_t seg;                                // segment length in list entries (the plan's)
+    size_t total;                               // bytes of the whole layout
+};
+
+// Channel rules of the wide instances, for the forward and the backward launcher alike: up to 16 channels are one launch,
+// 17..32 two launches over halves (the channels per launch);
+inline uint32_t raster_wide_chunk(uint32_t channels) { return channels <= 16u ? channels : (channels + 1u) / 2u; }
+// the smallest instance (8, 9, 12 or 16) that holds a launch of cnt channels
+inline int raster_wide_instance(uint32_t cnt) { return cnt <= 8u ? 8 : cnt == 9u ? 9 : cnt <= 12u ? 12 : 16; }
+
 int32_t raster_make_plan(uint32_t n_tiles_all, uint32_t n_isects, uint32_t channels, const int32_t *tuning, gs_raster_plan *plan);
 bool raster_plan_ok(const gs_raster_plan *plan, uint32_t n_tiles_all, uint32_t n_isects, uint32_t channels);
-int32_t raster_wave_fwd(const RasterArgs &a, const gs_raster_plan *plan, void *scratch, void *zero_fill, size_t zero_fill_bytes,
-                        hipStream_t st);
-int32_t raster_wave_bwd(const RasterArgs &a, const RasterGradArgs &ga, const float *render_colors, const gs_raster_plan *plan,
-                        void *scratch, hipStream_t st);
-// rasterize_wide.hip: one launch of the segmented backward over channels [ch_off, ch_off + cnt), 5 <= cnt <= 16
-void raster_seg_bwd_wide(const RasterArgs &a, const RasterGradArgs &ga, uint32_t max_items, int use_va, const void *items,
-                         const uint32_t *class_count, const float *ckpt, const float *render_colors, int32_t seg, uint32_t ch_off,
-                         uint32_t cnt, hipStream_t st);
+int32_t raster_dispatch_fwd(const RasterArgs &a, const gs_raster_plan *plan, void *scratch, void *zero_fill, size_t zero_fill_bytes,
+                            hipStream_t st);
+int32_t raster_dispatch_bwd(const RasterArgs &a, const RasterGradArgs &ga, const float *render_colors, const gs_raster_plan *plan,
+                            void *scratch, hipStream_t st);
+// rasterize_wide.hip: the segmented backward of 5..32 channels (one launch per raster_wide_chunk) from the forward's scratch
+void raster_seg_bwd_wide(const RasterArgs &a, const RasterGradArgs &ga, int use_va, const RasterScratch &v, const float *render_colors,
+                         hipStream_t st);

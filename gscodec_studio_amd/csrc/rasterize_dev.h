@@ -235,4 +235,7 @@ struct SegArgs {
     int32_t seg;
 };
 
+// (host) what both segmented backwards read of the forward's scratch
+inline SegArgs seg_args(const RasterScratch &v, const float *render_colors) { return {v.items, v.class_count, v.max_items, v.ckpt, render_colors, v.seg}; }
+
 } // namespace

@@ -17,7 +17,8 @@
 //     slot, component) atomics (one request per splat and line);
 //   * a launch covers channels [ch_off, ch_off + cnt): every gradient is LINEAR in the image gradient, so two launches over
 //     the two halves of 17..32 channels add up exactly (v_render_alphas rides with the first).  absgrad is not linear: with it
-//     more than 16 channels stay on the generic one-pass kernel.
+//     more than 16 channels stay on the generic one-pass kernel (raster_route_bwd in rasterize.hip).  The launcher at the end,
+//     raster_seg_bwd_wide, is called by raster_dispatch_bwd and shares raster_wide_chunk / raster_wide_instance with the forward.
 #include "gs_common.h"
 #include "rasterize_common.h"
 #include "dpp_reduce.h"
@@ -329,24 +330,29 @@ __global__ void __launch_bounds__(GS_WAVE, (GS_WIDE_BWD_WAVES > 0 && CDIM <= 9) 
 }
 
 template <int CDIM>
-void launch(const RasterArgs &a, const RasterGradArgs &ga, uint32_t max_items, int use_va, const SegArgs &sg, uint32_t ch_off, uint32_t cnt,
-            hipStream_t st) {
+void launch(const RasterArgs &a, const RasterGradArgs &ga, int use_va, const SegArgs &sg, uint32_t ch_off, uint32_t cnt, hipStream_t st) {
     if (ga.v_means2d_abs != nullptr)
-        hipLaunchKernelGGL((raster_seg_bwd_wide_kernel<CDIM, true>), dim3(max_items), dim3(GS_WAVE), 0, st, a, ga, use_va, sg, ch_off, cnt);
+        hipLaunchKernelGGL((raster_seg_bwd_wide_kernel<CDIM, true>), dim3(sg.max_items), dim3(GS_WAVE), 0, st, a, ga, use_va, sg, ch_off, cnt);
     else
-        hipLaunchKernelGGL((raster_seg_bwd_wide_kernel<CDIM, false>), dim3(max_items), dim3(GS_WAVE), 0, st, a, ga, use_va, sg, ch_off, cnt);
+        hipLaunchKernelGGL((raster_seg_bwd_wide_kernel<CDIM, false>), dim3(sg.max_items), dim3(GS_WAVE), 0, st, a, ga, use_va, sg, ch_off, cnt);
 }
 
 } // namespace
 
-// One launch of the segmented backward over channels [ch_off, ch_off + cnt), 5 <= cnt <= 16 (instances 8, 9, 12, 16: the
-// smallest one that holds cnt).  `use_va`: v_render_alphas takes part (the first launch of a chunked backward only).
-void raster_seg_bwd_wide(const RasterArgs &a, const RasterGradArgs &ga, uint32_t max_items, int use_va, const void *items,
-                         const uint32_t *class_count, const float *ckpt, const float *render_colors, int32_t seg, uint32_t ch_off,
-                         uint32_t cnt, hipStream_t st) {
-    const SegArgs sg = {(const uint2 *)items, class_count, max_items, ckpt, render_colors, seg};
-    if (cnt <= 8) launch<8>(a, ga, max_items, use_va, sg, ch_off, cnt, st);
-    else if (cnt == 9) launch<9>(a, ga, max_items, use_va, sg, ch_off, cnt, st);
-    else if (cnt <= 12) launch<12>(a, ga, max_items, use_va, sg, ch_off, cnt, st);
-    else launch<16>(a, ga, max_items, use_va, sg, ch_off, cnt, st);
+// The segmented backward of 5..32 channels from the forward's scratch (raster_dispatch_bwd, route TILE_WIDE): one launch per
+// raster_wide_chunk of the channels, each on the instance that holds it (raster_wide_instance).  `use_va`: v_render_alphas
+// takes part (it rides with the first launch only).
+void raster_seg_bwd_wide(const RasterArgs &a, const RasterGradArgs &ga, int use_va, const RasterScratch &v, const float *render_colors,
+                         hipStream_t st) {
+    const SegArgs sg = seg_args(v, render_colors);
+    const uint32_t chunk = raster_wide_chunk(a.channels);
+    for (uint32_t off = 0; off < a.channels; off += chunk, use_va = 0) {
+        const uint32_t cnt = min(chunk, a.channels - off);
+        switch (raster_wide_instance(cnt)) {
+            case 8: launch<8>(a, ga, use_va, sg, off, cnt, st); break;
+            case 9: launch<9>(a, ga, use_va, sg, off, cnt, st); break;
+            case 12: launch<12>(a, ga, use_va, sg, off, cnt, st); break;
+            default: launch<16>(a, ga, use_va, sg, off, cnt, st); break;
+        }
+    }
 }

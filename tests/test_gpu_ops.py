@@ -466,6 +466,68 @@ def test_wide_backward_gradient_layouts_through_the_c_abi(ops, channels, absgrad
         assert rel_l2(N(z_), N(x)) < 2e-4, (name, "generic vs segmented", rel_l2(N(z_), N(x)))
 
 
+def test_narrow_backward_gradient_layouts_through_the_c_abi(ops):
+    """The 3-channel sibling of the wide test above, absgrad on: gs_rasterize_bwd with the forward's plan + scratch (the segmented
+    kernel) writing into the packed rows (`packed16 = 1`: what rasterize_to_pixels uses) and into the reference's separate arrays
+    (`packed16 = 0`), and, without plan and scratch, the generic wave kernel.  All five gradients must agree, within the wide
+    test's bounds.  The forward without plan and scratch is the same kernel instance family and the same arithmetic as the planned
+    one (no checkpoints, no tile order): the same image bit for bit."""
+    import ctypes
+
+    from gscodec_studio_amd import _backend as B
+    from gscodec_studio_amd import _wrapper as W
+
+    channels = 3
+    c = _raster_case(n=2500, channels=channels, opac_boost=True)
+    C, H, Wd = c["C"], c["H"], c["W"]
+    dev = torch.device("cuda")
+    m2, cn, col, op = T(c["means2d"]), T(c["conics"]), T(c["colors"]), T(c["opacities"])
+    offs, flat = T(c["offs"]), T(c["flat"])
+    th, tw = c["offs"].shape[1:]
+    n_elems, n_isects = op.numel(), flat.shape[0]
+    rs = np.random.RandomState(channels)
+    v_rc, v_ra = T(rs.randn(C, H, Wd, channels).astype(np.float32)), T(rs.randn(C, H, Wd, 1).astype(np.float32))
+    st = torch.cuda.current_stream().cuda_stream
+    plan, sb = W._raster_plan(C * th * tw, n_isects, channels)
+    scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
+
+    def fwd(use_plan):
+        rc = torch.empty((C, H, Wd, channels), device=dev)
+        ra = torch.empty((C, H, Wd, 1), device=dev)
+        li = torch.empty((C, H, Wd), dtype=torch.int32, device=dev)
+        B.call("gs_rasterize_fwd", C, n_elems, n_isects, channels, B.ptr(m2), B.ptr(cn), B.ptr(col), B.ptr(op), None, None, None, Wd, H, 16, tw,
+               th, B.ptr(offs), B.ptr(flat), B.ptr(rc), B.ptr(ra), B.ptr(li), ctypes.addressof(plan) if use_plan else None,
+               B.ptr(scratch) if use_plan else None, None, 0, st)
+        return rc, ra, li
+
+    rc, ra, li = fwd(True)
+    for name, x, y in zip(("render_colors", "render_alphas", "last_ids"), (rc, ra, li), fwd(False)):
+        assert torch.equal(x, y), (name, "forward without plan vs with plan")
+
+    def bwd(packed16, use_plan):
+        z = lambda *shape: torch.zeros(shape, device=dev)  # noqa: E731
+        if packed16 == 1:
+            P = z(C, c["means2d"].shape[1], 16)
+            ptrs = (B.ptr(P), B.ptr(P), None, None, None)
+        else:
+            vm, vc_, vcol, vo, va = z(*m2.shape), z(*cn.shape), z(*col.shape), z(*op.shape), z(*m2.shape)
+            ptrs = (B.ptr(va), B.ptr(vm), B.ptr(vc_), B.ptr(vcol), B.ptr(vo))
+        B.call("gs_rasterize_bwd", C, n_elems, n_isects, channels, B.ptr(m2), B.ptr(cn), B.ptr(col), B.ptr(op), None, None, None, Wd, H, 16, tw,
+               th, B.ptr(offs), B.ptr(flat), B.ptr(rc), B.ptr(ra), B.ptr(li), B.ptr(v_rc), B.ptr(v_ra), channels, 1, *ptrs, packed16, None,
+               ctypes.addressof(plan) if use_plan else None, B.ptr(scratch) if use_plan else None, st)
+        if packed16 == 1:
+            return P[..., 0:2], P[..., 2:5], P[..., 6:6 + channels], P[..., 5], P[..., 10:12]
+        return vm, vc_, vcol, vo, va
+
+    a, b, g = bwd(1, True), bwd(0, True), bwd(0, False)
+    errs = [(name, rel_l2(N(y), N(x)), rel_l2(N(z_), N(x)))
+            for name, x, y, z_ in zip(("v_means2d", "v_conics", "v_colors", "v_opacities", "absgrad"), a, b, g)]
+    print("narrow layouts (separate arrays vs rows, generic vs segmented):", errs)
+    for name, e_layout, e_generic in errs:
+        assert e_layout < 2e-5, (name, "separate arrays vs rows", e_layout)
+        assert e_generic < 2e-4, (name, "generic vs segmented", e_generic)
+
+
 def test_rasterize_masks_tilesize_and_last_ids(ops):
     c = _raster_case(n=2000, cams=1, channels=3)
     th, tw = c["offs"].shape[1:]
