@@ -70,6 +70,13 @@ def _mlp(h0, mats, biases, factors, p):
     return h[:, 0], hs, ts
 
 
+def _sum_by_set(v, p, C):
+    """[E, ...] -> [C, ...]: the sum of v over the elements of each parameter set, accumulated in double."""
+    flat = v.reshape(v.shape[0], -1)
+    out = np.stack([np.bincount(p, weights=flat[:, k], minlength=C) for k in range(flat.shape[1])], axis=1)
+    return out.reshape((C,) + v.shape[1:]).astype(v.dtype)
+
+
 def _mlp_bwd(g_out, mats, biases, factors, p, hs, ts, g_mats, g_biases, g_factors):
     """Accumulates parameter gradients (w.r.t. the RAW parameters) and returns d/d h0 [E]."""
     L = len(factors)
@@ -82,33 +89,34 @@ def _mlp_bwd(g_out, mats, biases, factors, p, hs, ts, g_mats, g_biases, g_factor
             gf_t = g * t                                   # grad wrt tanh(F)
             gz = g * (1.0 + f * (1.0 - t * t))
             d_raw = gf_t * (1.0 - f * f)                   # through tanh(F)
-            for c in range(C):
-                g_factors[i][c, :, 0] += d_raw[p == c].sum(0)
+            g_factors[i][:, :, 0] += _sum_by_set(d_raw, p, C)
         else:
             gz = g
         A_raw = mats[i]
         A = _softplus(A_raw)[p]
         gA = gz[:, :, None] * hs[i][:, None, :]            # [E, wo, wi] grad wrt softplus(M)
         gA_raw = gA * _sigmoid(A_raw)[p]
-        for c in range(C):
-            sel = p == c
-            g_mats[i][c] += gA_raw[sel].sum(0)
-            g_biases[i][c, :, 0] += gz[sel].sum(0)
+        g_mats[i] += _sum_by_set(gA_raw, p, C)
+        g_biases[i][:, :, 0] += _sum_by_set(gz, p, C)
         g = np.einsum("eoi,eo->ei", A, gz)
     return g[:, 0]
 
 
-def factorized_bits_fwd(x, q, mats, biases, factors, bound=1e-6, dtype=np.float64, return_tape=False):
-    """x [N, C]; q scalar or [C]; returns bits [N, C]."""
+def factorized_bits_fwd(x, q, mats, biases, factors, bound=1e-6, dtype=np.float64, return_tape=False, rows=None, n_total=None):
+    """x [N, C]; q scalar or [C]; returns bits [N, C].  With ``rows`` (ascending row indices) x holds only those rows of
+    an [n_total, C] input: the parameter set of an element depends on its row index and on n_total."""
     x = np.asarray(x, dtype=dtype)
     N, C = x.shape
+    row_of = np.arange(N) if rows is None else np.asarray(rows, dtype=np.int64)
+    n_total = N if rows is None else int(n_total)
+    assert row_of.shape == (N,) and (N == 0 or (row_of.min() >= 0 and row_of.max() < n_total))
     mats = [np.asarray(m, dtype=dtype) for m in mats]
     biases = [np.asarray(b, dtype=dtype) for b in biases]
     factors = [np.asarray(f, dtype=dtype) for f in factors]
     qv = np.broadcast_to(np.asarray(q, dtype=dtype).reshape(-1), (C,)) if np.ndim(q) else np.full((C,), q, dtype=dtype)
-    n_idx, c_idx = np.meshgrid(np.arange(N), np.arange(C), indexing="ij")
+    n_idx, c_idx = np.meshgrid(row_of, np.arange(C), indexing="ij")
     n_idx, c_idx = n_idx.reshape(-1), c_idx.reshape(-1)
-    p = param_channel(n_idx, c_idx, N, C)
+    p = param_channel(n_idx, c_idx, n_total, C)
     xe = x.reshape(-1)
     half = (dtype(0.5) * qv)[c_idx]
     lower, hs_l, ts_l = _mlp(xe - half, mats, biases, factors, p)
@@ -124,9 +132,12 @@ def factorized_bits_fwd(x, q, mats, biases, factors, bound=1e-6, dtype=np.float6
     return bits
 
 
-def factorized_bits_bwd(x, q, mats, biases, factors, v_bits, bound=1e-6, dtype=np.float64):
-    """Returns (v_x [N, C], [v_mats], [v_biases], [v_factors]) for the upstream gradient v_bits [N, C]."""
-    bits, tp = factorized_bits_fwd(x, q, mats, biases, factors, bound, dtype, return_tape=True)
+def factorized_bits_bwd(x, q, mats, biases, factors, v_bits, bound=1e-6, dtype=np.float64, rows=None, n_total=None,
+                        return_fwd=False):
+    """Returns (v_x [N, C], [v_mats], [v_biases], [v_factors]) for the upstream gradient v_bits [N, C]; with
+    ``return_fwd`` also bits [N, C] and the likelihood BEFORE the lower bound [N, C] (an element is clamped where it is
+    below ``bound``).  ``rows`` / ``n_total`` as in factorized_bits_fwd."""
+    bits, tp = factorized_bits_fwd(x, q, mats, biases, factors, bound, dtype, return_tape=True, rows=rows, n_total=n_total)
     N, C = bits.shape
     vb = np.asarray(v_bits, dtype=dtype).reshape(-1)
     g_lik_b = -vb / (np.log(dtype(2.0)) * tp["lik_b"])
@@ -140,4 +151,6 @@ def factorized_bits_bwd(x, q, mats, biases, factors, v_bits, bound=1e-6, dtype=n
     g_factors = [np.zeros_like(f) for f in tp["factors"]]
     gx = _mlp_bwd(g_lower, tp["mats"], tp["biases"], tp["factors"], tp["p"], tp["hs_l"], tp["ts_l"], g_mats, g_biases, g_factors)
     gx = gx + _mlp_bwd(g_upper, tp["mats"], tp["biases"], tp["factors"], tp["p"], tp["hs_u"], tp["ts_u"], g_mats, g_biases, g_factors)
+    if return_fwd:
+        return gx.reshape(N, C), g_mats, g_biases, g_factors, bits, tp["lik"].reshape(N, C)
     return gx.reshape(N, C), g_mats, g_biases, g_factors
