@@ -88,13 +88,6 @@ class _Handover:
     __slots__ = ("render_colors", "render_alphas", "last_ids", "scratch", "plan", "grad_rows", "offsets", "flatten_ids")
 
 
-def applicable(means: Tensor, viewmats: Tensor, colors, sh_degree, packed: bool, distributed: bool, render_mode: str,
-               channel_chunk: int, deterministic: bool, fuse_sh: bool, row_colors) -> bool:
-    return (ENABLED and not packed and not distributed and not deterministic and render_mode == "RGB" and channel_chunk >= 3
-            and means.is_cuda and viewmats.is_cuda and not viewmats.requires_grad and means.shape[0] > 0 and viewmats.shape[0] > 0
-            and (fuse_sh or row_colors is not None))
-
-
 def _c(t: Optional[Tensor]) -> Optional[Tensor]:
     if t is None:
         return None
@@ -343,18 +336,9 @@ class _RowsState:
             pass
 
 
-def rows_applicable(rows: Optional[Tensor], colors: Optional[Tensor], packed: bool, render_mode: str, channel_chunk: int,
-                    deterministic: bool, absgrad: bool) -> bool:
-    """The gaussian-sharded mode's receiver side: [C_local, N_total, 16] splat rows with RGB colours in them."""
-    return (ENABLED and rows is not None and rows.is_cuda and not packed and not deterministic and render_mode == "RGB"
-            and channel_chunk >= 3 and colors is not None and colors.shape[-1] == 3
-            # (the block sums go straight into pinned memory: same size gate as the one-GPU fast path / isect_tiles_begin --
-            # tens of thousands of direct PCIe stores stalled the GPU for ~85 ms on some forwards)
-            and 0 < rows.shape[0] * rows.shape[1] <= W._PINNED_DIRECT_MAX * 1024)
-
-
 def rows_begin(radii: Tensor, depths: Tensor, rows: Tensor, tile_size: int, tile_width: int, tile_height: int) -> _RowsState:
-    """Queue the binning of ``rows`` up to its host read-back (``gs_step_fwd_begin`` with ``rows_ready``): count + depth keys
+    """The gaussian-sharded mode's receiver side ([C_local, N_total, 16] splat rows with RGB colours in them; when to: _route.route):
+    queue the binning of ``rows`` up to its host read-back (``gs_step_fwd_begin`` with ``rows_ready``): count + depth keys
     -> depth pre-sort.  Nothing differentiable happens here (the reference's ``isect_tiles`` is not differentiable either)."""
     C, N = radii.shape
     dev = rows.device
@@ -447,10 +431,7 @@ def rasterize_step(means, covars, quats, scales, opacities, viewmats, Ks, width,
         *(dyn_in + (dynamic,) if dynamic is not None else ()))
     render_colors, render_alphas = _StepComposite.apply(means2d, conics, colors_cn, opac_cn, backgrounds,
                                                         (int(width), int(height), int(tile_size), bool(absgrad)), hand)
-    meta = {
-        "camera_ids": None, "gaussian_ids": None, "radii": radii, "means2d": means2d, "depths": depths, "conics": conics,
-        "opacities": opac_cn, "tile_width": tile_width, "tile_height": tile_height, "tiles_per_gauss": tiles_per_gauss,
-        "isect_ids": isect_ids, "flatten_ids": flatten_ids, "isect_offsets": offsets, "width": width, "height": height,
-        "tile_size": tile_size, "n_cameras": C,
-    }
+    meta = {"camera_ids": None, "gaussian_ids": None, "radii": radii, "means2d": means2d, "depths": depths, "conics": conics,
+            "opacities": opac_cn}
+    meta.update(W.binning_meta(tile_size, tile_width, tile_height, tiles_per_gauss, isect_ids, flatten_ids, offsets, width, height, C))
     return render_colors, render_alphas, meta

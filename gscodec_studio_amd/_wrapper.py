@@ -852,6 +852,12 @@ class _FullyFusedProjection(torch.autograd.Function):
 _FUSE_SH_BWD = os.environ.get("GS_FUSE_SH_BWD", "1") == "1"  # (A/B switch: 0 = gs_sh_view_bwd + gs_projection_rows_bwd as two launches)
 
 
+def sh_bwd_fusable(K: int, sh_coeffs: Tensor, sh_rest: Optional[Tensor], pose_grads: bool) -> bool:
+    """Can the SH backward run inside the projection backward's own pass (gs_projection_rows_bwd): vectorisable coefficient rows
+    (3 K % 4 == 0, 16-byte aligned unless split) and fixed poses.  Asked by the forward too, before it fuses a shN mask."""
+    return _FUSE_SH_BWD and (3 * K) % 4 == 0 and not pose_grads and (sh_rest is not None or sh_coeffs.data_ptr() % 16 == 0)
+
+
 # GS_GRAD_PREFILL=0: the per-gaussian gradients are allocated by the projection backward itself instead of behind the
 # compositing gradient rows (they then do not keep the C * N * 64-byte row buffer alive while they are held as .grad, and a
 # forward under grad mode that never runs backward does not zero-fill ~236 B per gaussian for nothing; ~3 % slower per step)
@@ -1120,8 +1126,8 @@ def _project_rows_bwd(ctx, need, v_means2d, v_depths, v_conics, v_opac_cn, v_col
         K = sh_coeffs.shape[1] + (sh_rest.shape[1] if sh_rest is not None else 0)
         v_sh = out("sh", sh_coeffs)
         v_rest = out("sh_rest", sh_rest) if sh_rest is not None else None
-        fused = (_FUSE_SH_BWD and (3 * K) % 4 == 0 and not need["viewmats"] and v_sh.data_ptr() % 16 == 0
-                 and (v_rest is None or v_rest.data_ptr() % 16 == 0) and (sh_rest is not None or sh_coeffs.data_ptr() % 16 == 0))
+        fused = (sh_bwd_fusable(K, sh_coeffs, sh_rest, need["viewmats"]) and v_sh.data_ptr() % 16 == 0
+                 and (v_rest is None or v_rest.data_ptr() % 16 == 0))
         if mask is not None:
             if not fused:
                 raise RuntimeError("project_rows: the fused shN mask needs the fused SH backward (3 K % 4 == 0, aligned rows, fixed poses)")
@@ -1328,6 +1334,13 @@ def isect_tiles(
     """
     return isect_tiles_finish(isect_tiles_start(means2d, radii, depths, tile_size, tile_width, tile_height, sort, packed,
                                                 n_cameras, camera_ids, gaussian_ids))
+
+
+def binning_meta(tile_size, tile_width, tile_height, tiles_per_gauss, isect_ids, flatten_ids, isect_offsets, width, height, n_cameras) -> dict:
+    """The tile-binning entries of ``rasterization()``'s ``meta`` (reference rendering.py:440-452)."""
+    return {"tile_width": tile_width, "tile_height": tile_height, "tiles_per_gauss": tiles_per_gauss, "isect_ids": isect_ids,
+            "flatten_ids": flatten_ids, "isect_offsets": isect_offsets, "width": width, "height": height, "tile_size": tile_size,
+            "n_cameras": n_cameras}
 
 
 def isect_tiles_start(means2d, radii, depths, tile_size, tile_width, tile_height, sort=True, packed=False, n_cameras=None,
@@ -1752,7 +1765,7 @@ def _split_big_tiles(isect_offsets: Tensor, flatten_ids: Tensor, masks: Optional
     n = int(flatten_ids.shape[0])
     total = 4 * n
     if total >= 2 ** 31:
-        raise RuntimeError(f"tile_size > 16: {n} intersections x 4 sub-tile copies overflow the int32 tile offsets; use tile_size <= 16")
+        raise RuntimeError(f"tile_size > 16: {n} intersections x 4 sub-tile copies overflow the int32 tile offsets; use tiles of at most 16 pixels")
     dev = flatten_ids.device
     i32 = torch.int32
     start = isect_offsets.reshape(-1).to(i32)

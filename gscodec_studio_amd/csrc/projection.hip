@@ -593,7 +593,7 @@ extern "C" int32_t gs_projection_rows_bwd(
         GS_CHECK_ARG((sh_coeffs_rest == nullptr) == (v_sh_coeffs_rest == nullptr), "sh_coeffs_rest and v_sh_coeffs_rest go together");
         GS_CHECK_ARG((sh_K * 3u) % 4u == 0 && (uintptr_t)v_sh_coeffs % 16 == 0 && (uintptr_t)v_sh_coeffs_rest % 16 == 0 &&
                          (sh_coeffs_rest != nullptr ? sh_K >= 2 : (uintptr_t)sh_coeffs % 16 == 0),
-                     "fused SH backward needs 3 K % 4 == 0 and 16-byte aligned rows (gs_projection_rows_bwd_sh_ok); call gs_sh_view_bwd instead");
+                     "fused SH backward needs 3 K % 4 == 0 and 16-byte aligned rows; call gs_sh_view_bwd instead");
         rg.sh_coeffs = sh_coeffs; rg.sh_rest = sh_coeffs_rest; rg.sh_K = sh_K; rg.v_sh = v_sh_coeffs; rg.v_sh_rest = v_sh_coeffs_rest;
         rg.sh_mask_logits = sh_mask_logits; rg.sh_mask_temp = sh_mask_temperature; rg.sh_mask_binary = sh_mask_binary;
         rg.v_sh_mask_logits = v_sh_mask_logits;

@@ -24,9 +24,11 @@ from torch import Tensor
 from typing_extensions import Literal
 
 from . import _step
+from ._route import Route, direct_block_sums, route
 from .compression_simulation.ada_mask import MaskedShN
 from ._wrapper import (
     ROW_COLOR,
+    binning_meta,
     fully_fused_projection,
     project_rows,
     GradPrefill,
@@ -41,6 +43,7 @@ from ._wrapper import (
     spherical_harmonics,
     spherical_harmonics_shared,
     spherical_harmonics_view,
+    sh_bwd_fusable,
 )
 
 
@@ -72,16 +75,38 @@ def _camera_centers(viewmats: Tensor) -> Tensor:
     return -inv_t
 
 
-def _prefill_enabled() -> bool:
-    from . import _wrapper
+def _facts(means, colors, viewmats, Ks, covars, dynamic, sh_degree, packed, distributed, render_mode, rasterize_mode, channel_chunk,
+           deterministic, tile_size) -> Route:
+    """The one place that reads the routing facts off ``rasterization()``'s arguments; ``_route.route`` decides on them."""
+    N, C = means.shape[0], viewmats.shape[0]
+    pose_grads = viewmats.requires_grad
+    pair = {}
+    if isinstance(colors, (tuple, list)):
+        assert sh_degree is not None and len(colors) == 2, "a (sh0, shN) pair needs sh_degree"
+        sh0, shN = colors
+        mask = shN if isinstance(shN, MaskedShN) else None  # shN + the mask to apply to it (compression_simulation.ada_mask)
+        if mask is not None:
+            shN = mask.shN
+        assert sh0.shape == (N, 1, 3) and shN.dim() == 3 and shN.shape[0] == N and shN.shape[2] == 3, (sh0.shape, shN.shape)
+        form, D, K = "pair", 3, 1 + shN.shape[1]
+        pair = dict(mask=mask is not None, sh_bwd_fusable=sh_bwd_fusable(K, sh0, shN, pose_grads),
+                    shN_aligned=shN.is_contiguous() and shN.data_ptr() % 16 == 0,
+                    mask_n=mask is not None and mask.mask_logits.numel() == N)
+    else:
+        dim = colors.dim()
+        form = ("ND" if dim == 2 else "CND") if sh_degree is None else ("NK3" if dim == 3 else "CNK3")
+        D, K = (colors.shape[-1] if dim else 0), (colors.shape[-2] if dim >= 2 else 0)
+    sparse_enabled = False
+    if distributed:
+        from . import distributed as dist
 
-    return _wrapper.PREFILL_ENABLED
-
-
-def _step_max_elems() -> int:
-    from ._wrapper import _PINNED_DIRECT_MAX
-
-    return _PINNED_DIRECT_MAX * 1024  # (the count kernel's block sums go straight into pinned memory up to this size)
+        sparse_enabled = dist.sparse_enabled(means, [C])  # (every rank renders the same number of cameras)
+    return route(packed=packed, distributed=distributed, sparse_enabled=sparse_enabled, on_device=means.is_cuda and viewmats.is_cuda,
+                 pose_grads=pose_grads, camera_grads=pose_grads or Ks.requires_grad, means_grad=means.requires_grad,
+                 grad_enabled=torch.is_grad_enabled(), covars=covars is not None, sh_degree=sh_degree, form=form, D=D, K=K,
+                 render_mode=render_mode, antialiased=rasterize_mode == "antialiased", channel_chunk=channel_chunk,
+                 deterministic=deterministic, tile_size=tile_size, C=C, N=N, dynamic=dynamic is not None,
+                 dyn_quantize=tuple(dynamic.quantize) if dynamic is not None else (), **pair)
 
 
 class _RowsColorDepth(torch.autograd.Function):
@@ -99,6 +124,13 @@ class _RowsColorDepth(torch.autograd.Function):
         if v is None:
             return None, None, None
         return v[..., :3], v[..., 3], None
+
+
+def _expected_depth(render_colors: Tensor, render_alphas: Tensor) -> Tensor:
+    """accumulated depth -> expected depth (reference rendering.py:471-477: cat(rc[..., :-1], rc[..., -1:] / ra.clamp(min=1e-10)))"""
+    if render_colors.is_cuda and render_colors.dtype == torch.float32 and render_alphas.dtype == torch.float32:
+        return _ExpectedDepth.apply(render_colors, render_alphas)
+    return torch.cat([render_colors[..., :-1], render_colors[..., -1:] / render_alphas.clamp(min=1e-10)], dim=-1)
 
 
 class _ExpectedDepth(torch.autograd.Function):
@@ -199,15 +231,13 @@ def rasterization(
         dynamic = DynamicSlice.of(dynamic)
         dynamic.check(N)
         assert covars is None, "dynamic splats rotate their quaternions in time: pass quats + scales, not covars"
-        dyn_fused = (not packed and not distributed and covars is None and sh_degree is None and means.is_cuda and viewmats.is_cuda
-                     and not viewmats.requires_grad and torch.is_tensor(colors) and colors.dim() == 2)
-        if "colors" in dynamic.quantize and not (dyn_fused and colors.shape[-1] == 3):
-            dyn_fused = False
-        if not dyn_fused:  # every other route: the same chain through the stand-alone operators, then the plain call
-            means, quats, scales, opacities, c_ = dynamic.apply_unfused(means, quats, scales, opacities,
-                                                                         colors if torch.is_tensor(colors) else None)
-            colors = c_ if c_ is not None else colors
-            dynamic = None
+    R = _facts(means, colors, viewmats, Ks, covars, dynamic, sh_degree, packed, distributed, render_mode, rasterize_mode, channel_chunk,
+               deterministic, tile_size)
+    if dynamic is not None and not R.dyn_fused:  # the same chain through the stand-alone operators, then the plain call
+        means, quats, scales, opacities, c_ = dynamic.apply_unfused(means, quats, scales, opacities,
+                                                                     colors if torch.is_tensor(colors) else None)
+        colors = c_ if c_ is not None else colors
+        dynamic = None
     assert means.shape == (N, 3), means.shape
     if covars is None:
         assert quats.shape == (N, 4), quats.shape
@@ -227,32 +257,20 @@ def rasterization(
     sh_rest = None
     sh_mask = None
     if isinstance(colors, (tuple, list)):
-        assert sh_degree is not None and len(colors) == 2, "a (sh0, shN) pair needs sh_degree"
         sh0, shN = colors
-        masked = shN if isinstance(shN, MaskedShN) else None  # shN + the mask to apply to it (compression_simulation.ada_mask)
-        if masked is not None:
-            shN = masked.shN
-        assert sh0.shape == (N, 1, 3) and shN.dim() == 3 and shN.shape[0] == N and shN.shape[2] == 3, (sh0.shape, shN.shape)
-        split_ok = ((not packed) and (not distributed) and means.is_cuda and viewmats.is_cuda and not viewmats.requires_grad
-                    and shN.shape[1] >= 1)
-        # the fused mask rides on the fused SH backward: vectorisable rows (3 K % 4 == 0), which covers degrees 1 and 3
-        # -- and everything else the backward's fused route checks must be known to hold HERE, or the forward would succeed and
-        # training die in loss.backward() (GS_FUSE_SH_BWD=0, a misaligned shN view): such masks are materialised up front
-        from ._wrapper import _FUSE_SH_BWD
-        mask_ok = masked is None or (split_ok and _FUSE_SH_BWD and (3 * (1 + shN.shape[1])) % 4 == 0 and shN.is_contiguous()
-                                     and shN.data_ptr() % 16 == 0 and masked.mask_logits.numel() == N)
-        if masked is not None and not mask_ok:
-            shN, masked = masked.materialize(), None
-        if split_ok:
+        if isinstance(shN, MaskedShN):
+            if R.fuse_mask:
+                sh_mask, shN = (shN.mask_logits, shN.temperature, shN.binary), shN.shN
+            else:
+                shN = shN.materialize()
+        if R.split_pair:
             colors, sh_rest = sh0, shN
-            if masked is not None:
-                sh_mask = (masked.mask_logits, masked.temperature, masked.binary)
         else:
             colors = torch.cat([sh0, shN], dim=1)
     # the compositing kernels map a tile onto wave64 quadrants of 8x8 pixels: tiles up to 16x16 (the reference launches
     # tile_size^2 threads per block, i.e. accepts up to 32; every caller in the reference uses 16).  Checked here, before
     # projection and binning run, instead of surfacing as a native error afterwards.
-    assert 1 <= tile_size <= 32 and (tile_size <= 16 or tile_size % 2 == 0), \
+    assert 1 <= tile_size <= 32 and (tile_size < 17 or tile_size % 2 == 0), \
         f"tile_size must be in [1, 16] or an even size up to 32 on the HIP backend, got {tile_size}"
 
     if sh_degree is None:
@@ -282,66 +300,58 @@ def rasterization(
         # gaussians are sharded over ranks; gather #gaussians and all cameras
         C_world = [C] * world_size
         cap_world = None  # chunk capacities of the sparse exchange (None: every row travels)
-        if viewmats.requires_grad or Ks.requires_grad:
+        if R.gather_autograd:  # (pose or intrinsics gradients travel back through the gather)
             N_world = D.all_gather_int32(world_size, N, device=device)
             viewmats, Ks = D.all_gather_tensor_list(world_size, [viewmats, Ks])
         else:
-            sparse = (not packed) and D.sparse_enabled(means, C_world)
             # (the shard sizes travel over the host group while the projection is queued: resolved at the exchange)
-            shard_sizes, viewmats, Ks = D.gather_shard_meta(world_size, N, viewmats, Ks, D.sparse_capacity(C, N) if sparse else 0)
+            shard_sizes, viewmats, Ks = D.gather_shard_meta(world_size, N, viewmats, Ks, D.sparse_capacity(C, N) if R.sparse else 0)
             N_world = None
-            cap_world = () if sparse else None  # chunk capacities: known to be in use, values still in flight
+            cap_world = () if R.sparse else None  # chunk capacities: known to be in use, values still in flight
         C = len(viewmats)
 
     # Unpacked batches on one GPU go through SPLAT ROWS: the projection writes one 64-byte row per (camera, gaussian) --
     # mean2d, conic, opacity (x antialias compensation), colour, depth, radius -- that the compositing kernels fetch whole;
     # means2d / conics / opacities (/ colours) below are column views of that buffer (same shapes and dtypes as the
     # reference's separate tensors; like its means2d / conics they are only defined where radii > 0).
-    fuse_sh = (sh_degree is not None and not packed and colors.dim() == 3 and not viewmats.requires_grad and viewmats.is_cuda)
     # (gaussian-sharded: when the colours sit in the rows and the sparse exchange is on, the rows themselves travel --
     # distributed._ExchangeRows; otherwise the separate arrays of the reference's layout do)
-    dist_rows = (distributed and cap_world is not None and means.is_cuda
-                 and (fuse_sh or (sh_degree is None and colors.dim() == 2 and colors.shape[-1] == 3)))
-    use_rows = (not packed) and means.is_cuda and (not distributed or dist_rows)
-    # the fused SH route reads the means a second time (view directions): it gets them back FROM the projection, so that
-    # its contribution to d/d means is added inside the projection's backward kernel
-    means_alias = fuse_sh and means.requires_grad and not use_rows
+    row_colors = colors if R.row_colors else None
+    # shared SH coefficients and fixed poses: the colours are evaluated by the projection pass itself
+    sh_coeffs, sh_deg = (colors, sh_degree) if R.fuse_sh else (None, None)
+    antialiased = rasterize_mode == "antialiased"
+    if R.step_driver:
+        # the common training call: the whole forward as two native calls around the one host read-back (_step.py)
+        return _step.rasterize_step(
+            means, covars, quats, scales, opacities, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip,
+            antialiased, camera_model, row_colors, sh_coeffs, sh_rest, sh_deg, tile_size, backgrounds, absgrad, sh_mask=sh_mask,
+            dynamic=dynamic)
     rows = None
-    compensations = None
     prefill = None
-    if use_rows:
-        row_colors = colors if (sh_degree is None and colors.dim() == 2 and colors.shape[-1] == 3) else None
-        if _step.applicable(means, viewmats, colors, sh_degree, packed, distributed, render_mode, channel_chunk, deterministic,
-                            fuse_sh, row_colors) and C * N <= _step_max_elems() and tile_size <= 16:
-            # the common training call: the whole forward as two native calls around the one host read-back (_step.py)
-            return _step.rasterize_step(
-                means, covars, quats, scales, opacities, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip,
-                rasterize_mode == "antialiased", camera_model, row_colors, colors if fuse_sh else None, sh_rest,
-                sh_degree if fuse_sh else None, tile_size, backgrounds, absgrad, sh_mask=sh_mask, dynamic=dynamic)
+    if R.use_rows:
         # the dense per-gaussian gradients of the projection node are allocated and zero-filled by the compositing
         # forward's side job; its backward then writes the visible gaussians' rows only (_wrapper.GradPrefill)
-        prefill = GradPrefill() if (torch.is_grad_enabled() and _prefill_enabled()) else None
+        prefill = GradPrefill() if R.prefill else None
         radii, means2d, depths, conics, opacities, colors_rows, rows = project_rows(
             means, covars, quats, scales, viewmats, Ks, width, height, opacities, row_colors,
             eps2d=eps2d, near_plane=near_plane, far_plane=far_plane, radius_clip=radius_clip,
-            antialiased=(rasterize_mode == "antialiased"), camera_model=camera_model,
-            # shared SH coefficients and fixed poses: the colours are evaluated by the projection pass itself
-            sh_coeffs=colors if fuse_sh else None, sh_degree=sh_degree if fuse_sh else None, sh_rest=sh_rest,
+            antialiased=antialiased, camera_model=camera_model, sh_coeffs=sh_coeffs, sh_degree=sh_deg, sh_rest=sh_rest,
             prefill=prefill, sh_mask=sh_mask, dynamic=dynamic,
         )
         camera_ids, gaussian_ids = None, None
-        opacity_rider = False
-        if row_colors is not None or fuse_sh:
+        if R.row_colors or R.fuse_sh:
             colors = colors_rows  # [C, N, 3]: columns 6:9 of the rows
     else:
+        # the fused SH route reads the means a second time (view directions): with means_alias it gets them back FROM the
+        # projection, so that its contribution to d/d means is added inside the projection's backward kernel
         proj_results = fully_fused_projection(
             means, covars, quats, scales, viewmats, Ks, width, height,
             eps2d=eps2d, packed=packed, near_plane=near_plane, far_plane=far_plane,
             radius_clip=radius_clip, sparse_grad=sparse_grad,
-            calc_compensations=(rasterize_mode == "antialiased"), camera_model=camera_model, _means_alias=means_alias,
+            calc_compensations=antialiased, camera_model=camera_model, _means_alias=R.means_alias,
         )
         means_sh = means
-        if means_alias:
+        if R.means_alias:
             means_sh, proj_results = proj_results[5], proj_results[:5]
 
         if packed:
@@ -352,10 +362,8 @@ def rasterization(
             camera_ids, gaussian_ids = None, None
             # classic mode + shared SH on the fused route: the per-view opacities ride along with the colour kernels
             # (written by the SH forward, summed over cameras by its backward) instead of `.repeat` + autograd's sum
-            opacity_rider = (compensations is None and sh_degree is not None and colors.dim() == 3
-                             and not viewmats.requires_grad and viewmats.is_cuda)
             opacities_n = opacities
-            if not opacity_rider:
+            if not R.opacity_rider:
                 opacities = opacities.repeat(C, 1)  # [C, N]
 
         if compensations is not None:
@@ -384,44 +392,33 @@ def rasterization(
                                         0 if packed else N, n_elems, camera_ids.contiguous() if packed else None)
 
     # colours -> [C, N, D] or [nnz, D]
-    if use_rows and fuse_sh:
-        pass  # evaluated by the projection pass (columns 6:9 of the splat rows)
-    elif sh_degree is None:
+    if R.sh_op is None:
         if packed:
             colors = gather_rows(colors, gaussian_ids) if colors.dim() == 2 else colors[camera_ids, gaussian_ids]
+        elif colors.dim() == 2:
+            # (one camera: a view -- autograd's expand backward is a sum over the camera axis, a 35 us reduce kernel at 2 M x 9
+            # floats even when that axis has one entry)
+            colors = colors[None] if C == 1 else colors.expand(C, -1, -1)
+    elif R.sh_op == "view":
+        # fused: camera centres, dirs, mask, SH and clamp_min(. + 0.5, 0) in one kernel each way
+        if R.opacity_rider:
+            colors, opacities = spherical_harmonics_view(sh_degree, means_sh, viewmats, colors, radii, opacities=opacities_n)
+            meta["opacities"] = opacities
         else:
-            if colors.dim() == 2:
-                # (one camera: a view -- autograd's expand backward is a sum over the camera axis, a 35 us reduce kernel at 2 M x 9
-                # floats even when that axis has one entry)
-                colors = colors[None] if C == 1 else colors.expand(C, -1, -1)
-    else:
-        fused_sh = False
-        fuse = fuse_sh
-        campos = None if fuse else _camera_centers(viewmats)  # [C, 3] == inverse(viewmats)[:, :3, 3]
-        if packed:
+            colors = spherical_harmonics_view(sh_degree, means_sh, viewmats, colors, radii)  # [C, N, 3]
+    elif R.sh_op != "projection":  # ("projection": evaluated by the projection pass, columns 6:9 of the splat rows)
+        campos = _camera_centers(viewmats)  # [C, 3] == inverse(viewmats)[:, :3, 3]
+        masks = radii > 0
+        if R.sh_op == "packed":
             dirs = gather_rows(means, gaussian_ids) - campos[camera_ids]  # [nnz, 3]
-            masks = radii > 0
             shs = gather_rows(colors, gaussian_ids) if colors.dim() == 3 else colors[camera_ids, gaussian_ids, :, :]
             colors = spherical_harmonics(sh_degree, dirs, shs, masks=masks)  # [nnz, 3]
         else:
-            if fuse:
-                # fused: camera centres, dirs, mask, SH and clamp_min(. + 0.5, 0) in one kernel each way
-                if opacity_rider:
-                    colors, opacities = spherical_harmonics_view(sh_degree, means_sh, viewmats, colors, radii, opacities=opacities_n)
-                    meta["opacities"] = opacities
-                else:  # (with splat rows: written into columns 6:9 of the rows, returned as that view)
-                    colors = spherical_harmonics_view(sh_degree, means_sh, viewmats, colors, radii, rows=rows)  # [C, N, 3]
-                fused_sh = True
-            else:
-                dirs = means[None, :, :] - campos[:, None, :]  # [C, N, 3]
-                masks = radii > 0  # [C, N]
-                if colors.dim() == 3:
-                    colors = spherical_harmonics_shared(sh_degree, dirs, colors, masks=masks)  # [C, N, 3]
-                else:
-                    colors = spherical_harmonics(sh_degree, dirs, colors, masks=masks)  # [C, N, 3]
+            dirs = means[None, :, :] - campos[:, None, :]  # [C, N, 3]
+            sh_fn = spherical_harmonics_shared if R.sh_op == "shared" else spherical_harmonics
+            colors = sh_fn(sh_degree, dirs, colors, masks=masks)  # [C, N, 3]
         # same convention as the reference (rendering.py:392)
-        if not fused_sh:
-            colors = torch.clamp_min(colors + 0.5, 0.0)
+        colors = torch.clamp_min(colors + 0.5, 0.0)
 
     if distributed:
         from . import distributed as D
@@ -434,7 +431,7 @@ def rasterization(
             N_world, caps = shard_sizes()
             cap_world = caps if cap_world is not None else None
         for attempt in range(2):
-            if use_rows:
+            if R.use_rows:
                 C, radii, means2d, depths, conics, opacities, colors, rows = D.exchange_rows(
                     world_rank, N, N_world, C_world, cap_world, *pre[:6], pre_rows)
             else:
@@ -444,7 +441,7 @@ def rasterization(
             # binning up to its read-back; the depth pre-sort queued behind the count keeps the GPU busy while the host
             # looks at the overflow flags (stored to pinned memory before the count) and comes back for the rest
             rows_state = None
-            if use_rows and tile_size <= 16 and _step.rows_applicable(rows, colors, packed, render_mode, channel_chunk, deterministic, absgrad):
+            if R.rows_begin and direct_block_sums(radii.numel()):
                 # (received rows: binning + compositing as native calls around the read-back, like the one-GPU fast path)
                 rows_state = _step.rows_begin(radii, depths, rows, tile_size, tile_width, tile_height)
             else:
@@ -462,14 +459,11 @@ def rasterization(
         if rows_state is not None:
             render_colors, render_alphas, tiles_per_gauss, isect_ids, flatten_ids, isect_offsets = _step.rows_composite(
                 rows_state, means2d, conics, colors, opacities, backgrounds, width, height, absgrad, prefill)
-            meta.update({"tile_width": tile_width, "tile_height": tile_height, "tiles_per_gauss": tiles_per_gauss, "isect_ids": isect_ids,
-                         "flatten_ids": flatten_ids, "isect_offsets": isect_offsets, "width": width, "height": height,
-                         "tile_size": tile_size, "n_cameras": C})
+            meta.update(binning_meta(tile_size, tile_width, tile_height, tiles_per_gauss, isect_ids, flatten_ids, isect_offsets, width, height, C))
             return render_colors, render_alphas, meta
 
     if render_mode in ["RGB+D", "RGB+ED"]:
-        if (rows is not None and colors.dim() == 3 and colors.shape[-1] == 3 and colors.data_ptr() == rows.data_ptr() + 4 * ROW_COLOR
-                and colors.stride() == rows.stride()[:-1] + (1,) and not distributed):
+        if R.depth_view:
             # the colours ride in the splat rows, whose next column IS the depth: the four channels are a view (no cat, and the
             # compositing backward's gradient rows reach the projection backward in place instead of through autograd's split)
             colors = _RowsColorDepth.apply(colors, depths, (rows,))
@@ -491,20 +485,7 @@ def rasterization(
         )
         isect_offsets = isect_offset_encode(isect_ids, C, tile_width, tile_height)
 
-    meta.update(
-        {
-            "tile_width": tile_width,
-            "tile_height": tile_height,
-            "tiles_per_gauss": tiles_per_gauss,
-            "isect_ids": isect_ids,
-            "flatten_ids": flatten_ids,
-            "isect_offsets": isect_offsets,
-            "width": width,
-            "height": height,
-            "tile_size": tile_size,
-            "n_cameras": C,
-        }
-    )
+    meta.update(binning_meta(tile_size, tile_width, tile_height, tiles_per_gauss, isect_ids, flatten_ids, isect_offsets, width, height, C))
 
     if colors.shape[-1] > channel_chunk:
         n_chunks = (colors.shape[-1] + channel_chunk - 1) // channel_chunk
@@ -528,12 +509,6 @@ def rasterization(
             backgrounds=backgrounds, packed=packed, absgrad=absgrad, deterministic=deterministic, prefill=prefill,
         )
     if render_mode in ["ED", "RGB+ED"]:
-        # accumulated depth -> expected depth (reference rendering.py:471-477: cat(rc[..., :-1], rc[..., -1:] / ra.clamp(min=1e-10)))
-        if render_colors.is_cuda and render_colors.dtype == torch.float32 and render_alphas.dtype == torch.float32:
-            render_colors = _ExpectedDepth.apply(render_colors, render_alphas)
-        else:
-            render_colors = torch.cat(
-                [render_colors[..., :-1], render_colors[..., -1:] / render_alphas.clamp(min=1e-10)], dim=-1
-            )
+        render_colors = _expected_depth(render_colors, render_alphas)
 
     return render_colors, render_alphas, meta

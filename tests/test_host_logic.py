@@ -246,3 +246,109 @@ def test_reorder_splats_moves_parameters_optimizer_state_and_strategy_state_toge
     d = {"means": torch.nn.Parameter(torch.arange(12.0).reshape(4, 3)), "opacities": torch.nn.Parameter(torch.arange(4.0))}
     reorder_splats(d, perm=torch.tensor([3, 1, 0, 2]))
     assert d["opacities"].tolist() == [3.0, 1.0, 0.0, 2.0] and d["means"][0].tolist() == [9.0, 10.0, 11.0]
+
+
+# ---- the route decision of rasterization() (_route.route): plain facts in, one record out
+
+_BASE = dict(packed=False, distributed=False, sparse_enabled=False, on_device=True, pose_grads=False, camera_grads=False, means_grad=True,
+             grad_enabled=True, covars=False, sh_degree=3, form="NK3", D=3, K=16, render_mode="RGB", antialiased=False, channel_chunk=32,
+             deterministic=False, tile_size=16, C=1, N=1_000_000)
+# every fact with the values at which some decision changes; the colour entry is (sh_degree, form, D, K, mask, sh_bwd_fusable,
+# shN_aligned, mask_n), the camera entry (pose_grads, camera_grads), the size entry (C, N) within / beyond the pinned bound
+_COLOURS = ([(None, "ND", 3, 0), (None, "ND", 5, 0), (None, "CND", 3, 0), (3, "NK3", 3, 16), (3, "CNK3", 3, 16), (3, "pair", 3, 16), (0, "pair", 3, 1)],
+            [(3, "pair", 3, 16, True) + bits for bits in __import__("itertools").product((False, True), repeat=3)])
+ROUTE_GRID = dict(
+    packed=(False, True), distributed=(False, True), sparse_enabled=(False, True), on_device=(False, True),
+    camera=((False, False), (False, True), (True, True)), means_grad=(False, True), grad_enabled=(False, True),
+    colour=tuple(c + (False,) * 4 for c in _COLOURS[0]) + tuple(_COLOURS[1]), render_mode=("RGB", "D", "ED", "RGB+D", "RGB+ED"),
+    antialiased=(False, True), channel_chunk=(2, 32), deterministic=(False, True), tile_size=(16, 32), size=((2, 300), (1, 3_000_000)),
+    dynamic=((False, (), False), (False, (), True), (True, (), False), (True, ("colors",), False)),  # (dynamic, its quantize, covars)
+    step_enabled=(True, False), prefill_enabled=(True, False))
+
+
+def route_grid(stride=1, offset=0):
+    """(facts, (GS_STEP_DRIVER, GS_GRAD_PREFILL)) of every ``stride``-th point of the full grid."""
+    import itertools
+
+    for p in itertools.islice(itertools.product(*ROUTE_GRID.values()), offset, None, stride):
+        f = dict(zip(ROUTE_GRID, p))
+        (f["pose_grads"], f["camera_grads"]), (f["C"], f["N"]) = f.pop("camera"), f.pop("size")
+        (f["sh_degree"], f["form"], f["D"], f["K"], f["mask"], f["sh_bwd_fusable"], f["shN_aligned"], f["mask_n"]) = f.pop("colour")
+        f["dynamic"], f["dyn_quantize"], f["covars"] = f.pop("dynamic")
+        yield f, (f.pop("step_enabled"), f.pop("prefill_enabled"))
+
+
+def test_route_invariants_over_the_grid(monkeypatch):
+    """Every 61st point of the grid (61 divides no dimension, so every pair of values still meets; the whole grid, 7.4 M points, was walked
+    once against the predicates this function replaced)."""
+    from gscodec_studio_amd import _route, _step, _wrapper
+
+    bound = _wrapper._PINNED_DIRECT_MAX * 1024
+    n = 0
+    for f, (step_on, prefill_on) in route_grid(stride=61):
+        monkeypatch.setattr(_step, "ENABLED", step_on)
+        monkeypatch.setattr(_wrapper, "PREFILL_ENABLED", prefill_on)
+        r = _route.route(**f)
+        n += 1
+        fixed = not f["pose_grads"]
+        assert not r.fuse_mask or r.split_pair, f
+        assert not r.split_pair or r.fuse_sh, f
+        assert not r.fuse_sh or fixed, f
+        assert not (fixed and (f["packed"] or f["form"] not in ("NK3", "pair"))) or not r.fuse_sh, f
+        if r.step_driver:
+            assert r.use_rows and f["render_mode"] == "RGB" and f["channel_chunk"] >= 3 and not f["deterministic"] and not f["distributed"], f
+            assert f["C"] * f["N"] <= bound and f["tile_size"] <= 16 and step_on, f
+        assert not r.use_rows or (not f["packed"] and f["on_device"]), f
+        assert not r.means_alias or (r.fuse_sh and not r.use_rows), f
+        assert not r.opacity_rider or (not r.use_rows and not f["antialiased"]), f
+        assert not r.dyn_fused or (r.use_rows and f["sh_degree"] is None), f
+        assert not ("colors" in f["dyn_quantize"] and f["D"] != 3) or not r.dyn_fused, f
+        assert not r.depth_view or ((r.row_colors or r.fuse_sh) and r.use_rows and not f["distributed"]), f
+        assert not r.prefill or (prefill_on and f["grad_enabled"] and r.use_rows and not r.step_driver), f
+        assert (r.sh_op is None) == (f["sh_degree"] is None) and (r.sh_op == "projection") == (r.use_rows and r.fuse_sh), f
+    assert n > 100_000
+
+
+def test_route_named_rows(monkeypatch):
+    from gscodec_studio_amd import _route, _step, _wrapper
+
+    def R(**kw):
+        return _route.route(**{**_BASE, **kw})
+
+    # BASELINE config 2: one camera, 1 M splats, [N, 16, 3] coefficients at degree 3, unpacked -> the step driver
+    r = R()
+    assert r.step_driver and r.use_rows and r.fuse_sh and r.sh_op == "projection" and not r.prefill
+    # the API default packed=True -> packed arrays
+    r = R(packed=True)
+    assert not r.use_rows and not r.step_driver and not r.fuse_sh and r.sh_op == "packed" and not r.means_alias and not r.opacity_rider
+    # pose gradients with shared SH: nothing fused (rows through the operators, the stand-alone shared SH operator); the array
+    # projection with means_alias is the gaussian-sharded dense exchange's route for shared SH under fixed poses
+    r = R(pose_grads=True, camera_grads=True)
+    assert r.use_rows and not r.step_driver and not r.fuse_sh and r.sh_op == "shared" and not r.means_alias
+    r = R(distributed=True)
+    assert not r.use_rows and r.fuse_sh and r.means_alias and r.opacity_rider and r.sh_op == "view" and not r.sparse
+    r = R(distributed=True, sparse_enabled=True)
+    assert r.sparse and r.dist_rows and r.use_rows and r.rows_begin and not r.step_driver and not r.means_alias
+    # a mask on the pair: fused where the SH backward is (K = 16: 48 floats per splat), materialised where it is not (K = 9: 27)
+    for K, fused in ((9, False), (16, True), (4, True)):
+        sh0, shN = torch.zeros(8, 1, 3), torch.zeros(8, K - 1, 3)
+        pair = dict(form="pair", K=K, mask=True, shN_aligned=shN.is_contiguous() and shN.data_ptr() % 16 == 0, mask_n=True)
+        r = R(**pair, sh_bwd_fusable=_wrapper.sh_bwd_fusable(K, sh0, shN, False))
+        assert r.split_pair and r.fuse_mask == fused and r.step_driver, K
+        monkeypatch.setattr(_wrapper, "_FUSE_SH_BWD", False)  # (GS_FUSE_SH_BWD=0: read at call time)
+        assert not R(**pair, sh_bwd_fusable=_wrapper.sh_bwd_fusable(K, sh0, shN, False)).fuse_mask
+        monkeypatch.undo()
+        assert not _wrapper.sh_bwd_fusable(K, sh0, shN, True)
+    # the switches are read at call time
+    monkeypatch.setattr(_step, "ENABLED", False)
+    r = R()
+    assert not r.step_driver and r.use_rows and r.prefill
+    monkeypatch.setattr(_wrapper, "PREFILL_ENABLED", False)
+    assert not R().prefill
+    monkeypatch.undo()
+    monkeypatch.setattr(_wrapper, "_PINNED_DIRECT_MAX", 4)
+    assert not R().step_driver and R(N=4096).step_driver and not R(N=4097).step_driver and not R(N=0).step_driver
+    monkeypatch.undo()
+    assert not R(tile_size=32).step_driver and not R(render_mode="RGB+D").step_driver and R(render_mode="RGB+D").depth_view
+    assert R(sh_degree=None, form="ND", K=0, dynamic=True).dyn_fused and not R(sh_degree=None, form="ND", D=5, K=0, dynamic=True,
+                                                                              dyn_quantize=("colors",)).dyn_fused
