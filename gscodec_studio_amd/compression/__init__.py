@@ -12,9 +12,16 @@
 * ``png_compression``: the file level -- ``PngCompression.compress(dir, splats)`` / ``decompress(dir)`` with the reference's
   directory layout (PNG image grids, ``shN.npz`` + ``mask.bin``, ``meta.json``) and a self-contained 8-bit PNG reader /
   writer (the image has no imageio), so directories written by either implementation are read by the other.
+
+* ``entropy_coding_compression``: ``EntropyCodingCompression``, the reference's ``--compression entropy_coding`` -- the same
+  directory, with the scales and the quats rANS-coded on the GPU by ``ans`` (csrc/ans.hip: histogram, lane-per-stream encode,
+  pack, decode).  The reference takes its coder from the ``constriction`` package; the bitstream here is this project's own,
+  defined by the numpy coder ``ans_reference`` that the kernels match byte for byte.
 """
 from .decode import decode_to_rasterizer_inputs, kmeans_decode, kmeans_encode, morton_order, reorder_splats, sort_splats
 from .png_compression import PngCompression, png_read, png_write
+from .ans import ans_decode, ans_encode, normalize_frequencies, symbol_histogram
+from .entropy_coding_compression import EntropyCodingCompression
 from .grid_codec import (
     compress_to_arrays,
     decompress_from_arrays,
@@ -26,4 +33,5 @@ from .grid_codec import (
 
 __all__ = ["quantize_grid", "dequantize_grid", "compress_to_arrays", "decompress_from_arrays", "log_transform",
            "inverse_log_transform", "decode_to_rasterizer_inputs", "kmeans_decode", "kmeans_encode", "morton_order",
-           "sort_splats", "reorder_splats", "PngCompression", "png_read", "png_write"]
+           "sort_splats", "reorder_splats", "PngCompression", "png_read", "png_write", "EntropyCodingCompression", "ans_encode",
+           "ans_decode", "normalize_frequencies", "symbol_histogram"]

@@ -26,7 +26,7 @@ import os
 import struct
 import zlib
 from dataclasses import dataclass
-from typing import Any, Dict, Union
+from typing import Any, Dict, Tuple, Union
 
 import numpy as np
 import torch
@@ -110,6 +110,56 @@ def _meta_of(params: Tensor) -> Dict[str, Any]:
     return {"shape": list(params.shape), "dtype": str(params.dtype).split(".")[1]}
 
 
+def prepare_splats(splats: Dict[str, Tensor], opacity_threshold: float, use_sort: Union[bool, str], verbose: bool
+                   ) -> Tuple[Dict[str, Tensor], int]:
+    """What the reference's compress() does in front of the per-attribute codecs (png_compression.py:101-125), on detached
+    copies: the opacity filter, the log transform of the means, the normalised quats, the crop to a square count and the
+    ordering (``use_sort``: True = PLAS, "morton" = morton_order, False = none).  Returns (splats, side length)."""
+    splats = {k: v.detach() for k, v in splats.items()}
+    keep = torch.sigmoid(splats["opacities"]) >= opacity_threshold
+    splats = {k: v[keep] for k, v in splats.items()}
+    splats["means"] = log_transform(splats["means"])
+    splats["quats"] = torch.nn.functional.normalize(splats["quats"], dim=-1)
+    n_before = len(splats["means"])
+    splats, side = _crop_to_square(splats)
+    if verbose and len(splats["means"]) != n_before:
+        print(f"Warning: Number of Gaussians was not square. Removed {n_before - len(splats['means'])} Gaussians.")
+    if use_sort == "morton":
+        order = morton_order(splats["means"])
+        splats = {k: v[order] for k, v in splats.items()}
+    elif use_sort:
+        splats = sort_splats(splats, verbose=verbose)
+    return splats, side
+
+
+def compress_masked_kmeans(compress_dir: str, param_name: str, params: Tensor, n_clusters: int) -> Dict[str, Any]:
+    """png_compression.py:521-600: the splats with any positive higher-band coefficient are clustered, the rest is a bit
+    in mask.bin."""
+    mask = (params > 0).any(dim=1).any(dim=1).reshape(-1)
+    n = int(mask.numel())
+    np.packbits(mask.cpu().numpy().astype(bool))[: (n + 7) // 8].tofile(os.path.join(compress_dir, "mask.bin"))
+    if int(mask.sum()) == 0:  # nothing to cluster: an empty codebook, every splat decodes to zeros
+        np.savez_compressed(os.path.join(compress_dir, f"{param_name}.npz"), centroids=np.zeros((0, params[0].numel()), np.uint8),
+                            labels=np.zeros(0, np.uint16))
+        meta = {**_meta_of(params), "mins": 0.0, "maxs": 0.0, "quantization": 8}
+    else:
+        cq, labels, meta = kmeans_encode(params[mask], n_clusters=n_clusters)
+        np.savez_compressed(os.path.join(compress_dir, f"{param_name}.npz"), centroids=cq.cpu().numpy(),
+                            labels=labels.cpu().numpy().astype(np.uint16))
+    meta.update({"shape": list(params.shape), "mask_bits": n, "mask_byte": (n + 7) // 8})
+    return meta
+
+
+def decompress_masked_kmeans(compress_dir: str, param_name: str, m: Dict[str, Any], device) -> Tensor:
+    """png_compression.py:603-640: mask.bin + the codebook -> the higher bands, zeros where the mask is clear."""
+    bits_loaded = np.fromfile(os.path.join(compress_dir, "mask.bin"), dtype=np.uint8)
+    mask = torch.from_numpy(np.unpackbits(bits_loaded)[: m["mask_bits"]].astype(bool))
+    z = np.load(os.path.join(compress_dir, f"{param_name}.npz"))
+    if z["labels"].size == 0:
+        return torch.zeros(m["shape"], dtype=getattr(torch, m["dtype"]), device=device)
+    return kmeans_decode(torch.from_numpy(z["centroids"]), torch.from_numpy(z["labels"].astype(np.int32)), m, device=device, mask=mask)
+
+
 @dataclass
 class PngCompression:
     """The reference's ``PngCompression`` (same constructor arguments, same files).  ``use_sort``: True = PLAS (external
@@ -125,20 +175,7 @@ class PngCompression:
         if entropy_models is not None:
             raise ValueError("PngCompression should not require entropy_models")
         os.makedirs(compress_dir, exist_ok=True)
-        splats = {k: v.detach() for k, v in splats.items()}
-        keep = torch.sigmoid(splats["opacities"]) >= self.opacity_threshold
-        splats = {k: v[keep] for k, v in splats.items()}
-        splats["means"] = log_transform(splats["means"])
-        splats["quats"] = torch.nn.functional.normalize(splats["quats"], dim=-1)
-        n_before = len(splats["means"])
-        splats, side = _crop_to_square(splats)
-        if self.verbose and len(splats["means"]) != n_before:
-            print(f"Warning: Number of Gaussians was not square. Removed {n_before - len(splats['means'])} Gaussians.")
-        if self.use_sort == "morton":
-            order = morton_order(splats["means"])
-            splats = {k: v[order] for k, v in splats.items()}
-        elif self.use_sort:
-            splats = sort_splats(splats, verbose=self.verbose)
+        splats, side = prepare_splats(splats, self.opacity_threshold, self.use_sort, self.verbose)
 
         meta: Dict[str, Any] = {}
         for name, value in splats.items():
@@ -151,29 +188,12 @@ class PngCompression:
                 for fn, plane in zip(files, planes):
                     png_write(os.path.join(compress_dir, fn), plane.cpu().numpy())
             elif name == "shN":
-                meta[name] = self._compress_masked_kmeans(compress_dir, value)
+                meta[name] = compress_masked_kmeans(compress_dir, name, value, self.n_clusters)
             else:
                 np.savez_compressed(os.path.join(compress_dir, f"{name}.npz"), arr=value.cpu().numpy())
                 meta[name] = _meta_of(value)
         with open(os.path.join(compress_dir, "meta.json"), "w") as f:
             json.dump(meta, f)
-
-    def _compress_masked_kmeans(self, compress_dir: str, params: Tensor) -> Dict[str, Any]:
-        """png_compression.py:521-600: the splats with any positive higher-band coefficient are clustered, the rest is a bit
-        in mask.bin."""
-        mask = (params > 0).any(dim=1).any(dim=1).reshape(-1)
-        n = int(mask.numel())
-        np.packbits(mask.cpu().numpy().astype(bool))[: (n + 7) // 8].tofile(os.path.join(compress_dir, "mask.bin"))
-        if int(mask.sum()) == 0:  # nothing to cluster: an empty codebook, every splat decodes to zeros
-            np.savez_compressed(os.path.join(compress_dir, "shN.npz"), centroids=np.zeros((0, params[0].numel()), np.uint8),
-                                labels=np.zeros(0, np.uint16))
-            meta = {**_meta_of(params), "mins": 0.0, "maxs": 0.0, "quantization": 8}
-        else:
-            cq, labels, meta = kmeans_encode(params[mask], n_clusters=self.n_clusters)
-            np.savez_compressed(os.path.join(compress_dir, "shN.npz"), centroids=cq.cpu().numpy(),
-                                labels=labels.cpu().numpy().astype(np.uint16))
-        meta.update({"shape": list(params.shape), "mask_bits": n, "mask_byte": (n + 7) // 8})
-        return meta
 
     @torch.no_grad()
     def decompress(self, compress_dir: str, device="cuda") -> Dict[str, Tensor]:
@@ -189,14 +209,7 @@ class PngCompression:
                 planes = [torch.from_numpy(png_read(os.path.join(compress_dir, fn))) for fn in files]
                 splats[name] = dequantize_grid(planes, m, device=device)
             elif name == "shN":
-                bits_loaded = np.fromfile(os.path.join(compress_dir, "mask.bin"), dtype=np.uint8)
-                mask = torch.from_numpy(np.unpackbits(bits_loaded)[: m["mask_bits"]].astype(bool))
-                z = np.load(os.path.join(compress_dir, "shN.npz"))
-                if z["labels"].size == 0:
-                    splats[name] = torch.zeros(m["shape"], dtype=getattr(torch, m["dtype"]), device=device)
-                    continue
-                splats[name] = kmeans_decode(torch.from_numpy(z["centroids"]), torch.from_numpy(z["labels"].astype(np.int32)), m,
-                                             device=device, mask=mask)
+                splats[name] = decompress_masked_kmeans(compress_dir, name, m, device)
             else:
                 arr = np.load(os.path.join(compress_dir, f"{name}.npz"))["arr"]
                 splats[name] = torch.tensor(arr).reshape(m["shape"]).to(dtype=getattr(torch, m["dtype"]), device=device)

@@ -43,7 +43,8 @@ extern "C" {
  * entries (gs_ssim_fwd, gs_ssim_bwd, gs_ssim_work_bytes, gs_ssim_window): additive, no existing signature changed.  The
  * densification-strategy entries (gs_relocation, gs_inject_noise, gs_densify_stats) are additive in the same way, and so are
  * the two of the spacetime strategies (gs_stg_omega_mask, gs_stg_freeze_grads), and the bilateral-grid entries
- * (gs_bilagrid_slice_fwd / _bwd, gs_bilagrid_tv_fwd / _bwd, gs_bilagrid_tv_work_bytes). */
+ * (gs_bilagrid_slice_fwd / _bwd, gs_bilagrid_tv_fwd / _bwd, gs_bilagrid_tv_work_bytes), and the entropy-coder entries
+ * (gs_ans_histogram, gs_ans_encode_bytes, gs_ans_encode, gs_ans_pack, gs_ans_decode). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -849,6 +850,42 @@ int32_t gs_kmeans_decode(uint64_t n_rows, uint32_t width, const int32_t *labels,
  * (filter type, filtered scanline), out = h rows of stride bytes, bpp = bytes per pixel.  The sequential part of reading the
  * image grids the reference writes through imageio (gsplat/compression/png_compression.py:196, 271, 344-349). */
 int32_t gs_png_unfilter(const uint8_t *data, uint32_t h, uint32_t stride, uint32_t bpp, uint8_t *out);
+
+
+/* ------------------------------------------------------------------------
+ * Entropy coder of the on-disk format (ans.hip): a static, table-based, byte-wise rANS coder over MANY independent streams, one
+ * GPU lane per stream -- what EntropyCodingCompression (gsplat/compression/entropy_coding_compression.py:328-446) takes from the
+ * `constriction` package, behind a bitstream of this project's own whose definition is the numpy coder
+ * gscodec_studio_amd/compression/ans_reference.py (the kernels' output is byte-identical to it).
+ *   state 32 bits, lower bound 2^23, renormalised one byte at a time; probability resolution 2^P, 8 <= P <= 14;
+ *   channel c of the N symbols (8 bits each) is cut into n_streams = ceil(N / S) streams of S symbols, stream k = symbols
+ *   [k S, min(N, (k + 1) S)); stream index sid = c * n_streams + k; a stream is encoded last symbol first, so it decodes forward.
+ * freq / cum: uint32 [C, 256] integer frequencies (sum 2^P per channel) and their exclusive prefix sums, derived on the host.
+ *
+ * gs_ans_histogram: symbols uint8 [N, C] -> counts uint32 [C, 256] (ADDED to: the caller zero-fills), LDS histogram per
+ *   workgroup and one flush of atomics per workgroup; channel_major (uint8 [C, N], may be NULL) receives the transposed copy
+ *   the encoder streams through.  C <= 16.
+ * gs_ans_encode: each lane walks its stream backwards and writes its renormalisation bytes to the END of its slot of
+ *   gs_ans_slot_bytes(S, P) = ceil(S P / 8) + 8 bytes (the worst case) in scratch (>= gs_ans_encode_bytes); lengths [C n_streams]
+ *   = bytes written, states = final state; the bytes of stream sid are scratch[(sid + 1) slot - lengths[sid], (sid + 1) slot), in
+ *   the order the decoder consumes them.  *status (device uint32, zero-filled by the caller) gets bit 0 set when a symbol with
+ *   frequency 0 was met and bit 1 when a slot was too small (neither write leaves the slot).
+ * gs_ans_pack: after an exclusive scan of (4 + lengths) into offsets (int64 [n + 1], device): payload[offsets[sid]...] = the
+ *   little-endian final state, then the stream's bytes.  A stream that would not fit payload_bytes is skipped.
+ * gs_ans_decode: payload + offsets (int64 [C n_streams + 1], device) -> symbols uint8 [N, C] (the layout gs_grid_dequantize
+ *   reads).  Every read is bounded to the stream's byte range clamped to [0, payload_bytes]; beyond it the byte is 0: a damaged
+ *   file decodes to wrong symbols, never to an out-of-range access.  P <= 14: the slot-to-symbol table (2^P bytes) lives in LDS. */
+uint32_t gs_ans_slot_bytes(uint32_t S, uint32_t P);
+uint64_t gs_ans_encode_bytes(uint64_t N, uint32_t C, uint32_t S, uint32_t P);
+int32_t gs_ans_histogram(uint64_t N, uint32_t C, const uint8_t *symbols, uint32_t *counts, uint8_t *channel_major,
+                         gs_stream_t stream);
+int32_t gs_ans_encode(uint64_t N, uint32_t C, uint32_t S, uint32_t P, const uint8_t *channel_major, const uint32_t *freq,
+                      const uint32_t *cum, uint8_t *scratch, uint64_t scratch_bytes, uint32_t *lengths, uint32_t *states,
+                      uint32_t *status, gs_stream_t stream);
+int32_t gs_ans_pack(uint64_t n_streams_total, uint32_t S, uint32_t P, const uint8_t *scratch, const uint32_t *lengths,
+                    const uint32_t *states, const int64_t *offsets, uint8_t *payload, uint64_t payload_bytes, gs_stream_t stream);
+int32_t gs_ans_decode(uint64_t N, uint32_t C, uint32_t S, uint32_t P, const uint8_t *payload, uint64_t payload_bytes,
+                      const int64_t *offsets, const uint32_t *freq, const uint32_t *cum, uint8_t *symbols, gs_stream_t stream);
 
 
 /* ------------------------------------------------------------------------

@@ -1,0 +1,209 @@
+"""The rANS coder on the GPU (csrc/ans.hip behind gscodec_studio_amd.compression.ans) and EntropyCodingCompression: the reference's
+symbols, probability table and decoded parameters bit for bit (tests/golden/ans.npz, recorded from the reference's
+_compress_factorized_ans / _decompress_factorized_ans), byte identity with the numpy coder that defines the format, the size of
+the files against the empirical entropy, and the directory level."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from ans_cases import DISTRIBUTIONS, draw, entropy_bytes, probabilities, size_bound
+from util import N, T, golden
+
+pytestmark = pytest.mark.gpu
+
+
+def _golden_case(name):
+    g = golden("ans.npz")
+    return {k: g[f"{name}.{k}"] for k in ("x", "mins", "maxs", "symbols", "prob", "decoded")}
+
+
+@pytest.mark.parametrize("name", ["scales", "quats"])
+def test_symbols_probabilities_and_decoded_parameters_match_the_reference(name, tmp_path):
+    from gscodec_studio_amd.compression import ans, dequantize_grid, quantize_grid
+    from gscodec_studio_amd.compression import entropy_coding_compression as E
+
+    g = _golden_case(name)
+    x = T(g["x"])
+    (plane,), meta = quantize_grid(x, 64, bits=8)
+    symbols = plane.reshape(x.shape[0], -1)
+    assert np.array_equal(N(symbols).T, g["symbols"])  # includes the planted .5 ties (half to even) and the extremes 0 / 255
+    assert np.array_equal(np.asarray(meta["mins"], np.float32), g["mins"]) and np.array_equal(np.asarray(meta["maxs"], np.float32), g["maxs"])
+    counts = ans.symbol_histogram(symbols)
+    assert np.array_equal(N(counts), np.stack([np.bincount(r, minlength=256) for r in g["symbols"]]))
+    prob = ans.probabilities(counts)
+    assert prob.dtype == np.float32 and np.array_equal(prob.view(np.uint32), g["prob"].view(np.uint32))
+    # the parameters decoded from those symbols: float32 maxs - mins, float64 product and sum, cast
+    dec = dequantize_grid([T(np.ascontiguousarray(g["symbols"].T))], meta)
+    assert np.array_equal(N(dec).view(np.uint32), g["decoded"].view(np.uint32))
+    # and through the two codec functions, files in between
+    d = str(tmp_path)
+    meta2 = E._compress_factorized_ans(d, name, x, n_sidelen=64)
+    assert meta2 == meta and set(meta2) == {"shape", "dtype", "mins", "maxs"}
+    assert np.array_equal(np.load(os.path.join(d, f"{name}_prob.npy")).view(np.uint32), g["prob"].view(np.uint32))
+    out = E._decompress_factorized_ans(d, name, json.loads(json.dumps(meta2)))
+    assert out.dtype == torch.float32 and np.array_equal(N(out).view(np.uint32), g["decoded"].view(np.uint32))
+
+
+def _mixed(n, channels, seed):
+    """One distribution per channel, cycling through the three; channel 3 (when there is one) is a single symbol."""
+    sym = np.concatenate([draw(DISTRIBUTIONS[c % 3], n, 1, seed=seed + c) for c in range(channels)], axis=1)
+    if channels == 4:
+        sym[:, 3] = 41
+    return sym
+
+
+@pytest.mark.parametrize("channels", [1, 3, 4])
+@pytest.mark.parametrize("stream_len", [64, 1024])
+def test_byte_identity_with_the_numpy_coder(stream_len, channels):
+    """N = 1, S - 1, S, S + 1, 64 S + 3, 257 S + 5: one lane, a full and a ragged stream, several waves and (S = 64: 258 streams
+    per channel) more than one workgroup of the decoder and five of the encoder.  Either side's stream decodes exactly with
+    the other side's decoder."""
+    from gscodec_studio_amd.compression import ans, ans_reference as R
+
+    S = stream_len
+    for n in (1, S - 1, S, S + 1, 64 * S + 3, 257 * S + 5):
+        sym = _mixed(n, channels, seed=n % 97)
+        prob = probabilities(sym)
+        ours = ans.ans_encode(T(sym), prob, stream_len=S)
+        want = R.encode(sym, prob, stream_len=S)
+        assert ours.dtype == np.uint8 and ours.shape == want.shape and np.array_equal(ours, want), (S, channels, n)
+        back = ans.ans_decode(want, prob, device="cuda")
+        assert back.dtype == torch.uint8 and tuple(back.shape) == sym.shape and np.array_equal(N(back), sym), (S, channels, n)
+        assert np.array_equal(R.decode(ours, prob), sym)
+
+
+def test_other_resolutions_and_tables():
+    """P = 12 and 8 travel in the header; a table that is not the data's own histogram (every symbol possible) still round-trips."""
+    from gscodec_studio_amd.compression import ans, ans_reference as R
+
+    sym = _mixed(5 * 100 + 7, 3, seed=5)
+    flat = (probabilities(sym) + np.float32(1e-4)).astype(np.float32)
+    for bits, prob in ((12, probabilities(sym)), (8, flat), (14, flat)):
+        ours = ans.ans_encode(T(sym), prob, stream_len=100, bits=bits)
+        assert np.array_equal(ours, R.encode(sym, prob, stream_len=100, bits=bits))
+        assert np.array_equal(N(ans.ans_decode(ours, prob)), sym)
+    with pytest.raises(ValueError):  # a symbol the table gives no probability
+        ans.ans_encode(T(np.full((10, 3), 250, np.uint8)), probabilities(np.zeros((10, 3), np.uint8)))
+
+
+def test_damaged_payload_stays_in_bounds_and_matches_the_numpy_decoder():
+    """The container is valid, the bytes are not: the kernel substitutes 0 beyond each stream's range exactly like the numpy
+    decoder, so both give the same (wrong) symbols."""
+    from gscodec_studio_amd.compression import ans, ans_reference as R
+
+    sym = draw("uniform", 70 * 64 + 9, 2)
+    prob = probabilities(sym)
+    blob = R.encode(sym, prob, stream_len=64)
+    bad = blob.copy()
+    bad[-3000:] = np.random.default_rng(1).integers(0, 256, 3000, dtype=np.uint8)
+    out = N(ans.ans_decode(bad, prob))
+    assert np.array_equal(out, R.decode(bad, prob)) and not np.array_equal(out, sym)
+
+
+@pytest.mark.parametrize("kind", DISTRIBUTIONS)
+def test_size_bound_hip_coder(kind):
+    """file bytes <= 1.01 x empirical entropy + 8 bytes per stream + 64, on 16384 symbols at S = 1024 (by byte identity the
+    numpy coder's number; kept as a guard)."""
+    from gscodec_studio_amd.compression import ans
+
+    sym = draw(kind, 16384, 1)
+    blob = ans.ans_encode(T(sym), probabilities(sym), stream_len=1024)
+    print(f"{kind}: {blob.size} bytes, entropy {entropy_bytes(sym):.1f} bytes, bound {size_bound(sym, 1024):.1f}")
+    assert blob.size <= size_bound(sym, 1024)
+
+
+def _splats(n=2500):
+    """A 2,500-splat crop of the garden fixture with seeded raw (pre-activation) attributes and degree-1 higher bands.  Every
+    50th splat is transparent (sigmoid(-8) < 0.005), so the opacity filter drops n / 50 of them whatever the seed draws and the
+    crop to a square count has a remainder to drop: 2500 -> 2450 at the most -> 49^2."""
+    fx = golden("garden_small.npz")
+    g = torch.Generator().manual_seed(9)
+    shN = torch.randn(n, 3, 3, generator=g) * 0.1
+    shN[::4] = -shN[::4].abs()  # a quarter of the splats has no positive higher-band coefficient: masked out
+    opacities = torch.randn(n, generator=g) * 2 + 1
+    opacities[::50] = -8.0
+    s = {"means": torch.from_numpy(fx["means"][:n]), "scales": torch.log(torch.from_numpy(fx["scales"][:n]) + 1e-4),
+         "quats": torch.from_numpy(fx["quats"][:n]) * (0.5 + torch.rand(n, 1, generator=g)),
+         "opacities": opacities, "sh0": torch.randn(n, 1, 3, generator=g), "shN": shN}
+    return {k: v.float().cuda() for k, v in s.items()}
+
+
+def test_directory_round_trip(tmp_path):
+    from gscodec_studio_amd.compression import EntropyCodingCompression, ans, dequantize_grid, inverse_log_transform, quantize_grid
+    from gscodec_studio_amd.compression.png_compression import prepare_splats
+
+    splats = _splats()
+    before = {k: v.clone() for k, v in splats.items()}
+    d = str(tmp_path / "dir")
+    with pytest.raises(ValueError):
+        EntropyCodingCompression(use_sort=False, verbose=False).compress(d, splats, entropy_models=None)
+    with pytest.raises(ImportError):  # PLAS, as in the reference
+        EntropyCodingCompression(verbose=False).compress(str(tmp_path / "plas"), splats, entropy_models={})
+    codec = EntropyCodingCompression(use_sort="morton", verbose=False, n_clusters=256)
+    codec.compress(d, splats, entropy_models={})
+    assert all(torch.equal(splats[k], before[k]) for k in before)  # the caller's dictionary is left alone
+    assert sorted(os.listdir(d)) == sorted("means_l.png means_u.png scales.bin scales_prob.npy quats.bin quats_prob.npy opacities.png "
+                                           "sh0.png shN.npz mask.bin meta.json".split())
+    with open(os.path.join(d, "meta.json")) as f:
+        meta = json.load(f)
+    assert list(meta) == ["means", "scales", "quats", "opacities", "sh0", "shN"]
+    for k in ("means", "scales", "quats", "opacities", "sh0"):
+        assert set(meta[k]) == {"shape", "dtype", "mins", "maxs"}, k
+    assert set(meta["shN"]) == {"shape", "dtype", "mins", "maxs", "quantization", "mask_bits", "mask_byte"}
+    out = codec.decompress(d)
+
+    kept, side = prepare_splats(splats, 0.005, "morton", False)
+    assert side == 49 and len(kept["means"]) == 49 * 49  # both the filter and the crop dropped splats
+    for k in ("scales", "quats"):  # the dequantised symbols, bit for bit; the stream holds exactly those symbols
+        (plane,), m = quantize_grid(kept[k], side, bits=8)
+        sym = plane.reshape(side * side, -1)
+        assert torch.equal(out[k], dequantize_grid([sym], m)), k
+        prob = np.load(os.path.join(d, f"{k}_prob.npy"))
+        assert prob.dtype == np.float32 and prob.shape == (sym.shape[1], 256)
+        assert np.array_equal(prob, ans.probabilities(ans.symbol_histogram(sym)))
+        assert torch.equal(ans.ans_decode(np.fromfile(os.path.join(d, f"{k}.bin"), np.uint8), prob), sym)
+    for k, bits in (("means", 16), ("opacities", 8), ("sh0", 8)):  # what the existing grid codec gives
+        planes, m = quantize_grid(kept[k], side, bits=bits)
+        want = dequantize_grid(planes, m)
+        assert torch.equal(out[k], inverse_log_transform(want) if k == "means" else want), k
+    has = (kept["shN"] > 0).any(dim=1).any(dim=1)
+    assert out["shN"].shape == kept["shN"].shape and bool((out["shN"][~has] == 0).all())
+    assert torch.unique(out["shN"][has].reshape(int(has.sum()), -1), dim=0).shape[0] <= 256
+
+
+def test_directory_registry_and_foreign_streams(tmp_path):
+    from gscodec_studio_amd.compression import EntropyCodingCompression
+
+    splats = _splats(900)
+    d = str(tmp_path / "ans")
+    EntropyCodingCompression(use_sort=False, verbose=False, n_clusters=64).compress(d, splats, entropy_models={})
+    want = EntropyCodingCompression().decompress(d)
+
+    # scales through the plain PNG codec, and back: the same values either way (both are the 8-bit min-max symbols)
+    png = {"scales": {"encode": "_compress_png", "decode": "_decompress_png"}}
+    d2 = str(tmp_path / "png")
+    EntropyCodingCompression(use_sort=False, verbose=False, n_clusters=64, attribute_codec_registry=png).compress(d2, splats, entropy_models={})
+    names = os.listdir(d2)
+    assert "scales.png" in names and "scales.bin" not in names and "scales_prob.npy" not in names and "quats.bin" in names
+    got = EntropyCodingCompression(attribute_codec_registry=png).decompress(d2)
+    assert all(torch.equal(got[k], want[k]) for k in ("means", "scales", "quats", "opacities", "sh0"))
+    back = {"scales": {"encode": "_compress_factorized_ans", "decode": "_decompress_factorized_ans"}}
+    d3 = str(tmp_path / "back")
+    EntropyCodingCompression(use_sort=False, verbose=False, n_clusters=64, attribute_codec_registry=back).compress(d3, splats, entropy_models={})
+    assert np.array_equal(np.fromfile(os.path.join(d3, "scales.bin"), np.uint8), np.fromfile(os.path.join(d, "scales.bin"), np.uint8))
+
+    for key, name in (("encode", "_compress_gaussian_ans"), ("decode", "_decompress_gaussian_ans")):
+        codec = EntropyCodingCompression(use_sort=False, verbose=False, attribute_codec_registry={"quats": {key: name}})
+        with pytest.raises(NotImplementedError, match="hash-grid Gaussian"):
+            if key == "encode":
+                codec.compress(str(tmp_path / "gauss"), splats, entropy_models={})
+            else:
+                codec.decompress(d)
+
+    # a scales.bin of arbitrary uint32 words, as the reference's coder would leave it: refused on the host, with the reason
+    np.random.default_rng(2).integers(0, 2**32, 700, dtype=np.uint32).tofile(os.path.join(d, "scales.bin"))
+    with pytest.raises(ValueError, match="not interchangeable"):
+        EntropyCodingCompression().decompress(d)
