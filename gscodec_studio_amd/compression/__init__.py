@@ -7,7 +7,11 @@
   (``decode_to_rasterizer_inputs``), the K-means codebook of the higher SH bands (``kmeans_decode`` bit-exact against the
   reference's ``_decompress_kmeans``; ``kmeans_encode`` = seeded Lloyd iteration writing the same format), and the splat
   ordering in front of the grid codec (``sort_splats`` = PLAS, an external package as in the reference; ``morton_order`` =
-  deterministic substitute).
+  deterministic substitute on the means alone).
+* ``grid_sort``: ``grid_sort_order`` / ``sort_splats_grid``, the ordering over EVERY attribute that PLAS stands for, as the
+  library's own integer algorithm on the GPU (csrc/grid_sort.hip: box blur, random groups through the radix sort, best-of-24
+  assignment), defined by the numpy code ``grid_sort_reference`` that the kernels match element for element;
+  ``use_sort="grid"`` of the two codecs below.
 
 * ``png_compression``: the file level -- ``PngCompression.compress(dir, splats)`` / ``decompress(dir)`` with the reference's
   directory layout (PNG image grids, ``shN.npz`` + ``mask.bin``, ``meta.json``) and a self-contained 8-bit PNG reader /
@@ -22,6 +26,7 @@ from .decode import decode_to_rasterizer_inputs, kmeans_decode, kmeans_encode, m
 from .png_compression import PngCompression, png_read, png_write
 from .ans import ans_decode, ans_encode, normalize_frequencies, symbol_histogram
 from .entropy_coding_compression import EntropyCodingCompression
+from .grid_sort import grid_sort_order, sort_splats_grid
 from .grid_codec import (
     compress_to_arrays,
     decompress_from_arrays,
@@ -34,4 +39,4 @@ from .grid_codec import (
 __all__ = ["quantize_grid", "dequantize_grid", "compress_to_arrays", "decompress_from_arrays", "log_transform",
            "inverse_log_transform", "decode_to_rasterizer_inputs", "kmeans_decode", "kmeans_encode", "morton_order",
            "sort_splats", "reorder_splats", "PngCompression", "png_read", "png_write", "EntropyCodingCompression", "ans_encode",
-           "ans_decode", "normalize_frequencies", "symbol_histogram"]
+           "ans_decode", "normalize_frequencies", "symbol_histogram", "grid_sort_order", "sort_splats_grid"]

@@ -121,7 +121,8 @@ _AVAILABLE = {fn.__name__: fn for fn in (
 class EntropyCodingCompression:
     """The reference's ``EntropyCodingCompression``: same fields, same files (see the module docstring for the one difference,
     the payload of the ``.bin`` files).  ``use_sort`` as in ``PngCompression`` here: True = PLAS (external package, ImportError
-    without it), "morton" = the deterministic Morton order, False = keep the order.  ``attribute_codec_registry`` maps an
+    without it), "morton" = the deterministic Morton order, "grid" = the library's grid sort, False = keep the order.
+    ``attribute_codec_registry`` maps an
     attribute to ``{"encode": <name>, "decode": <name>}`` with the reference's function names as strings, e.g.
     ``{"scales": {"encode": "_compress_png", "decode": "_decompress_png"}}``.  Works on detached copies; the caller's dictionary
     is not written to.  A channel with ``maxs == mins`` is coded as symbol 0 and decodes to ``mins``."""

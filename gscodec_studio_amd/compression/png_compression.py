@@ -17,7 +17,8 @@ of ``grid_codec`` / ``decode``; this module is the container around them:
   sections 5, 9, 10).  Reading undoes all five filter types (the sequential part is ``gs_png_unfilter`` of the library);
   writing picks None / Sub / Up per row by the usual minimum-sum-of-absolute-differences heuristic.
 * the splat ordering is the one piece that needs an external package in the reference too (``plas``): ``use_sort=True``
-  calls it and raises ImportError without it, ``use_sort="morton"`` uses the deterministic Morton order instead.
+  calls it and raises ImportError without it, ``use_sort="morton"`` uses the deterministic Morton order of the means instead,
+  and ``use_sort="grid"`` the library's own grid sort over every attribute (``grid_sort``, csrc/grid_sort.hip).
 """
 from __future__ import annotations
 
@@ -34,6 +35,7 @@ from torch import Tensor
 
 from .. import _backend as B
 from .decode import kmeans_decode, kmeans_encode, morton_order, sort_splats
+from .grid_sort import sort_splats_grid
 from .grid_codec import ATTRIBUTE_CODECS, _crop_to_square, dequantize_grid, inverse_log_transform, log_transform, quantize_grid
 
 _PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
@@ -114,7 +116,8 @@ def prepare_splats(splats: Dict[str, Tensor], opacity_threshold: float, use_sort
                    ) -> Tuple[Dict[str, Tensor], int]:
     """What the reference's compress() does in front of the per-attribute codecs (png_compression.py:101-125), on detached
     copies: the opacity filter, the log transform of the means, the normalised quats, the crop to a square count and the
-    ordering (``use_sort``: True = PLAS, "morton" = morton_order, False = none).  Returns (splats, side length)."""
+    ordering (``use_sort``: True = PLAS, "morton" = morton_order, "grid" = sort_splats_grid, False = none).  Returns (splats,
+    side length)."""
     splats = {k: v.detach() for k, v in splats.items()}
     keep = torch.sigmoid(splats["opacities"]) >= opacity_threshold
     splats = {k: v[keep] for k, v in splats.items()}
@@ -127,6 +130,8 @@ def prepare_splats(splats: Dict[str, Tensor], opacity_threshold: float, use_sort
     if use_sort == "morton":
         order = morton_order(splats["means"])
         splats = {k: v[order] for k, v in splats.items()}
+    elif use_sort == "grid":
+        splats = sort_splats_grid(splats, verbose=verbose)
     elif use_sort:
         splats = sort_splats(splats, verbose=verbose)
     return splats, side
@@ -163,7 +168,8 @@ def decompress_masked_kmeans(compress_dir: str, param_name: str, m: Dict[str, An
 @dataclass
 class PngCompression:
     """The reference's ``PngCompression`` (same constructor arguments, same files).  ``use_sort``: True = PLAS (external
-    package, as in the reference), "morton" = the deterministic Morton order, False = keep the order."""
+    package, as in the reference), "morton" = the deterministic Morton order, "grid" = the library's grid sort, False = keep
+    the order."""
 
     use_sort: Union[bool, str] = True
     verbose: bool = True

@@ -44,7 +44,8 @@ extern "C" {
  * densification-strategy entries (gs_relocation, gs_inject_noise, gs_densify_stats) are additive in the same way, and so are
  * the two of the spacetime strategies (gs_stg_omega_mask, gs_stg_freeze_grads), and the bilateral-grid entries
  * (gs_bilagrid_slice_fwd / _bwd, gs_bilagrid_tv_fwd / _bwd, gs_bilagrid_tv_work_bytes), and the entropy-coder entries
- * (gs_ans_histogram, gs_ans_encode_bytes, gs_ans_encode, gs_ans_pack, gs_ans_decode). */
+ * (gs_ans_histogram, gs_ans_encode_bytes, gs_ans_encode, gs_ans_pack, gs_ans_decode), and the grid-sort entries
+ * (gs_gridsort_blur, gs_gridsort_keys, gs_gridsort_assign). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -886,6 +887,31 @@ int32_t gs_ans_pack(uint64_t n_streams_total, uint32_t S, uint32_t P, const uint
                     const uint32_t *states, const int64_t *offsets, uint8_t *payload, uint64_t payload_bytes, gs_stream_t stream);
 int32_t gs_ans_decode(uint64_t N, uint32_t C, uint32_t S, uint32_t P, const uint8_t *payload, uint64_t payload_bytes,
                       const int64_t *offsets, const uint32_t *freq, const uint32_t *cum, uint8_t *symbols, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Grid sort (grid_sort.hip): the order of the splats on the S x S image grid of the PNG codecs that makes every attribute image
+ * smooth -- the role of the `plas` package in the reference (gsplat/compression/sort.py), as an algorithm of this project's own
+ * whose definition is the numpy code gscodec_studio_amd/compression/grid_sort_reference.py.  Integer arithmetic only: the
+ * kernels' results equal the reference's element for element.  N = S * S < 2^31, 1 <= C <= 64 channels of 12-bit features
+ * q uint16 [N, C] (values <= 4095); order int32 [N]: order[p] = the splat at grid position p = y * S + x.  One round is
+ * gs_gridsort_blur -> gs_gridsort_keys -> gs_sort_pairs_u64_i32 over bits [0, 32 + bits of the largest block id) ->
+ * gs_gridsort_assign; every launch goes to `stream`, nothing waits on the host.
+ *
+ * gs_gridsort_blur: target[p] = the box blur of width 2 r + 1 (1 <= r < S, reflect borders) of the grid q[order[.]], rows
+ *   first (into tmp), then columns, each pass an exact integer window sum s followed by (2 s + w) / (2 w).  tmp and target:
+ *   uint16 [N, C].  One sliding window per (line, channel, segment of at most 128 outputs).
+ * gs_gridsort_keys: keys[p] = block(p) << 32 | hash(seed, k, p), vals[p] = p.  Block side b >= 1, shifted by
+ *   (hash(seed, k, N) % b, hash(seed, k, N + 1) % b): block(p) = ((y + oy) / b) (S / b + 2) + (x + ox) / b.  b = 0: no blocks,
+ *   the key is the hash alone (the start order).
+ * gs_gridsort_assign: one lane per run of four sorted positions.  Four positions of one block: the first of the 24
+ *   permutations in lexicographic order whose sum of squared distances between the four items q[order_in[.]] and the four
+ *   targets is least moves item i to position perm[i] of the run; any other run (and the trailing N % 4 positions) keeps its
+ *   entries.  order_out (must not alias order_in) receives every position exactly once. */
+int32_t gs_gridsort_blur(uint32_t S, uint32_t C, uint32_t r, const uint16_t *q, const int32_t *order, uint16_t *tmp,
+                         uint16_t *target, gs_stream_t stream);
+int32_t gs_gridsort_keys(uint32_t S, uint32_t b, uint32_t seed, uint32_t k, int64_t *keys, int32_t *vals, gs_stream_t stream);
+int32_t gs_gridsort_assign(uint32_t S, uint32_t C, const uint16_t *q, const uint16_t *target, const int64_t *sorted_keys,
+                           const int32_t *sorted_pos, const int32_t *order_in, int32_t *order_out, gs_stream_t stream);
 
 
 /* ------------------------------------------------------------------------
