@@ -6,7 +6,9 @@ Public surface (mirrors the reference's ``gsplat`` package for this path only):
   ``optimizers.{Adam, SelectiveAdam, step_all, visibility_mask}`` and ``losses.{fused_ssim, photometric_loss}`` and
   ``strategy.{Strategy, DefaultStrategy, MCMCStrategy, STG_Strategy, Modified_STG_Strategy}`` (``from gscodec_studio_amd.strategy import ...``, as in the reference) with
   ``relocation.compute_relocation``, and ``bilagrid.{BilateralGrid, slice, slice_image, total_variation_loss,
-  color_affine_transform}`` (``from gscodec_studio_amd.bilagrid import ...`` in place of ``from lib_bilagrid import ...``).
+  color_affine_transform}`` (``from gscodec_studio_amd.bilagrid import ...`` in place of ``from lib_bilagrid import ...``), and the 2D Gaussian splatting
+  renderer ``rasterization_2dgs`` with its operators ``fully_fused_projection_2dgs`` / ``rasterize_to_pixels_2dgs`` (``surfel.py``) and
+  ``utils.{depth_to_points, depth_to_normal}``.
 """
 from ._wrapper import (
     accumulate,
@@ -23,7 +25,9 @@ from ._wrapper import (
     spherical_harmonics_shared,
     world_to_cam,
 )
-from .rendering import rasterization
+from .rendering import rasterization, rasterization_2dgs
+from .surfel import fully_fused_projection_2dgs, rasterize_to_pixels_2dgs
+from . import utils
 from .version import __version__
 
 
@@ -39,4 +43,5 @@ __all__ = [
     "rasterization", "fully_fused_projection", "spherical_harmonics", "spherical_harmonics_shared",
     "isect_tiles", "isect_offset_encode", "rasterize_to_pixels", "quat_scale_to_covar_preci", "proj", "persp_proj",
     "world_to_cam", "rasterize_to_indices_in_range", "accumulate", "selective_adam_update", "PngCompression", "__version__",
+    "rasterization_2dgs", "fully_fused_projection_2dgs", "rasterize_to_pixels_2dgs", "utils",
 ]

@@ -512,3 +512,152 @@ def rasterization(
         render_colors = _expected_depth(render_colors, render_alphas)
 
     return render_colors, render_alphas, meta
+
+
+###### 2DGS ######
+def _affine_inverse(viewmats: Tensor) -> Tensor:
+    """``inverse(viewmats)`` for affine ``[[A, t], [0, 1]]`` matrices in closed form (adjugate / determinant): a few tiny
+    asynchronous kernels, differentiable, instead of ``torch.linalg.inv``'s batched LU with its host-side status check."""
+    A, t = viewmats[..., :3, :3], viewmats[..., :3, 3]
+    c0, c1, c2 = A[..., :, 0], A[..., :, 1], A[..., :, 2]
+    inv = torch.stack([torch.linalg.cross(c1, c2), torch.linalg.cross(c2, c0), torch.linalg.cross(c0, c1)], dim=-2)
+    inv = inv / (c0 * inv[..., 0, :]).sum(-1)[..., None, None]
+    out = torch.zeros_like(viewmats)
+    out[..., :3, :3] = inv
+    out[..., :3, 3] = -(inv @ t[..., None])[..., 0]
+    out[..., 3, 3] = 1.0
+    return out
+
+
+def rasterization_2dgs(
+    means: Tensor,  # [N, 3]
+    quats: Tensor,  # [N, 4]
+    scales: Tensor,  # [N, 3]
+    opacities: Tensor,  # [N]
+    colors: Tensor,  # [(C,) N, D] or [N, K, 3]
+    viewmats: Tensor,  # [C, 4, 4]
+    Ks: Tensor,  # [C, 3, 3]
+    width: int,
+    height: int,
+    near_plane: float = 0.01,
+    far_plane: float = 1e10,
+    radius_clip: float = 0.0,
+    eps2d: float = 0.3,
+    sh_degree: Optional[int] = None,
+    packed: bool = False,
+    tile_size: int = 16,
+    backgrounds: Optional[Tensor] = None,
+    render_mode: Literal["RGB", "D", "ED", "RGB+D", "RGB+ED"] = "RGB",
+    sparse_grad: bool = False,
+    absgrad: bool = False,
+    distloss: bool = False,
+    depth_mode: Literal["expected", "median"] = "expected",
+) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Dict]:
+    """Rasterize a set of 2D Gaussians (N) to a batch of image planes (C): the reference's
+    ``gsplat.rendering.rasterization_2dgs`` (rendering.py:1002-1321) -- same parameters, defaults, asserts and return order --
+    on the HIP operators of ``surfel.py``: project -> tile-intersect + radix sort -> offset-encode -> SH colour -> per-tile
+    compositing -> (expected depth) -> normals from depth.
+
+    Returns ``(render_colors [C,H,W,X], render_alphas [C,H,W,1], render_normals [C,H,W,3] (rotated to world space),
+    render_normals_from_depth [C,H,W,3] (``None`` unless the mode is "RGB+D" or "RGB+ED"), render_distort [C,H,W,1],
+    render_median [C,H,W,1], meta)``.  ``meta`` has the reference's keys, ``ray_transforms``, ``normals``, ``render_distort`` and
+    ``gradient_2dgs`` included; ``meta["gradient_2dgs"]`` is what ``DefaultStrategy(key_for_gradient="gradient_2dgs")`` reads, and
+    ``meta["means2d"].absgrad`` is set by the backward with ``absgrad=True`` (``gradient_2dgs`` gets no ``.absgrad``, as in the
+    reference).  "ED" normalises the accumulated depth by ``alphas.clamp(min=1e-10)``.  ``distloss`` needs a depth mode.
+
+    ``backgrounds`` is ``[C, D]`` for the colour channels; in the depth modes the depth channel's background is zero (a
+    ``[C, X]`` tensor that already covers every rendered channel is taken as it is).
+
+    One deliberate difference: ``gradient_2dgs.grad[c, n] = (v_ray_transforms[c, n, 0, 2], v_ray_transforms[c, n, 1, 2]) *
+    depths[c, n]`` is formed from the FINAL gradient sums; the reference reads them inside its backward kernel while other
+    workgroups are still adding (a race).  The normals from depth get their gradient through the depth map only.
+
+    Not in this version (``NotImplementedError`` before any launch): ``packed=True`` and ``sparse_grad=True``, more than 4
+    channels after the depth column is appended, ``tile_size != 16``.  There is no CPU path.
+    """
+    from . import surfel
+    from ._wrapper import _require_gpu
+
+    N = means.shape[0]
+    C = viewmats.shape[0]
+    assert means.shape == (N, 3), means.shape
+    assert quats.shape == (N, 4), quats.shape
+    assert scales.shape == (N, 3), scales.shape
+    assert opacities.shape == (N,), opacities.shape
+    assert viewmats.shape == (C, 4, 4), viewmats.shape
+    assert Ks.shape == (C, 3, 3), Ks.shape
+    assert render_mode in ["RGB", "D", "ED", "RGB+D", "RGB+ED"], render_mode
+    assert depth_mode in ["expected", "median"], depth_mode
+    if distloss:
+        assert render_mode in ["D", "ED", "RGB+D", "RGB+ED"], \
+            f"distloss requires depth rendering, render_mode should be D, ED, RGB+D, RGB+ED, but got {render_mode}"
+    if sh_degree is None:
+        # post-activation values [N, D] or [C, N, D]
+        assert (colors.dim() == 2 and colors.shape[0] == N) or (colors.dim() == 3 and colors.shape[:2] == (C, N)), colors.shape
+        D = colors.shape[-1]
+    else:
+        # SH coefficients [N, K, 3]; partial bands allowed
+        assert colors.dim() == 3 and colors.shape[0] == N and colors.shape[2] == 3, colors.shape
+        assert (sh_degree + 1) ** 2 <= colors.shape[1], colors.shape
+        D = 3
+    channels = {"RGB": D, "D": 1, "ED": 1}.get(render_mode, D + 1)
+    surfel.check_unpacked("rasterization_2dgs", packed, sparse_grad)
+    surfel.check_tile_size("rasterization_2dgs", tile_size)
+    surfel.check_channels("rasterization_2dgs", channels)
+    assert C > 0, "rasterization_2dgs needs at least one camera"
+    for t in (means, quats, scales, opacities, colors, viewmats, Ks):
+        _require_gpu(t, "rasterization_2dgs")
+
+    if backgrounds is not None and backgrounds.shape[-1] != channels:
+        assert render_mode != "RGB" and backgrounds.shape == (C, channels - 1), backgrounds.shape
+        backgrounds = torch.cat([backgrounds, torch.zeros(C, 1, dtype=backgrounds.dtype, device=backgrounds.device)], dim=-1)
+
+    radii, means2d, depths, ray_transforms, normals = surfel.fully_fused_projection_2dgs(
+        means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane, radius_clip, packed, sparse_grad)
+    opacities = opacities.repeat(C, 1)  # [C, N]
+    densify = torch.zeros_like(means2d, requires_grad=True)
+
+    tile_width = math.ceil(width / float(tile_size))
+    tile_height = math.ceil(height / float(tile_size))
+    # binning is split around its one host wait (the intersection count): the colour evaluation is queued in between
+    isect_state = isect_tiles_begin(means2d, radii, depths, tile_size, tile_width, tile_height, True, C, N, int(radii.numel()), None)
+
+    try:
+        if sh_degree is not None:
+            if viewmats.requires_grad:  # (the fused colour kernel has no gradient for the camera centres)
+                dirs = means[None, :, :] - _camera_centers(viewmats)[:, None, :]
+                colors = torch.clamp_min(spherical_harmonics_shared(sh_degree, dirs, colors, masks=radii > 0) + 0.5, 0.0)
+            else:
+                colors = spherical_harmonics_view(sh_degree, means, viewmats, colors, radii)  # [C, N, 3], clamp_min(. + 0.5, 0) included
+        elif colors.dim() == 2:
+            colors = colors.expand(C, -1, -1)
+    except BaseException:  # (the count kernel still stores into the state's pinned buffer: wait before it is recycled)
+        isect_tiles_abandon(isect_state)
+        raise
+
+    if render_mode in ["RGB+D", "RGB+ED"]:
+        colors = torch.cat((colors, depths[..., None]), dim=-1)
+    elif render_mode in ["D", "ED"]:
+        colors = depths[..., None]
+
+    tiles_per_gauss, isect_ids, flatten_ids, isect_offsets = isect_tiles_finish(isect_state, offsets_for=C)
+
+    render_colors, render_alphas, render_normals, render_distort, render_median = surfel.rasterize_to_pixels_2dgs(
+        means2d, ray_transforms, colors, opacities, normals, densify, width, height, tile_size, isect_offsets, flatten_ids,
+        backgrounds=backgrounds, packed=packed, absgrad=absgrad, distloss=distloss)
+
+    if render_mode in ["ED", "RGB+ED"]:
+        render_colors = _expected_depth(render_colors, render_alphas)
+    camtoworlds = _affine_inverse(viewmats)
+    render_normals_from_depth = None
+    if render_mode in ["RGB+ED", "RGB+D"]:
+        depth_for_normal = render_colors[..., -1:] if depth_mode == "expected" else render_median
+        render_normals_from_depth = surfel.depth_to_normal(depth_for_normal, camtoworlds, Ks)
+
+    meta = {"camera_ids": None, "gaussian_ids": None, "radii": radii, "means2d": means2d, "depths": depths,
+            "ray_transforms": ray_transforms, "opacities": opacities, "normals": normals}
+    meta.update(binning_meta(tile_size, tile_width, tile_height, tiles_per_gauss, isect_ids, flatten_ids, isect_offsets, width, height, C))
+    meta.update({"render_distort": render_distort, "gradient_2dgs": densify})
+
+    render_normals = torch.einsum("...ij,...hwj->...hwi", camtoworlds[..., :3, :3], render_normals)
+    return render_colors, render_alphas, render_normals, render_normals_from_depth, render_distort, render_median, meta

@@ -45,7 +45,8 @@ extern "C" {
  * the two of the spacetime strategies (gs_stg_omega_mask, gs_stg_freeze_grads), and the bilateral-grid entries
  * (gs_bilagrid_slice_fwd / _bwd, gs_bilagrid_tv_fwd / _bwd, gs_bilagrid_tv_work_bytes), and the entropy-coder entries
  * (gs_ans_histogram, gs_ans_encode_bytes, gs_ans_encode, gs_ans_pack, gs_ans_decode), and the grid-sort entries
- * (gs_gridsort_blur, gs_gridsort_keys, gs_gridsort_assign). */
+ * (gs_gridsort_blur, gs_gridsort_keys, gs_gridsort_assign), and the 2D Gaussian splatting entries (gs_projection_2dgs_fwd / _bwd,
+ * gs_rasterize_2dgs_fwd / _bwd, gs_depth_to_normal_fwd / _bwd). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -1339,6 +1340,68 @@ uint32_t gs_step_layout(uint64_t *out, uint32_t n);
 uint32_t gs_quant_desc_layout(uint64_t *out, uint32_t n);
 int32_t gs_step_fwd_begin(gs_step *step, gs_stream_t stream);
 int32_t gs_step_fwd_finish(gs_step *step, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * 2D Gaussian splatting (surfels): the operators behind rasterization_2dgs (reference gsplat/rendering.py:1002-1321,
+ * csrc/fully_fused_projection_2dgs_*.cu, csrc/rasterize_to_pixels_2dgs_*.cu).  Unpacked layout only: a splat is the flat
+ * index c * N + n.  fp32, contiguous, no host synchronisation; C == 0 or N == 0 is a no-op that returns success.
+ *
+ * gs_projection_2dgs_fwd: per (camera, splat) the ray transform M = K [R q_x s_x | R q_y s_y | mean_c] (row-major 3x3: rows
+ *   M_u, M_v, M_w), its screen-space centre and radius, the depth mean_c.z and the camera-space normal (third column of
+ *   R rot(q), flipped to face the camera).  Culled splats (z outside [near, far], M_w,x^2 + M_w,y^2 - M_w,z^2 == 0,
+ *   radius <= radius_clip, box outside the image) get radii = 0 and zeros in the other outputs.  eps2d is accepted and
+ *   unused, as in the reference.
+ * gs_projection_2dgs_bwd: ADDS into v_means [N,3], v_quats [N,4], v_scales [N,3] (component 2 is never touched) and, when
+ *   given, v_viewmats [C,4,4] (rows 0..2; summed per wave, one atomic per wave and value): the caller zeroes them.  Any of
+ *   v_means2d / v_depths / v_normals / v_ray_transforms may be NULL (no gradient arrived); no gradient for Ks.
+ *
+ * gs_rasterize_2dgs_fwd: one 256-lane workgroup per 16x16 tile composites its list front to back (channels in 1..4; the LAST
+ *   colour channel is what distortion and median depth read).  Per (pixel, splat): h_u = px M_w - M_u, h_v = py M_w - M_v,
+ *   zeta = h_u x h_v (skipped when zeta_z == 0), s = zeta_xy / zeta_z, weight = min(s.s, 2 |mean2d - p|^2),
+ *   alpha = min(0.999, o exp(-weight / 2)); alpha < 1/255 is skipped; the pixel stops before the splat that would bring
+ *   T (1 - alpha) <= 1e-4.  Outputs: colours + T background, alphas, camera-space normals, the distortion
+ *   sum 2 (w d (1 - T) - w sum_prev w d) (zeros unless distloss), the median depth (last channel of the last contributing
+ *   splat reached with T > 0.5; 0 when there is none), and last_ids / median_ids i32 [C,H,W] (indices into flatten_ids, -1:
+ *   none) for the backward.  masks (uint8 [C, tile_height, tile_width], optional): tiles with 0 get the background and zeros.
+ * gs_rasterize_2dgs_bwd: walks each tile back to front from its last_ids and ADDS (one atomic per wave and value, from waves
+ *   with a contributing lane) into v_means2d [C N,2], v_means2d_abs (optional), v_ray_transforms [C N,9], v_colors
+ *   [C N,channels], v_opacities [C N], v_normals [C N,3]: the caller zeroes them.  Geometry and opacity get nothing where
+ *   o exp(-weight / 2) > 0.999.  v_render_distort is read only with distloss; NULL v_render_* mean zero. */
+int32_t gs_projection_2dgs_fwd(uint32_t C, uint32_t N, const float *means, const float *quats, const float *scales,
+                               const float *viewmats, const float *Ks, int32_t width, int32_t height, float eps2d,
+                               float near_plane, float far_plane, float radius_clip, int32_t *radii, float *means2d,
+                               float *depths, float *ray_transforms, float *normals, gs_stream_t stream);
+int32_t gs_projection_2dgs_bwd(uint32_t C, uint32_t N, const float *means, const float *quats, const float *scales,
+                               const float *viewmats, const float *Ks, const int32_t *radii, const float *ray_transforms,
+                               const float *v_means2d, const float *v_depths, const float *v_normals,
+                               const float *v_ray_transforms, float *v_means, float *v_quats, float *v_scales,
+                               float *v_viewmats, gs_stream_t stream);
+int32_t gs_rasterize_2dgs_fwd(uint32_t C, uint32_t N, uint32_t n_isects, uint32_t channels, const float *means2d,
+                              const float *ray_transforms, const float *colors, const float *opacities, const float *normals,
+                              const float *backgrounds, const uint8_t *masks, uint32_t width, uint32_t height,
+                              uint32_t tile_size, uint32_t tile_width, uint32_t tile_height, const int32_t *tile_offsets,
+                              const int32_t *flatten_ids, int32_t distloss, float *render_colors, float *render_alphas,
+                              float *render_normals, float *render_distort, float *render_median, int32_t *last_ids,
+                              int32_t *median_ids, gs_stream_t stream);
+int32_t gs_rasterize_2dgs_bwd(uint32_t C, uint32_t N, uint32_t n_isects, uint32_t channels, const float *means2d,
+                              const float *ray_transforms, const float *colors, const float *opacities, const float *normals,
+                              const float *backgrounds, const uint8_t *masks, uint32_t width, uint32_t height,
+                              uint32_t tile_size, uint32_t tile_width, uint32_t tile_height, const int32_t *tile_offsets,
+                              const int32_t *flatten_ids, int32_t distloss, const float *render_colors,
+                              const float *render_alphas, const int32_t *last_ids, const int32_t *median_ids,
+                              const float *v_render_colors, const float *v_render_alphas, const float *v_render_normals,
+                              const float *v_render_distort, const float *v_render_median, float *v_means2d,
+                              float *v_means2d_abs, float *v_ray_transforms, float *v_colors, float *v_opacities,
+                              float *v_normals, gs_stream_t stream);
+/* Surface normals of a depth map (reference gsplat/utils.py:108-131): points = origin + depth * direction per pixel
+ * (direction = camtoworld rotation applied to ((j + 0.5 - cx) / fx, (i + 0.5 - cy) / fy, 1), normalised unless z_depth),
+ * normal = normalize((P[i+1,j] - P[i-1,j]) x (P[i,j+1] - P[i,j-1])) with F.normalize's eps 1e-12, zero on the border.
+ * depths [B,H,W], camtoworlds [B,4,4], Ks [B,3,3] -> normals [B,H,W,3], every pixel written.  The backward is a gather (each
+ * depth reads the <= 4 normals it took part in): v_depths [B,H,W] is overwritten, no atomics. */
+int32_t gs_depth_to_normal_fwd(uint32_t B, uint32_t H, uint32_t W, const float *depths, const float *camtoworlds,
+                               const float *Ks, int32_t z_depth, float *normals, gs_stream_t stream);
+int32_t gs_depth_to_normal_bwd(uint32_t B, uint32_t H, uint32_t W, const float *depths, const float *camtoworlds,
+                               const float *Ks, int32_t z_depth, const float *v_normals, float *v_depths, gs_stream_t stream);
 
 #ifdef __cplusplus
 }
