@@ -3,13 +3,14 @@ immutable record every later branch reads.  ``rendering._facts`` reads the facts
 package asks again whether the batch is unpacked, on one GPU, on the device, with fixed poses.
 
 The A/B switches are module attributes read at call time (tests flip them): ``_step.ENABLED`` (GS_STEP_DRIVER),
-``_wrapper.PREFILL_ENABLED`` (GS_GRAD_PREFILL), ``_wrapper._PINNED_DIRECT_MAX``; ``_wrapper._FUSE_SH_BWD`` (GS_FUSE_SH_BWD)
+``_wrapper.PREFILL_ENABLED`` (GS_GRAD_PREFILL), ``_readback._PINNED_DIRECT_MAX``; ``_wrapper._FUSE_SH_BWD`` (GS_FUSE_SH_BWD)
 and ``distributed.sparse_enabled`` (GS_DIST_SPARSE) reach this module as the facts ``sh_bwd_fusable`` and ``sparse_enabled``."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
 
 from . import _step, _wrapper
+from ._readback import direct_block_sums
 
 
 class Route(NamedTuple):
@@ -29,12 +30,6 @@ class Route(NamedTuple):
     sh_op: Optional[str]  # who evaluates SH colours: None | "projection" | "view" | "shared" | "per_view" | "packed"
     depth_view: bool  # RGB+D / RGB+ED: colour + depth are the view rows[..., 6:10] (else a cat)
     rows_begin: bool  # receiver side of the row exchange: binning + compositing by _step.rows_begin (else isect_tiles_start)
-
-
-def direct_block_sums(n_elems: int) -> bool:
-    """The count kernel's block sums go straight into pinned memory up to this size (one block per 1024 elements; beyond it
-    tens of thousands of direct PCIe stores stalled the GPU for ~85 ms on some forwards): what both uses of the step driver need."""
-    return 0 < n_elems <= _wrapper._PINNED_DIRECT_MAX * 1024
 
 
 def route(*, packed: bool, distributed: bool, sparse_enabled: bool, on_device: bool, pose_grads: bool, camera_grads: bool, means_grad: bool,

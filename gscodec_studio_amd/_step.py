@@ -27,6 +27,7 @@ import torch
 from torch import Tensor
 
 from . import _backend as B
+from . import _readback as RB
 from . import _wrapper as W
 
 ENABLED = os.environ.get("GS_STEP_DRIVER", "1") != "0"
@@ -128,49 +129,26 @@ def _phase1(s: "_Step", C: int, N: int, dev, n_sums: int, given=None) -> dict:
         sb1 = B.query("gs_cumsum_scratch_bytes", n_groups)
         scratch1 = empty(sb1, dtype=u8, device=dev)
         s.cumsum_scratch, s.cumsum_scratch_bytes = ptr(scratch1), sb1
-    pinned = W._pinned_take(2 * n_sums)  # [n_sums][2]: (intersections, visible elements) per block
+    sums = RB.BlockSums.stored(n_sums, torch.cuda.current_stream(dev))  # (the stream its kernel is queued on: what the wait watches)
     s.radii, s.depths, s.rows, s.tiles_per_gauss = ptr(radii), ptr(depths), ptr(rows), ptr(tiles_per_gauss)
     s.depth_keys, s.depth_vals, s.sort_temp, s.sort_temp_bytes = ptr(dkeys), ptr(dvals), ptr(temp), tb
     s.splitters, s.sorted_keys, s.perm, s.n_kept, s.group_sums, s.group_prefix = ptr(split), ptr(ko), ptr(perm), ptr(n_kept), ptr(gsums), ptr(gpre)
-    s.block_sums = pinned.data_ptr()
+    s.block_sums = sums.buf.data_ptr()
     s.bucketed, s.lds_capacity = int(bucketed), W._PRESORT["lds_capacity"]
     # (the dict keeps every buffer alive until the forward's launches are queued)
-    return {"radii": radii, "depths": depths, "rows": rows, "tiles_per_gauss": tiles_per_gauss, "pinned": pinned,
+    return {"radii": radii, "depths": depths, "rows": rows, "tiles_per_gauss": tiles_per_gauss, "sums": sums,
             "keep": (dkeys, dvals, perm, n_kept, gsums, temp, split, ko, gpre, scratch1)}
 
 
-_LEAKED: list = []  # pinned buffers a kernel may still write to (never handed back: see _drop_pinned)
-
-
-def _drop_pinned(bufs: Optional[dict], n_sums: int) -> None:
-    """Give the pinned block-sum buffer of an abandoned forward back.  The count kernel stores into it from the GPU and torch's
-    pinned allocator does not see kernel stores: the buffer may only be reused once every sum has landed -- bounded wait, and
-    if the kernel never gets there (a failed launch in front of it) the buffer is kept alive for good instead."""
-    if not bufs or bufs.get("pinned") is None:
-        return
-    import time
-
-    pinned, bufs["pinned"] = bufs["pinned"], None
-    ev = W._SentinelEvent(pinned)
-    deadline = time.perf_counter() + 1.0
-    while not ev.query():
-        if time.perf_counter() > deadline:
-            _LEAKED.append(pinned)
-            return
-        time.sleep(0)
-    W._PINNED_FREE.setdefault(2 * n_sums, []).append(pinned)
-
-
-def _finish(s, sp, stream, bufs, n_sums, C, N, height, width, tile_height, tile_width, dev, needs_bwd, prefill):
+def _finish(s, sp, stream, bufs, C, N, height, width, tile_height, tile_width, dev, needs_bwd, prefill):
     """From behind ``gs_step_fwd_begin`` to the compositing launch: the one host sync and both ``gs_step_fwd_finish`` phases."""
     i32, i64, f32, u8 = torch.int32, torch.int64, torch.float32, torch.uint8
     empty = torch.empty
     ptr = B.ptr
     n_elems = C * N
-    pinned = bufs["pinned"]
+    sums = bufs["sums"]
     offsets = empty((C, tile_height, tile_width), dtype=i32, device=dev)
     s.offsets = ptr(offsets)
-    sentinel = W._SentinelEvent(pinned, stream=torch.cuda.current_stream(dev))  # (the launch stream: what the wait watches for faults)
     # The phase-2 buffers are sized by n_isects, which only the read-back below delivers -- and everything the host does between the
     # read-back and the binning launch is time the GPU may spend idle (round 6, tools/host_timeline.py: three allocations, a size query
     # and the descriptor fields took 46 us there against the ~56 us of pre-sort the GPU still has when the sums land; 12-17 us of idle
@@ -188,8 +166,7 @@ def _finish(s, sp, stream, bufs, n_sums, C, N, height, width, tile_height, tile_
         s.isect_ids, s.flatten_ids, s.work, s.work_bytes = ptr(ids_buf), ptr(flat_buf), ptr(work), wb
     # ---- the one host sync: the count kernel's block sums land in pinned memory (-1 -> >= 0).  From here to the
     # binning launches the GPU has ~40 us of pre-sort left
-    W._wait_event(sentinel)
-    n_isects, n_kept_host = W.block_sum_totals(sentinel.np)
+    n_isects, n_kept_host = sums.wait()
     s.n_kept_host = n_kept_host if W._PACKED_PAIRS else 0
     s.n_isects = n_isects
     if ids_buf is None or n_isects > cap:
@@ -205,8 +182,7 @@ def _finish(s, sp, stream, bufs, n_sums, C, N, height, width, tile_height, tile_
     isect_ids = ids_buf if ids_buf.shape[0] == n_isects else ids_buf[:n_isects]
     flatten_ids = flat_buf if flat_buf.shape[0] == n_isects else flat_buf[:n_isects]
     _ISECT_CAP[key] = n_isects + (n_isects >> 5) + 4096
-    W._PINNED_FREE.setdefault(2 * n_sums, []).append(pinned)
-    bufs["pinned"] = None
+    sums.release()
     # ---- the compositing buffers (made while the GPU is busy with the binning)
     render_colors = empty((C, height, width, 3), dtype=f32, device=dev)
     render_alphas = empty((C, height, width, 1), dtype=f32, device=dev)
@@ -282,14 +258,10 @@ class _StepProject(torch.autograd.Function):
             prefill = W.GradPrefill()
             prefill.request = W.prefill_request(W._prefill_table(W._needs(ctx, _StepProject.INPUTS), means, covars, quats, scales, opacities,
                                                                  colors, sh_coeffs, sh_rest, dyn_ctx))
-        try:
-            with torch.cuda.device(dev):
-                B.call("gs_step_fwd_begin", sp, stream)
-                (offsets, isect_ids, flatten_ids, render_colors, render_alphas, last_ids, grad_rows, prefill, scratch, plan) = _finish(
-                    s, sp, stream, bufs, n_sums, C, N, height, width, tile_height, tile_width, dev, needs_bwd, prefill)
-        except BaseException:
-            _drop_pinned(bufs, n_sums)  # (an error between the two calls: the count kernel may still be storing into it)
-            raise
+        with torch.cuda.device(dev):
+            B.call("gs_step_fwd_begin", sp, stream)
+            (offsets, isect_ids, flatten_ids, render_colors, render_alphas, last_ids, grad_rows, prefill, scratch, plan) = _finish(
+                s, sp, stream, bufs, C, N, height, width, tile_height, tile_width, dev, needs_bwd, prefill)
         # ---- node 2's share
         hand.render_colors, hand.render_alphas, hand.last_ids, hand.scratch, hand.plan = render_colors, render_alphas, last_ids, scratch, plan
         hand.grad_rows, hand.offsets, hand.flatten_ids = grad_rows, offsets, flatten_ids
@@ -327,13 +299,7 @@ class _StepComposite(torch.autograd.Function):
 class _RowsState:
     """Binning in flight over splat rows some other producer wrote (``rows_begin`` ... ``rows_composite`` | ``rows_abandon``)."""
 
-    __slots__ = ("s", "bufs", "n_sums", "C", "N", "dev", "tile")
-
-    def __del__(self):  # dropped without finish or abandon (an exception in between): same care for the pinned buffer
-        try:
-            _drop_pinned(getattr(self, "bufs", None), getattr(self, "n_sums", 0))
-        except Exception:  # noqa: BLE001 -- interpreter shutdown
-            pass
+    __slots__ = ("s", "bufs", "C", "N", "dev", "tile")
 
 
 def rows_begin(radii: Tensor, depths: Tensor, rows: Tensor, tile_size: int, tile_width: int, tile_height: int) -> _RowsState:
@@ -348,8 +314,7 @@ def rows_begin(radii: Tensor, depths: Tensor, rows: Tensor, tile_size: int, tile
     s.C, s.N, s.rows_ready = C, N, 1
     s.tile_size, s.tile_width, s.tile_height = tile_size, tile_width, tile_height
     n_sums = int(B.query("gs_isect_count_blocks", C * N))
-    st.s, st.n_sums, st.C, st.N, st.dev, st.tile = s, n_sums, C, N, dev, (tile_size, tile_width, tile_height)
-    st.bufs = None
+    st.s, st.C, st.N, st.dev, st.tile = s, C, N, dev, (tile_size, tile_width, tile_height)
     st.bufs = _phase1(s, C, N, dev, n_sums, given=(radii, depths, rows))
     with torch.cuda.device(dev):
         B.call("gs_step_fwd_begin", ctypes.addressof(s), torch.cuda.current_stream(dev).cuda_stream)
@@ -357,10 +322,9 @@ def rows_begin(radii: Tensor, depths: Tensor, rows: Tensor, tile_size: int, tile
 
 
 def rows_abandon(st: Optional[_RowsState]) -> None:
-    """Drop a ``rows_begin`` without finishing it (the sparse exchange's overflow retry).  The count kernel stores its block
-    sums straight into the pinned buffer: it goes back to the free list only once the kernel has run."""
+    """Drop a ``rows_begin`` without finishing it, at once instead of when the state is collected (the sparse exchange's overflow retry)."""
     if st is not None:
-        _drop_pinned(st.bufs, st.n_sums)
+        st.bufs["sums"].abandon()
 
 
 class _StepRowsComposite(torch.autograd.Function):
@@ -379,7 +343,7 @@ class _StepRowsComposite(torch.autograd.Function):
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
             (offsets, isect_ids, flatten_ids, render_colors, render_alphas, last_ids, grad_rows, _, scratch, plan) = _finish(
-                s, ctypes.addressof(s), stream, st.bufs, st.n_sums, C, N, height, width, tile_height, tile_width, dev, needs_bwd, prefill)
+                s, ctypes.addressof(s), stream, st.bufs, C, N, height, width, tile_height, tile_width, dev, needs_bwd, prefill)
         W._save_composite(ctx, means2d, conics, colors, opacities, backgrounds, offsets, flatten_ids, render_colors, render_alphas, last_ids,
                           scratch, plan, _ROW_STRIDES, grad_rows, width, height, tile_size, absgrad)
         tiles_per_gauss = st.bufs["tiles_per_gauss"]

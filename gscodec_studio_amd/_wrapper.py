@@ -25,6 +25,7 @@ from torch import Tensor
 from typing_extensions import Literal
 
 from . import _backend as B
+from . import _readback as RB
 
 _CAMERA_MODELS = {"pinhole": 0, "ortho": 1, "fisheye": 2}
 # splat rows (include/gsplat_hip.h): one 64-byte row of 16 floats per projected splat
@@ -1369,13 +1370,6 @@ def isect_tiles_start(means2d, radii, depths, tile_size, tile_width, tile_height
     return isect_tiles_begin(means2d, radii, depths, tile_size, tile_width, tile_height, sort, C, N, n_elems, camera_ids)
 
 
-# pinned host buffers the count kernel writes its per-block sums into: taken in isect_tiles_begin, handed back in
-# isect_tiles_finish once read (a buffer is never shared by two calls in flight; one whose finish never runs is simply
-# garbage-collected).  Re-used so that the steady state makes no pinned allocation.
-_PINNED_FREE: dict = {}
-_PINNED_DIRECT_MAX = 2048  # block sums a kernel may store straight into pinned host memory (4-byte PCIe writes)
-
-
 # the depth pre-sort's route: "on" = the bucketed form where it applies (GS_PRESORT=0: always the LSD radix sort);
 # "lds_capacity": keys a local sort may hold in LDS (0 = the library's 4096; tests lower it to drive the global-memory route)
 _PRESORT = {"on": os.environ.get("GS_PRESORT", "1") != "0", "lds_capacity": 0}
@@ -1394,100 +1388,9 @@ def _split_elems() -> int:
     return _SPLIT_ELEMS[0]
 
 
-def block_sum_totals(a) -> Tuple[int, int]:
-    """(sum of the even entries, sum of the odd entries) of the pinned int32 block-sum array [(intersections, visible)] -- exact, and
-    ~10 us instead of the ~50 of ``a.reshape(-1, 2).sum(0)`` (a strided reduction with a dtype conversion), which sat between the
-    host's read-back and the binning launch with the GPU waiting (round 6, tools/host_timeline.py).  The non-negative pairs are read as
-    int64 words (little endian: even entry = low half, odd entry = high half) and the halves summed separately."""
-    w = a.view("int64")
-    return int((w & 0xFFFFFFFF).sum()), int((w >> 32).sum())
-
-
-def _pinned_take(n: int) -> Tensor:
-    """A pinned int32 buffer the count kernel stores its block sums into, PRE-SET to -1: every sum is >= 0, so the host sees
-    the kernel's progress in the buffer itself (``_SentinelEvent``) and no event has to be recorded behind the kernel -- a
-    recorded event is a barrier packet in the queue, ~6 us of idle GPU between the count kernel and the pre-sort."""
-    free = _PINNED_FREE.get(n)
-    buf = free.pop() if free else torch.empty(n, dtype=torch.int32, pin_memory=True)
-    buf.fill_(-1)
-    return buf
-
-
 # (camera, tile) key + depth rank as ONE 32-bit word through emission and pair sort when they fit (gs_isect_finish_presorted's
 # n_kept_host): GS_PACKED_PAIRS=0 keeps the (key, flatten id) pairs
 _PACKED_PAIRS = os.environ.get("GS_PACKED_PAIRS", "1") != "0"
-
-
-_WAIT_TIMEOUT_S = float(os.environ.get("GS_WAIT_TIMEOUT_S", "600"))  # backstop of any host wait on a BUSY stream (<= 0: none)
-_WAIT_WARNED = [False]
-
-
-class _SentinelEvent:
-    """``query`` / ``synchronize`` of an event over a pinned buffer whose entries go from -1 to >= 0 as the kernel stores them
-    (posted 4-byte writes of independent workgroups into host-coherent memory: each becomes visible on its own -- the
-    mechanism needs fine-grained coherent pinned memory, HIP's default for ``hipHostMalloc``; with HIP_HOST_COHERENT=0 the
-    stores only show at a synchronisation point, which the stream check below turns into a late but correct result).
-
-    The wait is BOUNDED and notices a dead GPU: round 4's query / yield loop for the first few hundred polls, then a yielding spin up to 20 ms, naps after that; every ~2 ms the launch stream is queried -- a
-    device fault raises there, and a stream that has drained while the sentinel is still unset means the kernel never stored
-    (failed launch, lost write): RuntimeError instead of a core spinning for good.  A stream that is still busy is waited for (one
-    warning after 30 s); ``GS_WAIT_TIMEOUT_S`` (600; <= 0: none) is only the backstop behind that."""
-
-    __slots__ = ("buf", "np", "stream", "what")
-
-    def __init__(self, buf: Tensor, stream=None, what: str = "the count kernel's block sums (isect_count_keys_kernel / projection_fwd_kernel)"):
-        self.buf = buf
-        self.np = buf.numpy()  # (a view of the pinned memory: numpy's min over ~1 K ints is a microsecond, torch's op is ~5)
-        self.stream = stream  # the stream the storing kernel was launched on (None: the current one at wait time)
-        self.what = what
-
-    def query(self) -> bool:
-        a = self.np
-        return a[-1] >= 0 and a[0] >= 0 and int(a.min()) >= 0  # (two cache lines while the kernel is far from done)
-
-    def synchronize(self, timeout_s: Optional[float] = None) -> None:
-        import time
-
-        query, nap0 = self.query, time.sleep
-        # fast phase: exactly round 4's wait (query, yield) for the first few hundred polls -- the usual wait is tens to hundreds of
-        # microseconds, up to a step's length when the host runs ahead of the GPU; no clock reads in here (an A/B on one box read
-        # 0.744 against 0.738 ms per step with a perf_counter() per poll)
-        for _ in range(400 if timeout_s is None else 1):
-            if query():
-                return
-            nap0(0)
-        t0 = time.perf_counter()
-        limit = _WAIT_TIMEOUT_S if timeout_s is None else timeout_s
-        next_check = t0
-        while not query():
-            now = time.perf_counter()
-            if now >= next_check:
-                next_check = now + 2e-3
-                st = self.stream if self.stream is not None else torch.cuda.current_stream()
-                try:
-                    drained = st.query()  # raises on a device fault / an earlier HIP error on the stream
-                except Exception as e:
-                    raise RuntimeError(f"GPU error while waiting for {self.what}: {e}") from e
-                if drained:
-                    # everything queued has run: stores of a finished kernel are visible now or never
-                    if query():
-                        return
-                    raise RuntimeError(f"the stream drained but {self.what} never arrived in pinned memory "
-                                       f"(kernel not launched, faulted, or its stores were lost)")
-                # a stream that is still BUSY is not an error: a long evaluation queued ahead, a shared GPU or a profiler serialising
-                # kernels can legitimately put many seconds of work in front of the count kernel.  Warn once and keep waiting; the
-                # bound (GS_WAIT_TIMEOUT_S, default 600 s; <= 0: none) is a backstop for a hung device whose stream query still answers
-                if now - t0 > 30.0 and not _WAIT_WARNED[0]:
-                    _WAIT_WARNED[0] = True
-                    import warnings
-
-                    warnings.warn(f"gscodec_studio_amd: waited {now - t0:.0f} s for {self.what}; the launch stream is still busy -- waiting on")
-                if limit > 0 and now - t0 > limit:
-                    raise RuntimeError(f"timed out after {limit:.1f} s (GS_WAIT_TIMEOUT_S) waiting for {self.what}")
-            # yielding spin for 20 ms (a thread that napped comes back late: a 50 us time.sleep takes ~100 us on the test hosts, and
-            # with naps from 1 ms on a 2-camera step read 2.63 ms instead of 1.37, tools/bench_multicam.py), naps after that: a wait
-            # this long is not a step's own
-            nap0(0 if now - t0 < 20e-3 else 200e-6)
 
 
 @torch.no_grad()
@@ -1496,7 +1399,7 @@ def isect_tiles_begin(means2d, radii, depths, tile_size, tile_width, tile_height
     prefix sum -- plus an ASYNCHRONOUS read-back of n_isects into pinned memory.  Work launched between
     ``begin`` and ``finish`` (the SH colours in ``rasterization``) runs while the host waits for the count, so the
     GPU does not idle across the one host sync of the pipeline (reference: the blocking ``.item()`` of
-    isect_tiles.cu:200)."""
+    isect_tiles.cu:200).  A state whose finish never runs may simply be dropped: its ``"sums"`` (``_readback.BlockSums``) see to the buffer."""
     _require_gpu(means2d, "isect_tiles")
     # means2d may be the first two columns of the splat rows (row stride 16): read in place
     means2d, s_m2 = _row_strided(means2d, 2)
@@ -1519,24 +1422,17 @@ def isect_tiles_begin(means2d, radii, depths, tile_size, tile_width, tile_height
 
     tiles_per_gauss = torch.empty(radii.shape, dtype=torch.int32, device=dev)
     st_["tiles_per_gauss"] = tiles_per_gauss
-    st_["cum"] = st_["perm"] = st_["pinned"] = st_["event"] = st_["n_kept"] = st_["gsums"] = st_["gpre"] = None
+    st_["cum"] = st_["perm"] = st_["sums"] = st_["n_kept"] = st_["gsums"] = st_["gpre"] = None
     with _device_of(means2d):
         if n_elems > 0:
             if sort:
                 # splat-level depth pre-sort: afterwards only the (camera, tile) bits need sorting
                 dkeys = torch.empty(n_elems, dtype=torch.int64, device=dev)
                 # n_isects = the sum of the per-block counts, known to the host ~100 us of GPU work (pre-sort, prefix sum,
-                # SH colours) before the pipeline needs it
-                # sum there.  The kernel stores them STRAIGHT into pinned host memory (device-visible under HIP's unified
-                # addressing; a few thousand posted 4-byte writes): no device-to-host copy command in the stream.
+                # SH colours) before the pipeline needs it; stored or copied: _readback.BlockSums
                 n_sums = B.query("gs_isect_count_blocks", n_elems)
-                # (a few thousand blocks -- 983 at 1 M splats -- store straight into pinned memory; beyond that the sums are
-                # added up on the device and 8 bytes are copied, as in round 1: with 48 K block sums per step at 49 M splats,
-                # stored directly OR copied as one 192 KB block, every third or fourth forward stalled the GPU for ~85 ms)
-                # every block reports (intersections, visible elements) as one 8-byte store: [n_sums][2]
-                direct = n_sums <= _PINNED_DIRECT_MAX
-                pinned = _pinned_take(2 * n_sums) if direct else torch.empty(2, dtype=torch.int64, pin_memory=True)
-                bsums = pinned if direct else torch.empty(2 * n_sums, dtype=torch.int32, device=dev)
+                sums = RB.BlockSums.stored(n_sums, torch.cuda.current_stream(dev)) if n_sums <= RB._PINNED_DIRECT_MAX else None
+                bsums = sums.buf if sums is not None else torch.empty(2 * n_sums, dtype=torch.int32, device=dev)
                 # the depth pre-sort: up to 2 M elements the BUCKETED form (sampled splitters -> one partition pass -> local
                 # sorts in LDS: 4 launches), above that the plain LSD radix sort (4 passes, bandwidth-bound there); the count
                 # kernel counts the digits of the first (only) partition pass into the sort's temp buffer either way
@@ -1552,12 +1448,8 @@ def isect_tiles_begin(means2d, radii, depths, tile_size, tile_width, tile_height
                 B.call("gs_isect_count_keys", n_elems, B.ptr(means2d), s_m2, B.ptr(radii), B.ptr(depths), tile_size, tile_width,
                        tile_height, B.ptr(tiles_per_gauss), B.ptr(dkeys), B.ptr(dvals), B.ptr(bsums),
                        B.ptr(temp) if hist_ready else None, tb if hist_ready else 0, B.ptr(split), st)
-                if direct:
-                    ev = _SentinelEvent(pinned, stream=torch.cuda.current_stream(dev))  # (the stream the count kernel was queued on)
-                else:
-                    pinned.copy_(bsums.view(-1, 2).sum(0, dtype=torch.int64), non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream(dev))
+                if sums is None:
+                    sums = RB.BlockSums.copied(bsums.view(-1, 2).sum(0, dtype=torch.int64))
                 # culled elements carry the maximal key: the sort drops them in its first pass
                 perm = torch.empty(n_elems, dtype=torch.int32, device=dev)
                 n_kept = torch.empty(1, dtype=torch.int32, device=dev)
@@ -1588,44 +1480,15 @@ def isect_tiles_begin(means2d, radii, depths, tile_size, tile_width, tile_height
                 B.call("gs_isect_count", n_elems, B.ptr(means2d), s_m2, B.ptr(radii), tile_size, tile_width, tile_height,
                        B.ptr(tiles_per_gauss), st)
                 B.call("gs_cumsum_i32", n_elems, B.ptr(tiles_per_gauss), B.ptr(cum), B.ptr(scratch), sb, st)
-                pinned = torch.empty(1, dtype=torch.int64, pin_memory=True)
-                pinned.copy_(cum[-1:], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-            st_["cum"], st_["pinned"], st_["event"] = cum, pinned, ev
+                sums = RB.BlockSums.copied(cum[-1:])
+            st_["cum"], st_["sums"] = cum, sums
     return st_
 
 
-def _wait_event(ev) -> None:
-    """Wait for a CUDA event by POLLING it.  ``Event.synchronize()`` spins only briefly and then sleeps; when the GPU needs a
-    few milliseconds to get there (49 M splats: 3 ms per forward) the wake-up came ~17 ms late on the bench host -- the
-    forward ran at 42 FPS instead of 300.  A few milliseconds of host polling cost nothing here.  Past 0.25 s the wait is
-    handed to the event's own ``synchronize`` (a real event sleeps and raises HIP errors; a ``_SentinelEvent`` naps, watches
-    the stream for faults and gives up after ``GS_WAIT_TIMEOUT_S``): never an unbounded spin."""
-    import time
-
-    if isinstance(ev, _SentinelEvent):
-        ev.synchronize()
-        return
-    deadline = time.perf_counter() + 0.25
-    while not ev.query():
-        if time.perf_counter() > deadline:  # something long is queued in front: stop burning the core
-            ev.synchronize()
-            return
-
-
 def isect_tiles_abandon(st_) -> None:
-    """Drop a state ``isect_tiles_begin`` / ``isect_tiles_start`` returned WITHOUT finishing it (the sparse exchange's
-    overflow retry, an exception between begin and finish).  The count kernel stores its block sums straight into the
-    state's pinned buffer; torch's pinned caching allocator does not track kernel stores, so the buffer must not go back to
-    it (or to our free list) before the kernel has run: wait for the state's event first."""
-    if st_ is None or st_.get("event") is None:
-        return
-    _wait_event(st_["event"])
-    pinned = st_.get("pinned")
-    if pinned is not None and pinned.dtype == torch.int32:
-        _PINNED_FREE.setdefault(pinned.numel(), []).append(pinned)
-    st_["pinned"] = st_["event"] = None
+    """Drop a state of ``isect_tiles_begin`` WITHOUT finishing it, at once instead of when it is collected (the sparse exchange's overflow retry)."""
+    if st_ is not None and st_["sums"] is not None:
+        st_["sums"].abandon()
 
 
 @torch.no_grad()
@@ -1640,17 +1503,9 @@ def isect_tiles_finish(st_, offsets_for: Optional[int] = None):
     if offsets_for is not None:  # (allocated before the wait: its size does not depend on the count)
         offsets = torch.empty((offsets_for, st_["tile_height"], st_["tile_width"]), dtype=torch.int32, device=dev)
     n_isects = n_kept = 0
-    if st_["event"] is not None:
-        _wait_event(st_["event"])  # the one host sync (isect_tiles.cu:200)
-        if st_["pinned"].numel() == 1:  # (the unsorted path: cum[-1])
-            n_isects = int(st_["pinned"][0])
-        else:  # [blocks][2] (or their two totals): intersections, elements the depth pre-sort keeps
-            pn = st_["pinned"].numpy()
-            pairs = block_sum_totals(pn) if pn.dtype == "int32" and pn.size % 2 == 0 and pn.size >= 2 else pn.reshape(-1, 2).sum(0, dtype="int64")
-            n_isects, n_kept = int(pairs[0]), int(pairs[1])
-        if st_["pinned"].dtype == torch.int32:
-            _PINNED_FREE.setdefault(st_["pinned"].numel(), []).append(st_["pinned"])
-            st_["pinned"] = None
+    if st_["sums"] is not None:
+        n_isects, n_kept = st_["sums"].wait()  # the one host sync (isect_tiles.cu:200)
+        st_["sums"].release()
     with _device_of(means2d):
         isect_ids = torch.empty(n_isects, dtype=torch.int64, device=dev)
         flatten_ids = torch.empty(n_isects, dtype=torch.int32, device=dev)

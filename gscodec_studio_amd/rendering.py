@@ -24,7 +24,8 @@ from torch import Tensor
 from typing_extensions import Literal
 
 from . import _step
-from ._route import Route, direct_block_sums, route
+from ._readback import direct_block_sums
+from ._route import Route, route
 from .compression_simulation.ada_mask import MaskedShN
 from ._wrapper import (
     ROW_COLOR,
@@ -451,7 +452,7 @@ def rasterization(
                 )
             if cap_world is None or not D.exchange_overflowed():
                 break
-            # (the pinned block-sum buffer is still being written by the count kernel)
+            # (the count kernel may still be storing into the state's pinned buffer: handed back here, not left to the collector)
             _step.rows_abandon(rows_state)
             isect_tiles_abandon(isect_state)
             isect_state = rows_state = None
@@ -622,18 +623,14 @@ def rasterization_2dgs(
     # binning is split around its one host wait (the intersection count): the colour evaluation is queued in between
     isect_state = isect_tiles_begin(means2d, radii, depths, tile_size, tile_width, tile_height, True, C, N, int(radii.numel()), None)
 
-    try:
-        if sh_degree is not None:
-            if viewmats.requires_grad:  # (the fused colour kernel has no gradient for the camera centres)
-                dirs = means[None, :, :] - _camera_centers(viewmats)[:, None, :]
-                colors = torch.clamp_min(spherical_harmonics_shared(sh_degree, dirs, colors, masks=radii > 0) + 0.5, 0.0)
-            else:
-                colors = spherical_harmonics_view(sh_degree, means, viewmats, colors, radii)  # [C, N, 3], clamp_min(. + 0.5, 0) included
-        elif colors.dim() == 2:
-            colors = colors.expand(C, -1, -1)
-    except BaseException:  # (the count kernel still stores into the state's pinned buffer: wait before it is recycled)
-        isect_tiles_abandon(isect_state)
-        raise
+    if sh_degree is not None:
+        if viewmats.requires_grad:  # (the fused colour kernel has no gradient for the camera centres)
+            dirs = means[None, :, :] - _camera_centers(viewmats)[:, None, :]
+            colors = torch.clamp_min(spherical_harmonics_shared(sh_degree, dirs, colors, masks=radii > 0) + 0.5, 0.0)
+        else:
+            colors = spherical_harmonics_view(sh_degree, means, viewmats, colors, radii)  # [C, N, 3], clamp_min(. + 0.5, 0) included
+    elif colors.dim() == 2:
+        colors = colors.expand(C, -1, -1)
 
     if render_mode in ["RGB+D", "RGB+ED"]:
         colors = torch.cat((colors, depths[..., None]), dim=-1)

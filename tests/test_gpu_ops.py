@@ -736,7 +736,7 @@ def test_isect_count_read_back_paths_agree(ops, monkeypatch):
     """The intersection count reaches the host in two ways: per-block sums stored straight into pinned memory (small
     inputs) or summed on the device and copied as 8 bytes (large ones; the direct form stalled the GPU at 49 M splats).
     Both must give the same lists."""
-    from gscodec_studio_amd import _wrapper as W
+    from gscodec_studio_amd import _readback as RB
 
     g = torch.Generator(device="cpu").manual_seed(11)
     C, n, tw, th, ts = 2, 70_000, 40, 30, 16
@@ -745,7 +745,7 @@ def test_isect_count_read_back_paths_agree(ops, monkeypatch):
     depths = (torch.rand(C, n, generator=g) * 10 + 0.1).cuda()
     outs = []
     for limit in (1 << 30, 0):
-        monkeypatch.setattr(W, "_PINNED_DIRECT_MAX", limit)
+        monkeypatch.setattr(RB, "_PINNED_DIRECT_MAX", limit)
         tpg, ids, flat = ops.isect_tiles(means2d, radii, depths, ts, tw, th)
         outs.append((N(tpg), N(ids), N(flat)))
     assert outs[0][1].size > 0

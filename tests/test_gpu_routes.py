@@ -54,7 +54,7 @@ CASES = {
     "two-launch-sh-bwd-mask16": dict(colors="mask", K=16, patch={("_wrapper", "_FUSE_SH_BWD"): False}),
     "prefill-off": dict(colors="sh", K=16, patch={("_wrapper", "PREFILL_ENABLED"): False}),
     "prefill-off-operators": dict(colors="sh", K=16, patch={("_wrapper", "PREFILL_ENABLED"): False, ("_step", "ENABLED"): False}),
-    "pinned-direct-max-0": dict(colors="sh", K=16, patch={("_wrapper", "_PINNED_DIRECT_MAX"): 0}),
+    "pinned-direct-max-0": dict(colors="sh", K=16, patch={("_readback", "_PINNED_DIRECT_MAX"): 0}),
 }
 
 
@@ -62,7 +62,7 @@ def run_case(colors, K=None, C=1, render_mode="RGB", packed=False, sparse_grad=F
              absgrad=False, deterministic=False, channel_chunk=32, tile_size=16, dynamic=None, patch=None):
     """-> (entry-point names, render, alphas, meta, {name: gradient})"""
     import gscodec_studio_amd as G
-    from gscodec_studio_amd import _backend, _step, _wrapper
+    from gscodec_studio_amd import _backend, _readback, _step, _wrapper
     from gscodec_studio_amd.compression_simulation.ada_mask import MaskedShN
     from gscodec_studio_amd.dynamic import DynamicSlice
 
@@ -122,7 +122,7 @@ def run_case(colors, K=None, C=1, render_mode="RGB", packed=False, sparse_grad=F
         calls.append(name)
         return real_call(name, *a, **kw)
 
-    mods = {"_step": _step, "_wrapper": _wrapper, "_backend": _backend}
+    mods = {"_step": _step, "_wrapper": _wrapper, "_backend": _backend, "_readback": _readback}
     patches = dict(patch or {})
     patches["_backend", "call"] = recording_call
     saved = {k: getattr(mods[k[0]], k[1]) for k in patches}

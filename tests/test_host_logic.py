@@ -183,11 +183,11 @@ def test_dynamic_slice_descriptor_logic():
 
 
 def test_block_sum_totals_is_exact():
-    """``_wrapper.block_sum_totals`` (the host's reduction of the count kernel's per-block (intersections, visible) pairs, read as int64
+    """``_readback.block_sum_totals`` (the host's reduction of the count kernel's per-block (intersections, visible) pairs, read as int64
     words) against the plain column sums, including totals beyond 2^32."""
     import numpy as np
 
-    from gscodec_studio_amd._wrapper import block_sum_totals
+    from gscodec_studio_amd._readback import block_sum_totals
 
     rng = np.random.default_rng(0)
     for n, hi_val in ((1, 10), (3930, 5000), (2048, 2_000_000), (2048, 2_100_000_000)):
@@ -281,9 +281,9 @@ def route_grid(stride=1, offset=0):
 def test_route_invariants_over_the_grid(monkeypatch):
     """Every 61st point of the grid (61 divides no dimension, so every pair of values still meets; the whole grid, 7.4 M points, was walked
     once against the predicates this function replaced)."""
-    from gscodec_studio_amd import _route, _step, _wrapper
+    from gscodec_studio_amd import _readback, _route, _step, _wrapper
 
-    bound = _wrapper._PINNED_DIRECT_MAX * 1024
+    bound = _readback._PINNED_DIRECT_MAX * 1024
     n = 0
     for f, (step_on, prefill_on) in route_grid(stride=61):
         monkeypatch.setattr(_step, "ENABLED", step_on)
@@ -310,7 +310,7 @@ def test_route_invariants_over_the_grid(monkeypatch):
 
 
 def test_route_named_rows(monkeypatch):
-    from gscodec_studio_amd import _route, _step, _wrapper
+    from gscodec_studio_amd import _readback, _route, _step, _wrapper
 
     def R(**kw):
         return _route.route(**{**_BASE, **kw})
@@ -346,7 +346,7 @@ def test_route_named_rows(monkeypatch):
     monkeypatch.setattr(_wrapper, "PREFILL_ENABLED", False)
     assert not R().prefill
     monkeypatch.undo()
-    monkeypatch.setattr(_wrapper, "_PINNED_DIRECT_MAX", 4)
+    monkeypatch.setattr(_readback, "_PINNED_DIRECT_MAX", 4)
     assert not R().step_driver and R(N=4096).step_driver and not R(N=4097).step_driver and not R(N=0).step_driver
     monkeypatch.undo()
     assert not R(tile_size=32).step_driver and not R(render_mode="RGB+D").step_driver and R(render_mode="RGB+D").depth_view

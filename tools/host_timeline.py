@@ -10,7 +10,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from gscodec_studio_amd import _backend as B  # noqa: E402
-from gscodec_studio_amd import _wrapper as W  # noqa: E402
+from gscodec_studio_amd._readback import BlockSums  # noqa: E402
 from gscodec_studio_amd import rasterization  # noqa: E402
 from gscodec_studio_amd._helper import sh_workload  # noqa: E402
 
@@ -19,7 +19,7 @@ w = sh_workload(scene_grid=3, device=dev, camera_mode="jitter0")
 params = {k: w[k].clone().requires_grad_(True) for k in ("means", "quats", "scales", "opacities", "sh")}
 vm, Ks = w["viewmats"][:1].contiguous(), w["Ks"][:1].contiguous()
 log = []
-orig_call, orig_wait = B.call, W._wait_event
+orig_call, orig_wait = B.call, BlockSums.wait
 
 
 def call(name, *a):
@@ -29,10 +29,11 @@ def call(name, *a):
     return r
 
 
-def wait(ev):
+def wait(sums):
     t0 = time.perf_counter()
-    orig_wait(ev)
+    totals = orig_wait(sums)
     log.append(("wait(block sums)", t0, time.perf_counter()))
+    return totals
 
 
 def step(trace):
@@ -49,14 +50,14 @@ def step(trace):
 for _ in range(20):
     step(False)
 torch.cuda.synchronize()
-B.call, W._wait_event = call, wait
+B.call, BlockSums.wait = call, wait
 rows = []
 for _ in range(200):
     del log[:]
     t0, t1 = step(True)
     fwd = [(n, a - t0, b - t0) for n, a, b in log if a < t1]
     rows.append(fwd + [("rasterization() returns", t1 - t0, t1 - t0)])
-B.call, W._wait_event = orig_call, orig_wait
+B.call, BlockSums.wait = orig_call, orig_wait
 names = [n for n, _, _ in rows[0]]
 print(f"{'host event':34s} enter us   leave us   (medians over {len(rows)} steps, t = 0 at the call of rasterization())")
 for j, n in enumerate(names):
