@@ -8,7 +8,9 @@ Public surface (mirrors the reference's ``gsplat`` package for this path only):
   ``relocation.compute_relocation``, and ``bilagrid.{BilateralGrid, slice, slice_image, total_variation_loss,
   color_affine_transform}`` (``from gscodec_studio_amd.bilagrid import ...`` in place of ``from lib_bilagrid import ...``), and the 2D Gaussian splatting
   renderer ``rasterization_2dgs`` with its operators ``fully_fused_projection_2dgs`` / ``rasterize_to_pixels_2dgs`` (``surfel.py``) and
-  ``utils.{depth_to_points, depth_to_normal}``.
+  ``utils.{depth_to_points, depth_to_normal}``, and the spacetime trainer's colour decoder
+  ``dynamic.{Sandwich, getcolormodel, decode_colors, trbfunction}`` (``from gscodec_studio_amd.dynamic import getcolormodel, trbfunction``
+  in place of ``from helper.STG.helper_model import ...``; ``dynamic.render_dynamic(..., decoder=, rays=)`` applies it after the render).
 """
 from ._wrapper import (
     accumulate,

@@ -10,6 +10,12 @@ ACTIVATED values (sigmoid / exp are applied by the caller, as in the trainer).  
 their load phase (csrc/projection_dyn.hip) -- bit-identical to ``temporal_slice`` followed by ``rasterization``, without the
 round trip of means_t / quats_t / opacity_t through HBM; opt-in on top, the trainer's activations (``raw``) and the round
 quantizer hooks (``quantize``) ride in the same pass.  ``render_dynamic`` is the dynamic trainer's ``rasterize_splats`` in that form.
+
+The spacetime trainer's colour decoder (reference examples/helper/STG/helper_model.py, applied to the nine-channel render at
+examples/simple_trainer_STG.py:578-581) is here too, so that ``from helper.STG.helper_model import getcolormodel, trbfunction``
+becomes ``from gscodec_studio_amd.dynamic import getcolormodel, trbfunction``: ``Sandwich`` / ``getcolormodel()`` -- the per-pixel
+12 -> 6 -> 3 MLP with the reference's parameters and state-dict keys, one HIP kernel each way (csrc/stg_decoder.hip) --,
+``decode_colors`` (its functional form over an NHWC render) and ``trbfunction``.  ``render_dynamic(..., decoder=, rays=)`` applies it.
 """
 from __future__ import annotations
 
@@ -17,7 +23,7 @@ import ctypes
 from typing import Dict, Optional, Sequence, Tuple, Union
 
 import torch
-from torch import Tensor
+from torch import Tensor, nn
 
 from . import _backend as B
 
@@ -271,8 +277,133 @@ def stg_features(colors: Tensor, features_dir: Tensor, features_time: Tensor, tr
     return _StgFeatures.apply(colors, features_dir, features_time, trbf_center, timestamp, quantize)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The spacetime colour decoder  (csrc/stg_decoder.hip)
+_DECODER_TUNING = {"max_blocks": 0}  # cap of the kernels' grid in workgroups; 0 = the library's default
+
+
+def _set_decoder_tuning(**kv) -> dict:
+    """Set tuning values (key: max_blocks; ``None`` / 0 = default) for the decoder calls that FOLLOW (a forward's backward reads the
+    value again); returns the previous values.  For tests: a small cap forces the grid-stride loop at a small shape."""
+    prev = dict(_DECODER_TUNING)
+    for k, v in kv.items():
+        assert k in _DECODER_TUNING, k
+        _DECODER_TUNING[k] = 0 if v is None else int(v)
+    return prev
+
+
+def _pixel_strided(f9: Tensor) -> Tuple[Tensor, int]:
+    """[C, H, W, 9] as the kernels read it, with its pixel stride: channel stride 1 and ONE pixel stride over the whole [C H W] run
+    (a contiguous copy otherwise)."""
+    C, H, W, _ = f9.shape
+    ps = f9.stride(2) if W > 1 else (f9.stride(1) if H > 1 else max(f9.stride(0), 9))
+    ok = f9.stride(3) == 1 and ps >= 9 and (H == 1 or f9.stride(1) == W * ps) and (C == 1 or f9.stride(0) == H * W * ps)
+    return (f9, ps) if ok else (f9.contiguous(), 9)
+
+
+class _DecodeColors(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, f9, rays, w1, w2):
+        C, H, W, _ = f9.shape
+        f9, ps = _pixel_strided(f9)
+        if not (rays.stride(3) == 1 and (H == 1 or rays.stride(2) == W)):
+            rays = rays.contiguous()
+        w1c, w2c = w1.contiguous(), w2.contiguous()
+        out = torch.empty((C, H, W, 3), dtype=torch.float32, device=f9.device)
+        ctx.geo = (C, H, W, ps, rays.stride(0), rays.stride(1))
+        with torch.cuda.device(f9.device):
+            B.call("gs_stg_decode_fwd", C, H, W, B.ptr(f9), ctx.geo[3], B.ptr(rays), ctx.geo[4], ctx.geo[5], B.ptr(w1c), B.ptr(w2c),
+                   _DECODER_TUNING["max_blocks"], B.ptr(out), torch.cuda.current_stream(f9.device).cuda_stream)
+        ctx.save_for_backward(f9, rays, w1c, w2c)
+        ctx.w_shapes = (w1.shape, w2.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, v_out):
+        f9, rays, w1c, w2c = ctx.saved_tensors
+        C, H, W, ps, rs_cam, rs_ch = ctx.geo
+        need_f, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        if not (need_f or need_w):
+            return None, None, None, None
+        dev = f9.device
+        v_out = v_out.contiguous().float()
+        cap = _DECODER_TUNING["max_blocks"]
+        v_f = torch.empty((C, H, W, 9), dtype=torch.float32, device=dev) if need_f else None
+        partials = None
+        if need_w:
+            partials = torch.empty((int(B.query("gs_stg_decode_partial_rows", C, H, W, cap)), 90), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            B.call("gs_stg_decode_bwd", C, H, W, B.ptr(f9), ps, B.ptr(rays), rs_cam, rs_ch, B.ptr(w1c), B.ptr(w2c), B.ptr(v_out), cap,
+                   B.ptr(v_f), B.ptr(partials), torch.cuda.current_stream(dev).cuda_stream)
+        v_w1 = v_w2 = None
+        if need_w:
+            sums = partials.sum(dim=0)  # (one row per workgroup, added here in torch's fixed order: no float atomics anywhere)
+            v_w1 = sums[:72].reshape(ctx.w_shapes[0]) if ctx.needs_input_grad[2] else None
+            v_w2 = sums[72:].reshape(ctx.w_shapes[1]) if ctx.needs_input_grad[3] else None
+        return v_f, None, v_w1, v_w2
+
+
+def decode_colors(features: Tensor, rays: Tensor, w1: Tensor, w2: Tensor) -> Tensor:
+    """The spacetime colour decoder over an NHWC render: ``features`` ``[C, H, W, >= 9]`` (the first nine channels are used and read in
+    place, e.g. a 10-channel ``RGB+D`` render or the permuted NCHW view the trainer makes), ``rays`` ``[C, 6, H, W]`` (origin, unit
+    direction; no gradient), ``w1`` = ``mlp1.weight`` ``[6, 12(, 1, 1)]``, ``w2`` = ``mlp2.weight`` ``[3, 6(, 1, 1)]`` -> ``[C, H, W, 3]``:
+    ``sigmoid(features[..., :3] + w2 relu(w1 cat(features[..., 3:9], rays)))`` per pixel.  One kernel forward, one backward
+    (gradients of the features and of both weights; the weights' are bit-identical from run to run)."""
+    for name, t in (("features", features), ("rays", rays), ("w1", w1), ("w2", w2)):
+        if not isinstance(t, Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"decode_colors: {name} must be a float32 tensor (got {getattr(t, 'dtype', type(t).__name__)})")
+    if features.dim() != 4 or features.shape[-1] < 9 or features.numel() == 0:
+        raise ValueError(f"decode_colors: features must be a non-empty [C, H, W, >= 9] tensor (got shape {tuple(features.shape)})")
+    C, H, W, _ = features.shape
+    if tuple(rays.shape) != (C, 6, H, W):
+        raise ValueError(f"decode_colors: rays must be [C, 6, H, W] = {(C, 6, H, W)} (got shape {tuple(rays.shape)})")
+    if w1.numel() != 72 or tuple(w1.shape[:2]) != (6, 12) or w2.numel() != 18 or tuple(w2.shape[:2]) != (3, 6):
+        raise ValueError(f"decode_colors: w1 must be [6, 12(, 1, 1)] and w2 [3, 6(, 1, 1)] (got {tuple(w1.shape)}, {tuple(w2.shape)})")
+    if rays.requires_grad:
+        raise NotImplementedError("decode_colors: rays requires a gradient, but the decoder has none for the rays (detach it)")
+    if C * H * W >= 2 ** 32:
+        raise ValueError(f"decode_colors: {tuple(features.shape)} has more than 2^32 - 1 pixels")
+    for name, t in (("features", features), ("rays", rays), ("w1", w1), ("w2", w2)):
+        if not t.is_cuda:
+            raise RuntimeError(f"decode_colors: the HIP path needs device tensors, {name} is on {t.device} (no CPU fallback)")
+        if t.device != features.device:
+            raise RuntimeError(f"decode_colors: features and {name} are on different devices ({features.device}, {t.device})")
+    return _DecodeColors.apply(features[..., :9], rays, w1, w2)
+
+
+class Sandwich(nn.Module):
+    """The spacetime trainer's colour decoder with the reference module's parameters: ``mlp1`` (12 -> 6) and ``mlp2`` (6 -> 3), 1x1
+    convolutions without bias, created in that order -- the same ``state_dict`` keys, shapes and seeded initialisation, so
+    checkpoints load both ways with ``strict=True``.  ``dim`` and ``outdim`` are accepted and, as in the reference, unused."""
+
+    def __init__(self, dim: int = 9, outdim: int = 3, bias: bool = False):
+        super().__init__()
+        if bias:
+            raise NotImplementedError("Sandwich: bias=True is not implemented (the kernels are bias-free, as getcolormodel() is)")
+        self.mlp1 = nn.Conv2d(12, 6, kernel_size=1, bias=False)
+        self.mlp2 = nn.Conv2d(6, 3, kernel_size=1, bias=False)
+
+    def forward(self, input: Tensor, rays: Tensor, time=None) -> Tensor:  # noqa: A002
+        """``input`` ``[C, 9, H, W]`` (the trainer's permuted view of the NHWC render is read in place), ``rays`` ``[C, 6, H, W]`` ->
+        ``[C, 3, H, W]``, a permuted view of the kernel's NHWC output: the trainer's ``.permute(0, 2, 3, 1)`` that follows is
+        contiguous.  ``time`` is unused, as in the reference."""
+        if not isinstance(input, Tensor) or input.dim() != 4 or input.shape[1] != 9:
+            raise ValueError(f"Sandwich: input must be [C, 9, H, W] (got shape {tuple(getattr(input, 'shape', ()))})")
+        return decode_colors(input.permute(0, 2, 3, 1), rays, self.mlp1.weight, self.mlp2.weight).permute(0, 3, 1, 2)
+
+
+def getcolormodel() -> Sandwich:
+    return Sandwich(9, 3)
+
+
+def trbfunction(x: Tensor) -> Tensor:
+    """The temporal radial basis ``exp(-x^2)`` (plain torch)."""
+    return torch.exp(-(x * x))
+
+
 def render_dynamic(splats: Dict[str, Tensor], timestamp: float, viewmats: Tensor, Ks: Tensor, width: int, height: int,
-                   compression_sim=None, step: int = 0, features: str = "colors", temp_vis_mask: bool = False, **kwargs):
+                   compression_sim=None, step: int = 0, features: str = "colors", temp_vis_mask: bool = False, decoder=None,
+                   rays: Optional[Tensor] = None, **kwargs):
     """The dynamic trainer's ``rasterize_splats`` (reference examples/simple_trainer_dyngs.py:463-577, compression_sim on or off) on
     the fused route: ``splats`` is the trainer's RAW parameter dict (means, scales (log), quats, opacities (logits), trbf_center,
     trbf_scale (log), motion, omega, colors [, features_dir, features_time]); returns ``(render_colors, render_alphas, info)``.
@@ -285,9 +416,14 @@ def render_dynamic(splats: Dict[str, Tensor], timestamp: float, viewmats: Tensor
     ``temp_vis_mask`` (the trainer's option, dyngs.py:137, 526-571): splats whose temporal basis is <= 0.05 at this timestamp are culled
     by the projection; ``info["t_vis_mask"]`` is the mask and the per-gaussian ``info`` tensors are full-size, as the reference leaves them
     (its ``info["means2d"]`` alone stays compacted to the masked subset: here it is [C, N, 2] like the rest).
+    ``decoder`` (a ``Sandwich``, with ``features="stg"``) and ``rays`` ``[C, 6, H, W]``: the nine rendered channels go through the colour
+    decoder (examples/simple_trainer_STG.py:578-581) and ``render_colors`` is the decoded ``[C, H, W, 3]``; with a depth render mode the
+    depth column follows unchanged.
     -> also returns ``esti_bits`` of the hooks that ran outside as ``info["esti_bits"]``."""
     from .rendering import rasterization
 
+    if decoder is not None and (features != "stg" or rays is None):
+        raise ValueError('render_dynamic: decoder needs features="stg" and rays [C, 6, H, W]')
     P = dict(splats)
     esti_bits = {}
     quantize = {}
@@ -328,4 +464,7 @@ def render_dynamic(splats: Dict[str, Tensor], timestamp: float, viewmats: Tensor
     info["esti_bits"] = esti_bits
     if temp_vis_mask:
         info["t_vis_mask"] = ds.t_vis_mask
+    if decoder is not None:
+        decoded = decoder(rc[..., :9].permute(0, 3, 1, 2), rays, timestamp).permute(0, 2, 3, 1)
+        rc = decoded if rc.shape[-1] == 9 else torch.cat((decoded, rc[..., 9:]), dim=-1)
     return rc, ra, info

@@ -46,7 +46,8 @@ extern "C" {
  * (gs_bilagrid_slice_fwd / _bwd, gs_bilagrid_tv_fwd / _bwd, gs_bilagrid_tv_work_bytes), and the entropy-coder entries
  * (gs_ans_histogram, gs_ans_encode_bytes, gs_ans_encode, gs_ans_pack, gs_ans_decode), and the grid-sort entries
  * (gs_gridsort_blur, gs_gridsort_keys, gs_gridsort_assign), and the 2D Gaussian splatting entries (gs_projection_2dgs_fwd / _bwd,
- * gs_rasterize_2dgs_fwd / _bwd, gs_depth_to_normal_fwd / _bwd). */
+ * gs_rasterize_2dgs_fwd / _bwd, gs_depth_to_normal_fwd / _bwd), and the spacetime colour decoder's (gs_stg_decode_fwd / _bwd,
+ * gs_stg_decode_partial_rows). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -1212,6 +1213,29 @@ int32_t gs_bilagrid_tv_fwd(const float *x, uint32_t N, uint32_t C, uint32_t L, u
                            uint64_t work_bytes, float *out, gs_stream_t stream);
 int32_t gs_bilagrid_tv_bwd(const float *x, uint32_t N, uint32_t C, uint32_t L, uint32_t H, uint32_t W, const float *grad,
                            float *v_x, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * B2  The spacetime trainer's colour decoder (examples/helper/STG/helper_model.py: Sandwich / getcolormodel(), applied to the
+ * 9-channel render at examples/simple_trainer_STG.py:578-581), forward and backward.  No host synchronisation.
+ * Per pixel, f[0..8] the rendered feature and r[0..5] the ray: x = (f[3..8], r[0..5]); h[j] = max(0, sum_k w1[12 j + k] x[k]),
+ * j = 0..5; out[c] = sigmoid(f[c] + sum_j w2[6 c + j] h[j]), c = 0..2.  w1: fp32 [6, 12] (mlp1.weight), w2: fp32 [3, 6]
+ * (mlp2.weight), contiguous DEVICE arrays.
+ * features: fp32 [C, H, W, .] with channel stride 1 and ONE pixel stride pix_stride >= 9 (in elements) over the whole [C H W]
+ * run: pixel p's channels start at features + p * pix_stride (columns 0-8 of a 10-channel render work without a copy).
+ * rays: fp32 [C, 6, H, W], every H x W plane contiguous; plane (c, k) starts at rays + c * ray_cam_stride + k * ray_ch_stride
+ * (elements).  C H W < 2^32.  max_blocks: cap of the grid (workgroups of 256 lanes, grid-stride loop); 0 = the library's default.
+ * gs_stg_decode_fwd writes out [C, H, W, 3], contiguous.
+ * gs_stg_decode_bwd: from v_out [C, H, W, 3] (contiguous) writes v_features [C, H, W, 9] (contiguous) and / or partials
+ * [G, 90], G = gs_stg_decode_partial_rows(C, H, W, max_blocks): row b holds workgroup b's sums of v_w1 [6, 12] followed by v_w2
+ * [3, 6]; the caller adds the G rows.  Either may be NULL (not needed).  h and out are recomputed.  No float atomics: for one
+ * shape and max_blocks the partials are bit-identical from run to run.  The rays get no gradient. */
+uint32_t gs_stg_decode_partial_rows(uint32_t C, uint32_t H, uint32_t W, uint32_t max_blocks);
+int32_t gs_stg_decode_fwd(uint32_t C, uint32_t H, uint32_t W, const float *features, int64_t pix_stride, const float *rays,
+                          int64_t ray_cam_stride, int64_t ray_ch_stride, const float *w1, const float *w2, uint32_t max_blocks,
+                          float *out, gs_stream_t stream);
+int32_t gs_stg_decode_bwd(uint32_t C, uint32_t H, uint32_t W, const float *features, int64_t pix_stride, const float *rays,
+                          int64_t ray_cam_stride, int64_t ray_ch_stride, const float *w1, const float *w2, const float *v_out,
+                          uint32_t max_blocks, float *v_features, float *partials, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * D1  The densification strategies (gsplat/strategy/default.py, mcmc.py, ops.py; gsplat/relocation.py).  One thread per
