@@ -10,7 +10,9 @@ Public surface (mirrors the reference's ``gsplat`` package for this path only):
   renderer ``rasterization_2dgs`` with its operators ``fully_fused_projection_2dgs`` / ``rasterize_to_pixels_2dgs`` (``surfel.py``) and
   ``utils.{depth_to_points, depth_to_normal}``, and the spacetime trainer's colour decoder
   ``dynamic.{Sandwich, getcolormodel, decode_colors, trbfunction}`` (``from gscodec_studio_amd.dynamic import getcolormodel, trbfunction``
-  in place of ``from helper.STG.helper_model import ...``; ``dynamic.render_dynamic(..., decoder=, rays=)`` applies it after the render).
+  in place of ``from helper.STG.helper_model import ...``; ``dynamic.render_dynamic(..., decoder=, rays=)`` applies it after the render),
+  and the static trainer's appearance module ``appearance.AppearanceOptModule`` (``from gscodec_studio_amd.appearance import
+  AppearanceOptModule`` in place of ``from utils import AppearanceOptModule``; ``module.colors(...)`` is the fused form of its call site).
 """
 from ._wrapper import (
     accumulate,
@@ -30,6 +32,7 @@ from ._wrapper import (
 from .rendering import rasterization, rasterization_2dgs
 from .surfel import fully_fused_projection_2dgs, rasterize_to_pixels_2dgs
 from . import utils
+from .appearance import AppearanceOptModule
 from .version import __version__
 
 
@@ -46,4 +49,5 @@ __all__ = [
     "isect_tiles", "isect_offset_encode", "rasterize_to_pixels", "quat_scale_to_covar_preci", "proj", "persp_proj",
     "world_to_cam", "rasterize_to_indices_in_range", "accumulate", "selective_adam_update", "PngCompression", "__version__",
     "rasterization_2dgs", "fully_fused_projection_2dgs", "rasterize_to_pixels_2dgs", "utils",
+    "AppearanceOptModule",
 ]

@@ -47,7 +47,8 @@ extern "C" {
  * (gs_ans_histogram, gs_ans_encode_bytes, gs_ans_encode, gs_ans_pack, gs_ans_decode), and the grid-sort entries
  * (gs_gridsort_blur, gs_gridsort_keys, gs_gridsort_assign), and the 2D Gaussian splatting entries (gs_projection_2dgs_fwd / _bwd,
  * gs_rasterize_2dgs_fwd / _bwd, gs_depth_to_normal_fwd / _bwd), and the spacetime colour decoder's (gs_stg_decode_fwd / _bwd,
- * gs_stg_decode_partial_rows). */
+ * gs_stg_decode_partial_rows), and the appearance module's (gs_appearance_fwd / _bwd, gs_appearance_partial_rows,
+ * gs_appearance_partial_cols). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -1236,6 +1237,36 @@ int32_t gs_stg_decode_fwd(uint32_t C, uint32_t H, uint32_t W, const float *featu
 int32_t gs_stg_decode_bwd(uint32_t C, uint32_t H, uint32_t W, const float *features, int64_t pix_stride, const float *rays,
                           int64_t ray_cam_stride, int64_t ray_ch_stride, const float *w1, const float *w2, const float *v_out,
                           uint32_t max_blocks, float *v_features, float *partials, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * The static trainer's appearance module (--app_opt; reference examples/utils.py: AppearanceOptModule, called at
+ * examples/simple_trainer.py:766-774), csrc/appearance.hip.  Per camera c and splat n, with a hidden width of 64:
+ *   x = cat(embeds[c] [E], features[n] [F], bases(d / max(|d|, 1e-12)) [K]);  d = dirs[c, n], or means[n] - cam_centers[c] when dirs
+ *   is NULL;  the first num_bases = (sh_degree + 1)^2 <= K bases are Sloan's fast evaluation, the rest zero;
+ *   colors[c, n] = w3 relu(w2 relu(w1 x + b1) + b2) + b3 (+ base[n] when base is given), through a sigmoid when activate != 0.
+ * fp32, contiguous: features [N, F], embeds [C, E] (already gathered; NULL or E == 0: a zero embedding), dirs [C, N, 3], means [N, 3],
+ * cam_centers [C, 3], w1 [64, E + F + K], b1 [64], w2 [64, 64], b2 [64], w3 [3, 64], b3 [3] (torch's [out, in] layout), base [N, 3]
+ * or NULL, colors [C, N, 3].  1 <= F <= 96, 1 <= K <= 25, E + F + K <= 128.  max_blocks: cap of the grid (0 or anything above it = the library's default:
+ * two workgroups per CU forward, one backward).
+ * gs_appearance_bwd recomputes the activations from the same inputs and, from v_colors [C, N, 3], writes v_features [N, F], v_dirs
+ * [C, N, 3] (with dirs) or v_means [N, 3] (with means), v_base [N, 3] -- each may be NULL; the [N, .] ones are summed over the cameras
+ * inside the kernel -- and partials [R, L], R = gs_appearance_partial_rows(N, F, E, K, max_blocks), L =
+ * gs_appearance_partial_cols(C, F, K): row r holds one wave's sums of v_w1[:, E:] [64, F + K], v_w2 [64, 64], v_w3 [3, 64], v_b2
+ * [64], v_b3 [3], one float of padding, and d_pre [C, 64], the gradient of the per-camera pre-activation w1[:, :E] embeds[c] + b1.
+ * The caller adds the R rows; then v_b1 = sum_c d_pre[c], v_w1[:, :E] = d_pre^T embeds and v_embeds = d_pre w1[:, :E].  No float
+ * atomics: for one shape and max_blocks every output is bit-identical from run to run.  A direction of exactly zero has a finite
+ * forward value; its gradient is unspecified. */
+uint32_t gs_appearance_partial_rows(uint32_t N, uint32_t F, uint32_t E, uint32_t K, uint32_t max_blocks);
+uint64_t gs_appearance_partial_cols(uint32_t C, uint32_t F, uint32_t K);
+int32_t gs_appearance_fwd(uint32_t N, uint32_t C, uint32_t F, uint32_t E, uint32_t K, uint32_t num_bases, const float *features,
+                          const float *embeds, const float *dirs, const float *means, const float *cam_centers, const float *w1,
+                          const float *b1, const float *w2, const float *b2, const float *w3, const float *b3, const float *base,
+                          int32_t activate, uint32_t max_blocks, float *colors, gs_stream_t stream);
+int32_t gs_appearance_bwd(uint32_t N, uint32_t C, uint32_t F, uint32_t E, uint32_t K, uint32_t num_bases, const float *features,
+                          const float *embeds, const float *dirs, const float *means, const float *cam_centers, const float *w1,
+                          const float *b1, const float *w2, const float *b2, const float *w3, const float *b3, const float *base,
+                          int32_t activate, const float *v_colors, uint32_t max_blocks, float *v_features, float *v_dirs,
+                          float *v_means, float *v_base, float *partials, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * D1  The densification strategies (gsplat/strategy/default.py, mcmc.py, ops.py; gsplat/relocation.py).  One thread per
