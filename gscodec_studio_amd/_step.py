@@ -33,52 +33,7 @@ from . import _wrapper as W
 ENABLED = os.environ.get("GS_STEP_DRIVER", "1") != "0"
 
 
-class _Plan(ctypes.Structure):  # gs_raster_plan
-    _fields_ = [("magic", ctypes.c_uint32), ("n_tiles_all", ctypes.c_uint32), ("n_isects", ctypes.c_uint32), ("channels", ctypes.c_uint32),
-                ("seg", ctypes.c_int32), ("solo_min", ctypes.c_int32), ("xcd_fwd", ctypes.c_uint32), ("xcd_bwd", ctypes.c_uint32),
-                ("scratch_bytes", ctypes.c_uint64), ("reserved", ctypes.c_uint32 * 6)]
-
-
-_P, _U32, _I32, _U64, _F = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_float
-
-
-class _Step(ctypes.Structure):  # gs_step of include/gsplat_hip.h (field for field)
-    _fields_ = [
-        ("C", _U32), ("N", _U32),
-        ("means", _P), ("covars", _P), ("quats", _P), ("scales", _P), ("viewmats", _P), ("Ks", _P), ("opacities", _P), ("colors", _P),
-        ("sh_coeffs", _P), ("sh_rest", _P),
-        ("sh_K", _U32), ("sh_degree", _U32), ("width", _I32), ("height", _I32),
-        ("eps2d", _F), ("near_plane", _F), ("far_plane", _F), ("radius_clip", _F),
-        ("camera_model", _I32), ("antialiased", _I32), ("tile_size", _U32), ("tile_width", _U32), ("tile_height", _U32),
-        ("bucketed", _I32), ("lds_capacity", _U32), ("sh_mask_binary", _I32),
-        ("sh_mask_logits", _P), ("sh_mask_temperature", _F), ("rows_ready", _U32),
-        ("backgrounds", _P),
-        ("radii", _P), ("depths", _P), ("rows", _P), ("tiles_per_gauss", _P), ("depth_keys", _P), ("depth_vals", _P),
-        ("sort_temp", _P), ("sort_temp_bytes", _U64), ("splitters", _P), ("sorted_keys", _P), ("perm", _P), ("n_kept", _P),
-        ("group_sums", _P), ("group_prefix", _P), ("cumsum_scratch", _P), ("cumsum_scratch_bytes", _U64), ("block_sums", _P),
-        ("n_isects", _U64), ("n_kept_host", _U32), ("reserved1", _U32), ("isect_ids", _P), ("flatten_ids", _P), ("offsets", _P), ("work", _P), ("work_bytes", _U64),
-        ("render_colors", _P), ("render_alphas", _P), ("last_ids", _P), ("plan", _Plan), ("scratch", _P), ("zero_fill", _P),
-        ("zero_fill_bytes", _U64), ("finish_phase", _I32),
-        ("dyn_motion", _P), ("dyn_omega", _P), ("dyn_trbf_center", _P), ("dyn_trbf_scale", _P),
-        ("dyn_timestamp", _F), ("dyn_raw_params", _U32), ("dyn_quant_mask", _U32), ("dyn_min_trbf", _F),
-        ("dyn_quant_lo", _F * 4), ("dyn_quant_hi", _F * 4), ("dyn_quant_range", _F * 4), ("dyn_quant_step_norm", _F * 4),
-        ("dyn_trbf_alive", _P),
-    ]
-
-
-_LAYOUT_FIELDS = ("C", "sh_K", "eps2d", "tile_size", "sh_mask_logits", "rows_ready", "backgrounds", "radii", "sort_temp_bytes", "block_sums",
-                  "n_isects", "n_kept_host", "work_bytes", "plan", "scratch", "zero_fill_bytes", "finish_phase", "dyn_motion", "dyn_timestamp",
-                  "dyn_quant_lo", "dyn_trbf_alive")
-
-
-def check_layout() -> None:
-    """The ctypes mirror above against the library's own ``sizeof`` / ``offsetof`` of ``gs_step`` (``gs_step_layout``)."""
-    want = (ctypes.c_uint64 * 64)()
-    m = int(B.query("gs_step_layout", want, 64))
-    mine = [ctypes.sizeof(_Step)] + [getattr(_Step, f).offset for f in _LAYOUT_FIELDS]
-    if m != len(mine) or list(want[:m]) != mine:
-        raise ImportError(f"gs_step: the ctypes mirror in _step.py does not match the library's struct layout ({list(want[:m])} vs {mine})")
-
+_Step = B.struct("gs_step")  # fields, order and types as include/gsplat_hip.h declares them; B.lib() guards the layout
 
 _ROW_STRIDES = (ctypes.c_uint32 * 4)(W.ROW, W.ROW, W.ROW, W.ROW)
 
@@ -190,13 +145,13 @@ def _finish(s, sp, stream, bufs, C, N, height, width, tile_height, tile_width, d
     grad_rows = None
     if needs_bwd:
         fill, grad_rows, _, prefill = W._grad_fill(n_elems, 3, prefill, dev)
-        grad_rows = grad_rows.view(C, N, 16)
+        grad_rows = grad_rows.view(C, N, W.ROW)
         s.zero_fill, s.zero_fill_bytes = ptr(fill), fill.numel() * 4
     else:
         prefill = None
     s.render_colors, s.render_alphas, s.last_ids = ptr(render_colors), ptr(render_alphas), ptr(last_ids)
     plan, sbytes = W._raster_plan(C * tile_height * tile_width, n_isects, 3, forward_only=not needs_bwd)
-    ctypes.memmove(ctypes.addressof(s.plan), plan, 64)
+    s.plan = plan
     scratch = empty(sbytes, dtype=u8, device=dev)
     s.scratch = ptr(scratch)
     s.finish_phase = 2
@@ -366,7 +321,6 @@ _GSHIFT, _PREFIX_FROM = [0], [8192]
 
 
 def _init_consts() -> int:
-    check_layout()  # (once per process, before the first descriptor is handed to the library)
     _GSHIFT[0] = int(B.query("gs_isect_emit_group_shift"))
     _PREFIX_FROM[0] = int(B.query("gs_isect_emit_prefix_from_groups"))
     return _GSHIFT[0]

@@ -17,7 +17,6 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-import struct
 from typing import Optional, Tuple
 
 import torch
@@ -27,9 +26,11 @@ from typing_extensions import Literal
 from . import _backend as B
 from . import _readback as RB
 
-_CAMERA_MODELS = {"pinhole": 0, "ortho": 1, "fisheye": 2}
+# (every value the native side shares comes from include/gsplat_hip.h: B.const, B.struct)
+_CAMERA_MODELS = {"pinhole": B.const("GS_CAMERA_PINHOLE"), "ortho": B.const("GS_CAMERA_ORTHO"), "fisheye": B.const("GS_CAMERA_FISHEYE")}
 # splat rows (include/gsplat_hip.h): one 64-byte row of 16 floats per projected splat
-ROW, ROW_MEAN2D, ROW_CONIC, ROW_OPACITY, ROW_COLOR, ROW_DEPTH, ROW_RADIUS, ROW_COMP = 16, 0, 2, 5, 6, 9, 10, 11
+ROW, ROW_MEAN2D, ROW_CONIC, ROW_OPACITY, ROW_COLOR, ROW_DEPTH, ROW_RADIUS, ROW_COMP = (B.const("GS_ROW_" + c) for c in (
+    "FLOATS", "MEAN2D", "CONIC", "OPACITY", "COLOR", "DEPTH", "RADIUS", "COMPENSATION"))
 
 
 def _require_gpu(t: Tensor, what: str) -> None:
@@ -1584,16 +1585,19 @@ def set_raster_tuning(**kv) -> dict:
     return prev
 
 
+_RasterPlan = B.struct("gs_raster_plan")
+
+
 def _raster_plan(n_tiles_all: int, n_isects: int, channels: int, forward_only: bool = False):
-    """(plan buffer, scratch bytes): a gs_raster_plan (host struct, 64 bytes) for one forward / backward pair.
+    """(plan, scratch bytes): a gs_raster_plan (host struct) for one forward / backward pair.
     ``forward_only``: no backward will follow -- segment length 0, i.e. no checkpoints (the scratch then only holds the
     forward's tile order and cost counters)."""
-    plan = ctypes.create_string_buffer(64)
+    plan = _RasterPlan()
     tun = (ctypes.c_int32 * 5)(*_RASTER_TUNING)
     if forward_only:
         tun[0] = 0
     B.call("gs_rasterize_plan", n_tiles_all, n_isects, channels, ctypes.addressof(tun), ctypes.addressof(plan))
-    return plan, struct.unpack_from("<Q", plan, 32)[0]
+    return plan, plan.scratch_bytes
 
 
 def _splat_layout(means2d: Tensor, conics: Tensor, colors: Tensor, opacities: Tensor):
@@ -1731,11 +1735,11 @@ def _grad_fill(n_elems: int, channels: int, prefill: Optional[GradPrefill], dev)
     if extra:
         extra += 64  # slack behind the last piece (a multi-GPU reduction rounds the span of all pieces up into it)
     wide = _pad64(n_elems * channels) if _grad_layout(channels)[0] == 2 else 0
-    fill = torch.empty(n_elems * 16 + wide + extra, dtype=torch.float32, device=dev)
-    grad_colors = fill[n_elems * 16:n_elems * 16 + n_elems * channels] if wide else None
+    fill = torch.empty(n_elems * ROW + wide + extra, dtype=torch.float32, device=dev)
+    grad_colors = fill[n_elems * ROW:n_elems * ROW + n_elems * channels] if wide else None
     if extra:
-        prefill.carve(fill, n_elems * 16 + wide)
-    return fill, fill[:n_elems * 16], grad_colors, prefill if extra else None
+        prefill.carve(fill, n_elems * ROW + wide)
+    return fill, fill[:n_elems * ROW], grad_colors, prefill if extra else None
 
 
 def _save_composite(ctx, means2d, conics, colors, opacities, backgrounds, isect_offsets, flatten_ids, render_colors, render_alphas, last_ids,
@@ -1785,7 +1789,7 @@ class _RasterizeToPixels(torch.autograd.Function):
             grad_rows = grad_colors = fill = None
             if needs_bwd and _grad_layout(channels)[1] and n_elems > 0:
                 fill, grad_rows, grad_colors, _ = _grad_fill(n_elems, channels, prefill, dev)
-                grad_rows = grad_rows.view(opacities.shape + (16,))
+                grad_rows = grad_rows.view(opacities.shape + (ROW,))
                 if grad_colors is not None:
                     grad_colors = grad_colors.view(opacities.shape + (channels,))
             B.call("gs_rasterize_fwd", C, n_elems, n_isects, channels, B.ptr(means2d), B.ptr(conics), B.ptr(colors),
@@ -1834,11 +1838,11 @@ def _rasterize_bwd(ctx, v_render_colors: Optional[Tensor], v_render_alphas: Opti
             # (the deterministic route's finalize kernel WRITES every row -- except when there is nothing to composite:
             # gs_rasterize_bwd returns before it with n_isects == 0, and the rows must then be zeros, not stale memory)
             P = (torch.empty if (det is not None and n_isects > 0) else torch.zeros)(
-                opacities.shape + (16,), dtype=torch.float32, device=means2d.device)
-        v_means2d, v_conics, v_opacities = P[..., 0:2], P[..., 2:5], P[..., 5]
+                opacities.shape + (ROW,), dtype=torch.float32, device=means2d.device)
+        v_means2d, v_conics, v_opacities = P[..., ROW_MEAN2D:ROW_MEAN2D + 2], P[..., ROW_CONIC:ROW_CONIC + 3], P[..., ROW_OPACITY]
         v_means2d_abs = P[..., 10:12] if ctx.absgrad else None
         if packed16 == 1:
-            v_colors = P[..., 6:6 + channels]
+            v_colors = P[..., ROW_COLOR:ROW_COLOR + channels]
             out_ptrs = (B.ptr(P) if ctx.absgrad else None, B.ptr(P), None, None, None)
         else:  # geometry rows + the colour gradients in their own dense array
             v_colors, ctx.grad_colors = ctx.grad_colors, None
@@ -1874,29 +1878,8 @@ def _rasterize_bwd(ctx, v_render_colors: Optional[Tensor], v_render_alphas: Opti
 # ---------------------------------------------------------------------------
 # Adam / SelectiveAdam step  (reference _wrapper.py:19-34, csrc/adam.cu; torch.optim.adam._single_tensor_adam)
 # ---------------------------------------------------------------------------
-ADAM_DENSE, ADAM_SELECTIVE = 0, 1
-
-
-class _AdamDesc(ctypes.Structure):  # gs_adam_desc of include/gsplat_hip.h
-    _fields_ = [("n", ctypes.c_uint64), ("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
-                ("exp_avg_sq", ctypes.c_void_p), ("visibility", ctypes.c_void_p), ("rows", ctypes.c_uint32),
-                ("row_width", ctypes.c_uint32), ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
-                ("eps", ctypes.c_float), ("one_minus_beta1", ctypes.c_float), ("one_minus_beta2", ctypes.c_float),
-                ("step_size", ctypes.c_float), ("bias_correction2_sqrt", ctypes.c_float), ("mode", ctypes.c_int32)]
-
-
-_ADAM_DESC_CHECKED = [False]
-
-
-def check_adam_desc_layout() -> None:
-    """``_AdamDesc`` against the library's ``sizeof`` / ``offsetof`` of ``gs_adam_desc``."""
-    want = (ctypes.c_uint64 * 16)()
-    m = int(B.query("gs_adam_desc_layout", want, 16))
-    mine = [ctypes.sizeof(_AdamDesc)] + [getattr(_AdamDesc, f).offset for f in ("n", "param", "grad", "exp_avg", "exp_avg_sq", "visibility",
-                                                                                 "rows", "row_width", "lr", "step_size", "mode")]
-    if m != len(mine) or list(want[:m]) != mine:
-        raise ImportError(f"gs_adam_desc: the ctypes mirror in _wrapper.py does not match the library's struct layout ({list(want[:m])} vs {mine})")
-    _ADAM_DESC_CHECKED[0] = True
+ADAM_DENSE, ADAM_SELECTIVE = B.const("GS_ADAM_DENSE"), B.const("GS_ADAM_SELECTIVE")
+_AdamDesc = B.struct("gs_adam_desc")
 
 
 def adam_dense_scalars(lr: float, beta1: float, beta2: float, step: float) -> Tuple[float, float, float, float]:
@@ -1927,8 +1910,6 @@ def adam_multi(descs, like: Tensor) -> None:
     """Launch ``gs_adam_multi`` over ``descs`` (a list of ``_AdamDesc``, tensors on ``like``'s device) on the current stream."""
     if not descs:
         return
-    if not _ADAM_DESC_CHECKED[0]:
-        check_adam_desc_layout()
     table = (_AdamDesc * len(descs))(*descs)
     with _device_of(like):
         B.call("gs_adam_multi", len(descs), ctypes.addressof(table), _stream(like))
@@ -1961,7 +1942,7 @@ def selective_adam_update(param: Tensor, param_grad: Tensor, exp_avg: Tensor, ex
 # ---------------------------------------------------------------------------
 # SSIM / L1 photometric loss  (the fused_ssim package's fused_ssim; csrc/loss.hip)
 # ---------------------------------------------------------------------------
-SSIM_PADDING = {"same": 0, "valid": 1}
+SSIM_PADDING = {"same": B.const("GS_SSIM_SAME"), "valid": B.const("GS_SSIM_VALID")}
 
 
 def _strides4(strides) -> ctypes.Array:

@@ -32,7 +32,7 @@ def _f32(v: float) -> float:
     return float(np.float32(v))
 
 
-_ACTS = {None: 0, "exp": 1, "sigmoid": 2}  # GS_ACT_* of include/gsplat_hip.h
+_ACTS = {None: B.const("GS_ACT_NONE"), "exp": B.const("GS_ACT_EXP"), "sigmoid": B.const("GS_ACT_SIGMOID")}
 
 
 class _NoiseQuant(torch.autograd.Function):
@@ -97,25 +97,8 @@ class STE(torch.autograd.Function):
         return v_x, None, None, None, None
 
 
-class _QuantDesc(ctypes.Structure):  # gs_quant_desc of include/gsplat_hip.h
-    _fields_ = [("n", ctypes.c_uint64), ("x", ctypes.c_void_p), ("out", ctypes.c_void_p), ("v_out", ctypes.c_void_p),
-                ("v_x", ctypes.c_void_p), ("lo", ctypes.c_float), ("hi", ctypes.c_float), ("q_step", ctypes.c_float),
-                ("activation", ctypes.c_int32), ("philox_offset", ctypes.c_uint64)]
-
-
-QUANT_MULTI_MAX = 8
-_DESC_CHECKED = [False]
-
-
-def check_desc_layout() -> None:
-    """``_QuantDesc`` against the library's ``sizeof`` / ``offsetof`` of ``gs_quant_desc``."""
-    want = (ctypes.c_uint64 * 16)()
-    m = int(B.query("gs_quant_desc_layout", want, 16))
-    mine = [ctypes.sizeof(_QuantDesc)] + [getattr(_QuantDesc, f).offset for f in ("n", "x", "out", "v_out", "v_x", "lo", "q_step", "activation",
-                                                                                  "philox_offset")]
-    if m != len(mine) or list(want[:m]) != mine:
-        raise ImportError(f"gs_quant_desc: the ctypes mirror in ops.py does not match the library's struct layout ({list(want[:m])} vs {mine})")
-    _DESC_CHECKED[0] = True
+_QuantDesc = B.struct("gs_quant_desc")
+QUANT_MULTI_MAX = B.const("GS_QUANT_MULTI_MAX")
 _GRID_CAP: Dict[int, int] = {}
 
 
@@ -136,8 +119,6 @@ class _NoiseQuantMulti(torch.autograd.Function):
     @staticmethod
     def forward(ctx, specs: Sequence[Tuple[float, float, float, int]], *xs: Tensor):
         dev = xs[0].device
-        if not _DESC_CHECKED[0]:
-            check_desc_layout()
         for x in xs:
             _require_gpu(x, "fake_quantize_ste")
             if x.dtype != torch.float32 or x.device != dev:
@@ -248,8 +229,6 @@ class _RoundQuantMulti(torch.autograd.Function):
     @staticmethod
     def forward(ctx, specs: Sequence[Tuple[float, float, int, int]], *xs: Tensor):
         dev = xs[0].device
-        if not _DESC_CHECKED[0]:
-            check_desc_layout()
         for x in xs:
             _require_gpu(x, "STE")
             if x.dtype != torch.float32 or x.device != dev or not x.is_contiguous():

@@ -90,7 +90,7 @@ def temporal_slice(
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-_RAW_BITS = {"scales": 1, "opacities": 2, "trbf_scale": 4}  # GS_DYN_RAW_* of include/gsplat_hip.h
+_RAW_BITS = {"scales": B.const("GS_DYN_RAW_SCALES"), "opacities": B.const("GS_DYN_RAW_OPACITIES"), "trbf_scale": B.const("GS_DYN_RAW_TRBF_SCALE")}
 _QUANT_SLOTS = ("scales", "quats", "opacities", "colors")   # bit k of quant_mask
 _F4 = ctypes.c_float * 4
 

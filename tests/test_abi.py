@@ -111,29 +111,46 @@ def test_cpu_tensors_are_rejected_not_emulated():
         fake_quantize_ste(torch.randn(10), -1, 1, 8, "round")
 
 
-def test_host_struct_mirrors_match_the_library_layout():
-    """The two host structs that cross the boundary by pointer (gs_step, gs_quant_desc) are mirrored by hand in ctypes: the
-    library reports its own sizeof / offsetof (gs_step_layout, gs_quant_desc_layout) and the mirrors must agree; a mirror that
-    drifts is refused before a descriptor is ever handed over."""
-    import ctypes
-
-    from gscodec_studio_amd import _step
+def test_host_struct_mirrors_match_the_library_layout(tmp_path):
+    """The host structs that cross the boundary by pointer (gs_step, gs_quant_desc, gs_adam_desc) are ctypes classes derived from
+    the header: the library reports its own sizeof / offsetof (gs_step_layout, gs_quant_desc_layout, gs_adam_desc_layout) and the
+    classes must agree; a header that drifted from the library is refused before a descriptor is ever handed over.  Names and order
+    come from the header too, so two same-typed neighbours cannot be swapped behind the guard's back."""
+    from gscodec_studio_amd import _backend as B
+    from gscodec_studio_amd import _step, _wrapper
     from gscodec_studio_amd.compression_simulation import ops
 
-    _step.check_layout()
-    ops.check_desc_layout()
-    assert int(_step.B.query("gs_step_layout", None, 0)) == 1 + len(_step._LAYOUT_FIELDS)
+    B.check_layouts()  # gs_step, gs_quant_desc and gs_adam_desc, each against its own entry point
+    assert set(B._LAYOUT_GUARDS) == {"gs_step", "gs_quant_desc", "gs_adam_desc"}
+    # what lib() guarded (the default header's classes) are the very objects the modules build their descriptors from
+    guarded = B._header().structs
+    assert B._header() is B._header(B.HEADER_PATH)
+    assert _step._Step is guarded["gs_step"] and ops._QuantDesc is guarded["gs_quant_desc"] and _wrapper._AdamDesc is guarded["gs_adam_desc"]
+    assert _wrapper._RasterPlan is guarded["gs_raster_plan"] is dict(_step._Step._fields_)["plan"]
+    for name, (entry, guarded) in B._LAYOUT_GUARDS.items():  # (gs_step_layout(None, 0) == 1 + len(its guarded field list), and so on)
+        assert int(B.query(entry, None, 0)) == 1 + len(guarded), name
 
-    class Drift(ctypes.Structure):  # a field too many in the middle: everything behind it moves
-        _fields_ = _step._Step._fields_[:5] + [("extra", ctypes.c_uint64)] + _step._Step._fields_[5:]
+    src = open(B.HEADER_PATH).read()
+    # a field too many in the middle of gs_step: everything behind it moves
+    drift = tmp_path / "drift.h"
+    anchor = "    uint32_t sh_K, sh_degree;\n"
+    assert src.count(anchor) == 1
+    drift.write_text(src.replace(anchor, anchor + "    uint64_t extra;\n"))
+    assert "extra" in [f[0] for f in B.struct("gs_step", str(drift))._fields_]
+    with pytest.raises(ImportError, match="struct layout"):
+        B.check_layouts(str(drift))
 
-    real = _step._Step
-    _step._Step = Drift
-    try:
-        with pytest.raises(ImportError, match="struct layout"):
-            _step.check_layout()
-    finally:
-        _step._Step = real
+    # two same-typed neighbours swapped (what a hand-written mirror could get wrong unnoticed): the class follows the header
+    swap = tmp_path / "swap.h"
+    pointers = "const float *means, *covars, *quats"
+    assert src.count(pointers) == 1
+    swap.write_text(src.replace(pointers, "const float *covars, *means, *quats").replace(
+        "uint32_t tile_size, tile_width, tile_height;", "uint32_t tile_size, tile_height, tile_width;"))
+    real = [f[0] for f in B.struct("gs_step")._fields_]
+    swapped = [f[0] for f in B.struct("gs_step", str(swap))._fields_]
+    assert real != swapped and sorted(real) == sorted(swapped)
+    assert real.index("means") + 1 == real.index("covars") and swapped.index("covars") + 1 == swapped.index("means")
+    assert real.index("tile_width") + 1 == real.index("tile_height") and swapped.index("tile_height") + 1 == swapped.index("tile_width")
 
 
 def test_product_never_imports_the_oracle():

@@ -88,7 +88,7 @@ def test_adam_multi_is_declared_exported_and_mirrored():
         assert hasattr(B.lib(), name), name
     hdr = open(os.path.join(ROOT, "include", "gsplat_hip.h")).read()
     assert int(re.search(r"#define GS_ADAM_MULTI_MAX (\d+)", hdr).group(1)) == int(B.query("gs_adam_multi_max"))
-    W.check_adam_desc_layout()
+    B.check_layouts()  # (gs_adam_desc among them)
     # a bad descriptor is refused before anything is launched (no device needed to reach the check)
     bad = W._AdamDesc()
     bad.n, bad.mode = 16, 7
