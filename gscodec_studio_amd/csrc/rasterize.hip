@@ -4,7 +4,8 @@
 // Replaces gsplat/cuda/csrc/rasterize_to_pixels_fwd.cu:16-185 and
 // rasterize_to_pixels_bwd.cu:17-277.  Same per-pixel arithmetic and decisions
 // (alpha = min(0.999, o * exp(-sigma)); skip sigma < 0 or alpha < 1/255; exclusive stop when
-// T (1 - alpha) <= 1e-4; last_ids; alpha-clamp gradient gate), different mapping:
+// T (1 - alpha) <= 1e-4; last_ids; alpha-clamp gradient gate -- splat_sample and the constants beside it in
+// rasterize_dev.h, the one definition every kernel here and in rasterize_wide.hip uses), different mapping:
 //
 //   * ONE WAVE64 OWNS ONE 16x16 TILE; lane (lx, ly) of an 8x8 grid owns FOUR pixels, one in
 //     each 8x8 quadrant.  No workgroup barriers (the reference's 256-thread block needs two
@@ -53,7 +54,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "rasterize_dev.h"
+#include "rasterize_seg_dev.h"
 
 namespace {
 
@@ -204,15 +205,12 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_fwd_kernel(RasterArgs a, 
 #pragma unroll
             for (int i = 0; i < NQ; ++i) {
                 const float dx = c0.x - px[i], dy = c0.y - py[i];
-                // the same arithmetic as the tile kernels (exponent with log2(opacity) in its last fma, "sigma < 0" read as
-                // pl > log2(opacity)): every compositing kernel takes bit-identical accept decisions
-                const float pl = __builtin_fmaf(dx, __builtin_fmaf(c0.w, dy, c0.z * dx), __builtin_fmaf(c1.x * dy, dy, c1.y));
-                const float alpha = fminf(0.999f, __builtin_amdgcn_exp2f(pl));
-                const bool ok = rec_ok && !(pl > c1.y) && (alpha >= ALPHA_MIN);
-                const float a_eff = ok ? alpha : 0.f;
+                SplatSample sm;
+                const bool ok = splat_sample(dx, dy, c0.z, c0.w, c1.x, c1.y, sm, rec_ok);
+                const float a_eff = ok ? sm.alpha : 0.f;
                 const float Tj = T[i];
                 const float next_T = Tj - Tj * a_eff;         // the loop-carried chain
-                const bool stop = ok && (next_T <= 1e-4f);    // exclusive stop
+                const bool stop = ok && (next_T <= T_MIN);     // exclusive stop
                 const bool live = !done[i] && !stop;          // this record is composited
                 Tkeep[i] = done[i] ? Tkeep[i] : Tj;           // transmittance before the stopping splat
                 const float vis = live ? a_eff * Tj : 0.f;
@@ -483,13 +481,9 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
                     const float dx = c0[g].x - px, dy = c0[g].y - py;
-                    // pl = power + log2(opacity), power = -sigma log2(e) = dx (a' dx + b' dy) + c' dy^2; the constant rides in
-                    // the last fma, and "sigma < 0" (reject) is read off as pl > log2(opacity): the two differ only for
-                    // |sigma| below the rounding of pl, where the sign of a computed sigma is rounding noise in any case
-                    const float lo = c1[g].y;
-                    const float pl = __builtin_fmaf(dx, __builtin_fmaf(c0[g].w, dy, c0[g].z * dx), __builtin_fmaf(c1[g].x * dy, dy, lo));
-                    alpha[g] = fminf(0.999f, __builtin_amdgcn_exp2f(pl));
-                    ok[g] = !(pl > lo) && (alpha[g] >= ALPHA_MIN);
+                    SplatSample sm;
+                    ok[g] = splat_sample(dx, dy, c0[g].z, c0[g].w, c1[g].x, c1[g].y, sm);
+                    alpha[g] = sm.alpha;
                 }
                 // T is FROZEN at the stopping splat (= the transmittance in front of it, what the epilogue and the
                 // checkpoints need), so a live pixel always has T > 1e-4 and a rejected record (a_eff = 0) cannot stop it
@@ -499,7 +493,7 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
                     // select (the alpha actually applied: 0 for a finished or finishing pixel) instead of separate selects
                     // for the weight and for T -- T is then recomputed with it (a second fma is cheaper than a select)
                     const float Tj = T;
-                    const bool stop = ok[g] && (__builtin_fmaf(-Tj, alpha[g], Tj) <= 1e-4f);
+                    const bool stop = ok[g] && (__builtin_fmaf(-Tj, alpha[g], Tj) <= T_MIN);
                     done = done || stop;
                     const bool use = ok[g] && !done; // composited: accepted, and the pixel neither finished nor finishing
                     const float a_use = use ? alpha[g] : 0.f;
@@ -929,10 +923,9 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_bwd_kernel(RasterArgs a, 
 #pragma unroll
             for (int i = 0; i < NQ; ++i) {
                 const float dx = c0.x - px[i], dy = c0.y - py[i];
-                const float pl = __builtin_fmaf(dx, __builtin_fmaf(c0.w, dy, c0.z * dx), __builtin_fmaf(c1.x * dy, dy, c1.y));
-                const float araw = __builtin_amdgcn_exp2f(pl); // = o exp(-sigma)
-                const float alpha = fminf(0.999f, araw);
-                const bool valid = (idx <= bin_final[i]) && !(pl > c1.y) && (alpha >= ALPHA_MIN);
+                SplatSample sm;
+                const bool valid = splat_sample(dx, dy, c0.z, c0.w, c1.x, c1.y, sm, idx <= bin_final[i]);
+                const float araw = sm.araw, alpha = sm.alpha;
                 any_valid |= valid;
                 const float ra = __builtin_amdgcn_rcpf(1.f - alpha);
                 const float Tn = T[i] * ra;
@@ -950,8 +943,8 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_bwd_kernel(RasterArgs a, 
                 }
                 facs[i] = facv;
                 const float v_alpha = D * Tn + (Tw[i] - Bq[i]) * ra;
-                // gradient gate: nothing for conic / xy / opacity when o * vis > 0.999
-                const float v_sigma = (valid && araw <= 0.999f) ? -araw * v_alpha : 0.f;
+                // gradient gate: nothing for conic / xy / opacity when o * vis > ALPHA_MAX (`&`: see seg_sample)
+                const float v_sigma = (valid & (araw <= ALPHA_MAX)) ? -araw * v_alpha : 0.f;
                 Bq[i] += facv * D;
                 T[i] = valid ? Tn : T[i];
                 const float sdx = v_sigma * dx, sdy = v_sigma * dy;
@@ -1040,6 +1033,9 @@ void launch_bwd(const RasterArgs &a, const RasterGradArgs &ga, uint32_t cnt, uin
 //     counts here, and a splat typically touches ~2 of the 4 quadrants;
 //   * the 6 + CDIM (+2) per-splat sums are reduced by hand-scheduled interleaved v_add_f32_dpp
 //     chains (dpp_reduce.h): 6 instructions per value, no moves, no hazards.
+// Work-item lookup, gather, per-pixel state, batch staging, the sample body and the moments -> geometry gradients are the
+// stages of rasterize_seg_dev.h, shared with raster_seg_bwd_wide_kernel (here over all CDIM channels, ChanAll); the walk
+// (software-pipelined by two), the reductions and the grad_add layouts below are this kernel's own.
 // record: R0 = (mx, my, a', b')  R1 = (c', log2 o, col0, col1)  R2 = (col2, col3, a, b)  R3 = (c, o, g, -)
 // ---------------------------------------------------------------------------
 #ifndef GS_SEG_WAVES
@@ -1052,129 +1048,31 @@ __global__ void __launch_bounds__(GS_WAVE, GS_SEG_WAVES) raster_seg_bwd_kernel(R
     __shared__ float4 s_rec[GS_WAVE * REC];
     __shared__ float4 s_acc[GS_WAVE * ACC];
     const uint32_t lane = threadIdx.x;
-    const uint32_t lx = lane & 7u, ly = lane >> 3;
-    // block index -> item: the classes in order of decreasing cost (the grid is an upper bound on the total)
-    uint32_t n_work = 0;
-#pragma unroll 8
-    for (int c = 0; c < COST_CLASSES; ++c) n_work += sg.class_count[c];
-    if (blockIdx.x >= n_work) return;
-    uint32_t r = xcd_remap(blockIdx.x, n_work, a.xcd_group);
-    int cls = COST_CLASSES - 1;
-    for (; cls > 0; --cls) {
-        const uint32_t nc = sg.class_count[cls];
-        if (r < nc) break;
-        r -= nc;
-    }
-    const uint2 it = sg.items[(size_t)cls * sg.max_items + r];
-    const int32_t seg_k = (int32_t)it.y;
-    TileGeom tg = tile_geom(a, it.x);
-    if (a.masks != nullptr && !a.masks[tg.lin]) return;
-    const int32_t tile_end = tg.range_end;
-    tg.range_start = max(tg.range_start, seg_k * sg.seg);
-    tg.range_end = min(tg.range_end, (seg_k + 1) * sg.seg);
-    const bool from_ckpt = tg.range_end < tile_end;
+    constexpr ChanAll<CDIM> ch{};
+    TileGeom tg;
+    int32_t seg_k;
+    bool from_ckpt;
+    if (!seg_item(a, sg, tg, seg_k, from_ckpt)) return;
 
     // issue the first batch's gathers before anything else: their latency overlaps the pixel-state
     // loads below.  The walk starts at the segment's far end; entries behind every pixel's
     // last_ids are dropped by the per-quadrant test (idx <= q_bin_max).
     const int32_t first = tg.range_end - 1;
-    auto fetch = [&](int32_t idx, SplatRaw &s, float *col) {
-        s.g = 0;
-        s.mx = s.my = s.ca = s.cb = s.cc = s.opac = 0.f;
-#pragma unroll
-        for (int k = 0; k < CDIM; ++k) col[k] = 0.f;
-        if (idx >= tg.range_start) fetch_splat<CDIM>(a, a.flatten_ids[idx], s, col);
-    };
     SplatRaw nxt;
     float ncol[CDIM];
-    fetch(first - (int32_t)lane, nxt, ncol);
+    seg_fetch<CDIM>(a, first - (int32_t)lane, tg.range_start, ch, nxt, ncol);
 
-    bool inside[4];
-    float T[4], Wq[4], vc[4][CDIM]; // Wq = T_final (v_alpha_out - bg . v_out) - B  (the only way Tw and B are used)
-    const float px0 = (float)(tg.px0 + lx) + 0.5f, py0 = (float)(tg.py0 + ly) + 0.5f; // quadrant i: + 8 (i&1), + 8 (i>>1)
-    int32_t bin_final[4], q_bin_max[4];
-    float qx0[4], qx1[4], qy0[4], qy1[4];
-    unsigned q_live = 0;
-    const float *bg = a.backgrounds ? a.backgrounds + (size_t)tg.cam * a.channels : nullptr;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t ox = lx + 8u * (i & 1), oy = ly + 8u * (i >> 1);
-        const uint32_t x = tg.px0 + ox, y = tg.py0 + oy;
-        inside[i] = ox < a.tile_size && oy < a.tile_size && x < a.image_width && y < a.image_height;
-        const size_t pix = inside[i] ? ((size_t)tg.cam * a.image_height + y) * a.image_width + x : 0;
-        const float T_final = inside[i] ? 1.f - ga.render_alphas[pix] : 1.f;
-        T[i] = T_final;
-        float bg_dot = 0.f;
-#pragma unroll
-        for (int k = 0; k < CDIM; ++k) {
-            vc[i][k] = inside[i] ? ga.v_render_colors[pix * ga.s_vrc_pix + k * ga.s_vrc_ch] : 0.f;
-            if (bg != nullptr) bg_dot += bg[k] * vc[i][k];
-        }
-        const float v_a = (inside[i] && use_v_alpha) ? ga.v_render_alphas[pix] : 0.f;
-        Wq[i] = T_final * (v_a - bg_dot);
-        bin_final[i] = inside[i] ? ga.last_ids[pix] : -1;
-        if (from_ckpt && inside[i]) {
-            const float *cb = sg.ckpt + (size_t)(seg_k + 1) * (CDIM + 1) * 256 + i * 64 + lane;
-            T[i] = cb[0];
-            float bsum = 0.f;
-#pragma unroll
-            for (int k = 0; k < CDIM; ++k) {
-                float fin = sg.render_colors[pix * CDIM + k];
-                if (bg != nullptr) fin -= T_final * bg[k];
-                bsum += vc[i][k] * (fin - cb[(k + 1) * 256]);
-            }
-            Wq[i] -= bsum;
-        }
-        q_bin_max[i] = __builtin_amdgcn_readfirstlane(wave_max_i32(bin_final[i])); // make it an SGPR
-        if (q_bin_max[i] >= tg.range_start) q_live |= 1u << i;
-        // quadrant rectangle (pixel centres), clipped to tile size and image
-        const float X0 = (float)(tg.px0 + 8u * (i & 1)) + 0.5f, Y0 = (float)(tg.py0 + 8u * (i >> 1)) + 0.5f;
-        auto sgpr = [](float v) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v))); };
-        qx0[i] = sgpr(X0);
-        qy0[i] = sgpr(Y0);
-        qx1[i] = sgpr(fminf(X0 + 7.f, fminf((float)(tg.px0 + a.tile_size) - 0.5f, (float)a.image_width - 0.5f)));
-        qy1[i] = sgpr(fminf(Y0 + 7.f, fminf((float)(tg.py0 + a.tile_size) - 0.5f, (float)a.image_height - 0.5f)));
-    }
-    if (q_live == 0u) return; // nothing composited in this segment for any pixel
+    SegPixels<CDIM> px;
+    seg_pixels_init<CDIM>(a, ga, use_v_alpha, sg, tg, seg_k, from_ckpt, ch, lane, px);
+    if (px.q_live == 0u) return; // nothing composited in this segment for any pixel
     const int32_t total = first - tg.range_start + 1;
     const int32_t num_batches = (total + GS_WAVE - 1) / GS_WAVE;
 
     for (int32_t b = 0; b < num_batches; ++b) {
         const int32_t batch_end = first - b * GS_WAVE; // slot t holds list index batch_end - t
         unsigned long long qm[4];
-        {
-        const SplatRaw s = nxt;
-        CullSplat cs;
-        const int32_t my_idx = batch_end - (int32_t)lane;
-        const bool live = (my_idx >= tg.range_start) && cull_prepare(s, cs);
-        // Pixels whose last contributor lies in front of this batch take no part in it (idx <= bin_final fails for every
-        // entry): the splats are culled against the bounding rectangle of the pixels that ARE still in play, not against
-        // the whole quadrant.  Most pixels saturate a third of the way into their tile's list, so towards the far end of a
-        // list a quadrant is often down to a handful of pixels.  Exact: a culled splat has alpha < 1/255 on every pixel
-        // that can use it.
-        const int32_t batch_lo = max(tg.range_start, batch_end - (GS_WAVE - 1));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const unsigned long long in_play = __ballot(bin_final[i] >= batch_lo);
-            qm[i] = 0ull;
-            if (((q_live >> i) & 1u) && in_play != 0ull) { // (wave-uniform)
-                const LiveRect lr = live_rect(in_play, qx0[i], qy0[i]);
-                const bool touch = live && (my_idx <= q_bin_max[i]) && rect_touch(s, cs, lr.x0, lr.x1, lr.y0, lr.y1);
-                qm[i] = __ballot(touch);
-            }
-        }
-        {
-            float c0 = ncol[0], c1 = 0.f, c2 = 0.f, c3 = 0.f;
-            if (CDIM > 1) c1 = ncol[CDIM > 1 ? 1 : 0];
-            if (CDIM > 2) c2 = ncol[CDIM > 2 ? 2 : 0];
-            if (CDIM > 3) c3 = ncol[CDIM > 3 ? 3 : 0];
-            s_rec[lane * REC + 0] = make_float4(s.mx, s.my, -0.5f * LOG2E * s.ca, -LOG2E * s.cb);
-            s_rec[lane * REC + 1] = make_float4(-0.5f * LOG2E * s.cc, __log2f(s.opac), c0, c1);
-            s_rec[lane * REC + 2] = make_float4(c2, c3, s.ca, s.cb);
-            s_rec[lane * REC + 3] = make_float4(s.cc, s.opac, __int_as_float(s.g), 0.f);
-        }
-        }
-        if (b + 1 < num_batches) fetch(first - (b + 1) * GS_WAVE - (int32_t)lane, nxt, ncol);
+        seg_stage<CDIM>(nxt, ncol, batch_end, tg.range_start, lane, px, qm, &s_rec[lane * REC]);
+        if (b + 1 < num_batches) seg_fetch<CDIM>(a, first - (b + 1) * GS_WAVE - (int32_t)lane, tg.range_start, ch, nxt, ncol);
         __builtin_amdgcn_wave_barrier();
 
         unsigned long long any = qm[0] | qm[1] | qm[2] | qm[3];
@@ -1201,69 +1099,25 @@ __global__ void __launch_bounds__(GS_WAVE, GS_SEG_WAVES) raster_seg_bwd_kernel(R
             if (CDIM > 1) col[CDIM > 1 ? 1 : 0] = r1.w;
             if (CDIM > 2) col[CDIM > 2 ? 2 : 0] = r2.x;
             if (CDIM > 3) col[CDIM > 3 ? 3 : 0] = r2.y;
-            const int32_t idx = batch_end - t;
             const unsigned long long bit = 1ull << t;
-            float S0 = 0.f, Sx = 0.f, Sy = 0.f, Sxx = 0.f, Sxy = 0.f, Syy = 0.f, Ax = 0.f, Ay = 0.f;
-            float Cs[CDIM];
-#pragma unroll
-            for (int k = 0; k < CDIM; ++k) Cs[k] = 0.f;
-            float av_sum = 0.f; // > 0 in the lanes with a valid sample in some quadrant (one add per pass; a lane-mask "or" costs four scalar instructions per pass)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (!(qm[i] & bit)) continue; // wave-uniform (scalar) branch
-                const float dx = r0.x - (px0 + 8.f * (float)(i & 1)), dy = r0.y - (py0 + 8.f * (float)(i >> 1));
-                // pl = power + log2(opacity) with the constant riding in the last fma; "sigma < 0" reads pl > log2(opacity)
-                // (as in the forward: the two differ only where the sign of a computed sigma is rounding noise)
-                const float lo2 = r1.y;
-                const float pl = __builtin_fmaf(dx, __builtin_fmaf(r0.w, dy, r0.z * dx), __builtin_fmaf(r1.x * dy, dy, lo2));
-                const float araw = __builtin_amdgcn_exp2f(pl); // = o exp(-sigma)
-                const float alpha = fminf(0.999f, araw);
-                const bool valid = (idx <= bin_final[i]) && !(pl > lo2) && (alpha >= ALPHA_MIN);
-                // a rejected record gets alpha = 0: then ra = rcp(1) = 1 exactly, Tn = T and facv = 0, i.e. the
-                // transmittance and the colour sums need no select of their own (selects cost 1.5 issue units here)
-                const float av = valid ? alpha : 0.f;
-                av_sum += av;
-                const float ra = __builtin_amdgcn_rcpf(1.f - av);
-                const float Tn = T[i] * ra;
-                const float facv = av * Tn;
-                float D = 0.f;
-#pragma unroll
-                for (int k = 0; k < CDIM; ++k) {
-                    D += col[k] * vc[i][k];
-                    Cs[k] += facv * vc[i][k];
-                }
-                const float v_alpha = D * Tn + Wq[i] * ra;
-                const float v_sigma = (valid && araw <= 0.999f) ? -araw * v_alpha : 0.f;
-                Wq[i] -= facv * D;
-                T[i] = Tn;
-                const float sdx = v_sigma * dx, sdy = v_sigma * dy;
-                S0 += v_sigma;
-                Sx += sdx;
-                Sy += sdy;
-                Sxx += sdx * dx;
-                Sxy += sdx * dy;
-                Syy += sdy * dy;
-                if (ABS) {
-                    Ax += fabsf(r2.z * sdx + r2.w * sdy);
-                    Ay += fabsf(r2.w * sdx + r3.x * sdy);
-                }
-            }
-            if (!__any(av_sum > 0.f)) return;
+            SegSums<CDIM> sm;
+            seg_sample<CDIM, ABS>(r0, r1.x, r1.y, col, r2.z, r2.w, r3.x, batch_end - t, bit, qm, px, sm);
+            if (!__any(sm.av_sum > 0.f)) return;
             // 8 values through the permlane butterfly (20 VALU), the rest through plain DPP chains.
             // slot floats: [Sx, Sy | Sxx, Sxy | Syy, S0 | C0, C1 | C2, C3, Ax, Ay]
             float lo, hi;
-            const float C1v = CDIM > 1 ? Cs[CDIM > 1 ? 1 : 0] : 0.f;
-            float C2v = CDIM > 2 ? Cs[CDIM > 2 ? 2 : 0] : 0.f, C3v = CDIM > 3 ? Cs[CDIM > 3 ? 3 : 0] : 0.f;
+            const float C1v = CDIM > 1 ? sm.Cs[CDIM > 1 ? 1 : 0] : 0.f;
+            float C2v = CDIM > 2 ? sm.Cs[CDIM > 2 ? 2 : 0] : 0.f, C3v = CDIM > 3 ? sm.Cs[CDIM > 3 ? 3 : 0] : 0.f;
             // RGB without absgrad (the hot case): the ninth sum rides in the row reduction of the butterfly and is stored as
             // its four row partials (added up at the flush, once per batch) -- 4 DPP adds instead of a chain of 6 with padding
             constexpr bool ROW3 = !ABS && CDIM == 3;
-            if (ROW3) wave_reduce_sum_8_butterfly_rows(Sx, Syy, Sxx, Cs[0], Sy, S0, Sxy, C1v, lo, hi, C2v);
-            else wave_reduce_sum_8_butterfly(Sx, Syy, Sxx, Cs[0], Sy, S0, Sxy, C1v, lo, hi);
+            if (ROW3) wave_reduce_sum_8_butterfly_rows(sm.Sx, sm.Syy, sm.Sxx, sm.Cs[0], sm.Sy, sm.S0, sm.Sxy, C1v, lo, hi, C2v);
+            else wave_reduce_sum_8_butterfly(sm.Sx, sm.Syy, sm.Sxx, sm.Cs[0], sm.Sy, sm.S0, sm.Sxy, C1v, lo, hi);
             if (ROW3) {
             } else if (ABS) {
-                if (CDIM > 3) wave_reduce_sum_4(C2v, C3v, Ax, Ay);
-                else if (CDIM > 2) wave_reduce_sum_3(C2v, Ax, Ay);
-                else wave_reduce_sum_2(Ax, Ay);
+                if (CDIM > 3) wave_reduce_sum_4(C2v, C3v, sm.Ax, sm.Ay);
+                else if (CDIM > 2) wave_reduce_sum_3(C2v, sm.Ax, sm.Ay);
+                else wave_reduce_sum_2(sm.Ax, sm.Ay);
             } else {
                 if (CDIM > 3) wave_reduce_sum_2(C2v, C3v);
                 else if (CDIM > 2) wave_reduce_sum_1(C2v);
@@ -1277,7 +1131,7 @@ __global__ void __launch_bounds__(GS_WAVE, GS_SEG_WAVES) raster_seg_bwd_kernel(R
                 reinterpret_cast<float2 *>(acc)[row] = make_float2(lo, hi);
                 if (ROW3) acc[8 + row] = C2v; // the four row partials of C2 in the slot's third float4
             }
-            if (!ROW3 && lane == GS_WAVE - 1) s_acc[t * ACC + 2] = make_float4(C2v, C3v, Ax, Ay);
+            if (!ROW3 && lane == GS_WAVE - 1) s_acc[t * ACC + 2] = make_float4(C2v, C3v, sm.Ax, sm.Ay);
         };
         {
             Rec ra, rb;
@@ -1301,12 +1155,11 @@ __global__ void __launch_bounds__(GS_WAVE, GS_SEG_WAVES) raster_seg_bwd_kernel(R
             // lane = (slot, component): the <= 12 components of a splat go out as ONE request to ONE
             // 64-byte line instead of 9-11 requests to 4 arrays (atomics were 27% of this kernel).
             if ((touched >> lane) & 1ull) {
-                const float4 a0 = s_acc[lane * ACC + 0], a1 = s_acc[lane * ACC + 1];
-                const float4 e2 = s_rec[lane * REC + 2], e3 = s_rec[lane * REC + 3];
-                const float e_ca = e2.z, e_cb = e2.w, e_cc = e3.x, e_op = e3.y;
+                float4 a0 = s_acc[lane * ACC + 0], a1 = s_acc[lane * ACC + 1];
+                seg_geom_grads(&s_rec[lane * REC], a0, a1.x, a1.y);
                 // row layout: vx vy | ca cb cc | o | c0 c1 c2 c3 | ax ay   (a2 already holds c2 c3 ax ay)
-                s_acc[lane * ACC + 0] = make_float4(e_ca * a0.x + e_cb * a0.y, e_cb * a0.x + e_cc * a0.y, 0.5f * a0.z, a0.w);
-                s_acc[lane * ACC + 1] = make_float4(0.5f * a1.x, -a1.y / e_op, a1.z, a1.w);
+                s_acc[lane * ACC + 0] = a0;
+                s_acc[lane * ACC + 1] = a1;
                 if (!ABS && CDIM == 3) { // C2 arrives as four row partials
                     const float4 a2 = s_acc[lane * ACC + 2];
                     reinterpret_cast<float *>(&s_acc[lane * ACC + 2])[0] = (a2.x + a2.y) + (a2.z + a2.w);
@@ -1326,24 +1179,23 @@ __global__ void __launch_bounds__(GS_WAVE, GS_SEG_WAVES) raster_seg_bwd_kernel(R
                 }
             }
         } else if ((touched >> lane) & 1ull) {
-            const float4 a0 = s_acc[lane * ACC + 0], a1 = s_acc[lane * ACC + 1];
+            float4 a0 = s_acc[lane * ACC + 0], a1 = s_acc[lane * ACC + 1];
             float4 a2 = s_acc[lane * ACC + 2];
             if (!ABS && CDIM == 3) a2.x = (a2.x + a2.y) + (a2.z + a2.w); // C2 arrives as four row partials
             // this lane staged slot `lane`: its raw conic / opacity / id are still in the record
-            const float4 e2 = s_rec[lane * REC + 2], e3 = s_rec[lane * REC + 3];
-            const size_t g = (size_t)__float_as_int(e3.z);
-            const float e_ca = e2.z, e_cb = e2.w, e_cc = e3.x, e_op = e3.y;
+            seg_geom_grads(&s_rec[lane * REC], a0, a1.x, a1.y);
+            const size_t g = (size_t)__float_as_int(s_rec[lane * REC + 3].z);
             float *vcol = ga.v_colors + g * CDIM;
             grad_add<DET ? 1 : 0>(ga, vcol, g, 6u, a1.z);
             if (CDIM > 1) grad_add<DET ? 1 : 0>(ga, vcol + 1, g, 7u, a1.w);
             if (CDIM > 2) grad_add<DET ? 1 : 0>(ga, vcol + 2, g, 8u, a2.x);
             if (CDIM > 3) grad_add<DET ? 1 : 0>(ga, vcol + 3, g, 9u, a2.y);
-            grad_add<DET ? 1 : 0>(ga, ga.v_means2d + ga.s_xy * g, g, 0u, e_ca * a0.x + e_cb * a0.y);
-            grad_add<DET ? 1 : 0>(ga, ga.v_means2d + ga.s_xy * g + 1, g, 1u, e_cb * a0.x + e_cc * a0.y);
-            grad_add<DET ? 1 : 0>(ga, ga.v_conics + ga.s_conic * g, g, 2u, 0.5f * a0.z);
+            grad_add<DET ? 1 : 0>(ga, ga.v_means2d + ga.s_xy * g, g, 0u, a0.x);
+            grad_add<DET ? 1 : 0>(ga, ga.v_means2d + ga.s_xy * g + 1, g, 1u, a0.y);
+            grad_add<DET ? 1 : 0>(ga, ga.v_conics + ga.s_conic * g, g, 2u, a0.z);
             grad_add<DET ? 1 : 0>(ga, ga.v_conics + ga.s_conic * g + 1, g, 3u, a0.w);
-            grad_add<DET ? 1 : 0>(ga, ga.v_conics + ga.s_conic * g + 2, g, 4u, 0.5f * a1.x);
-            grad_add<DET ? 1 : 0>(ga, ga.v_opacities + ga.s_opac * g, g, 5u, -a1.y / e_op);
+            grad_add<DET ? 1 : 0>(ga, ga.v_conics + ga.s_conic * g + 2, g, 4u, a1.x);
+            grad_add<DET ? 1 : 0>(ga, ga.v_opacities + ga.s_opac * g, g, 5u, a1.y);
             if (ABS) {
                 grad_add<DET ? 1 : 0>(ga, ga.v_means2d_abs + ga.s_abs * g, g, 10u, a2.z);
                 grad_add<DET ? 1 : 0>(ga, ga.v_means2d_abs + ga.s_abs * g + 1, g, 11u, a2.w);

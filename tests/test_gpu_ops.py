@@ -5,13 +5,14 @@ reference's tests/test_basic.py (cited per test).  All calls go through the C AB
 Bars (BASELINE.json north_star): tile/bin indices bit-exact; fp32 results within 1e-4
 relative (plus an absolute floor for values near zero), tolerances written per assert.
 """
+import functools
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from util import N, T, assert_close, garden, golden, rel_l2
+from util import N, T, assert_close, garden, golden, rel_l2, tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -526,6 +527,59 @@ def test_narrow_backward_gradient_layouts_through_the_c_abi(ops):
     for name, e_layout, e_generic in errs:
         assert e_layout < 2e-5, (name, "separate arrays vs rows", e_layout)
         assert e_generic < 2e-4, (name, "generic vs segmented", e_generic)
+
+
+@functools.lru_cache(maxsize=None)
+def _small_tile_scene(ts):
+    """The 160x100 one-camera scene of test_rasterize_masks_tilesize_and_last_ids below, binned at tile size ts, with seeded tile
+    masks that keep about 70 % of the tiles.  Read-only: shared by the cases of the test that follows."""
+    fx = garden(1500, scale_mult=6.0)
+    W, H = 160, 100
+    Ks = fx["Ks"][:1].copy()
+    Ks[:, 0] *= W / fx["width"]
+    Ks[:, 1] *= H / fx["height"]
+    radii, means2d, depths, conics, _ = O.projection_fwd(fx["means"], None, fx["quats"], fx["scales"], fx["viewmats"][:1], Ks, W, H)
+    tw, th = math.ceil(W / ts), math.ceil(H / ts)
+    _, ids, flat = O.isect_tiles(means2d, radii, depths, ts, tw, th)
+    offs = O.isect_offset_encode(ids, 1, tw, th)
+    masks = np.random.RandomState(ts).rand(1, th, tw) > 0.3
+    return dict(means2d=means2d, conics=conics, opacities=fx["opacities"][None].copy(), offs=offs, flat=flat, masks=masks, W=W, H=H)
+
+
+@pytest.mark.parametrize("tile_size", [8, 16])
+@pytest.mark.parametrize("channels,absgrad", [(3, True), (9, True), (24, False)])
+def test_segmented_backward_channel_window_on_small_masked_tiles(ops, channels, absgrad, tile_size):
+    """Channel window x several segments per tile x small tiles x tile masks x an image that is no multiple of the tile, with
+    backgrounds: rasterize_to_pixels with 64-entry segments (the segmented kernels; 24 channels = two launches of the 12-channel
+    instance, the second at channel offset 12) against the same call without segments (the generic kernel).  The two forwards
+    are the same arithmetic: images bit for bit, and alphas wherever they are written (a masked tile's alphas are not, as in the
+    reference).  The gradients agree within the "generic vs segmented" bound of the two layout tests above."""
+    c = _small_tile_scene(tile_size)
+    W, H = c["W"], c["H"]
+    sizes = np.diff(np.append(c["offs"].ravel(), c["flat"].shape[0]))
+    assert (sizes > 128).mean() >= 0.5, "64-entry segments must leave most tiles with a third segment or more"
+    rs = np.random.RandomState(100 * channels + tile_size)
+    colors = rs.rand(1, 1500, channels).astype(np.float32)
+    bg = T(rs.rand(1, channels).astype(np.float32))
+    v_rc, v_ra = T(rs.randn(1, H, W, channels).astype(np.float32)), T(rs.randn(1, H, W, 1).astype(np.float32))
+    kept = T(np.repeat(np.repeat(c["masks"], tile_size, 1), tile_size, 2)[:, :H, :W])
+
+    def run(route):
+        m2, cn, col, op = T(c["means2d"], True), T(c["conics"], True), T(colors, True), T(c["opacities"], True)
+        with tuned(route):
+            rc, ra = ops.rasterize_to_pixels(m2, cn, col, op, W, H, tile_size, T(c["offs"]), T(c["flat"]), backgrounds=bg,
+                                             masks=T(c["masks"]), absgrad=absgrad)
+            g = torch.autograd.grad((rc * v_rc).sum() + (ra * v_ra)[kept].sum(), (m2, cn, col, op))  # (a masked tile's alphas are unwritten)
+        return rc, ra, g + ((m2.absgrad,) if absgrad else ())
+
+    rc_s, ra_s, g_s = run({"raster_seg": 64})
+    rc_g, ra_g, g_g = run("unsegmented")
+    assert torch.equal(rc_s, rc_g), "render_colors"
+    assert torch.equal(ra_s[kept], ra_g[kept]), "render_alphas"
+    errs = [(name, rel_l2(N(y), N(x))) for name, x, y in zip(("v_means2d", "v_conics", "v_colors", "v_opacities", "absgrad"), g_s, g_g)]
+    print(f"{channels} channels, tile {tile_size}: {int((sizes > 128).sum())} of {sizes.size} tiles above 128 entries; generic vs segmented:", errs)
+    for name, e in errs:
+        assert e < 2e-4, (name, "generic vs segmented", e)
 
 
 def test_rasterize_masks_tilesize_and_last_ids(ops):
