@@ -17,15 +17,21 @@
   directory layout (PNG image grids, ``shN.npz`` + ``mask.bin``, ``meta.json``) and a self-contained 8-bit PNG reader /
   writer (the image has no imageio), so directories written by either implementation are read by the other.
 
+* ``stg_compression``: ``STGPngCompression``, the reference's ``--compression stg`` of the two dynamic trainers -- the spacetime
+  attributes (means, scales, quats, opacities, trbf_center, trbf_scale, motion in three images, omega, colors, features_dir,
+  features_time) as PNG image grids in the reference's layout; ``decompress`` decodes all of them with ONE launch
+  (``decode_to_dynamic_inputs``, csrc/codec.hip) into the RAW parameter dict ``dynamic.render_dynamic`` takes.
+
 * ``entropy_coding_compression``: ``EntropyCodingCompression``, the reference's ``--compression entropy_coding`` -- the same
   directory, with the scales and the quats rANS-coded on the GPU by ``ans`` (csrc/ans.hip: histogram, lane-per-stream encode,
   pack, decode).  The reference takes its coder from the ``constriction`` package; the bitstream here is this project's own,
   defined by the numpy coder ``ans_reference`` that the kernels match byte for byte.
 """
-from .decode import decode_to_rasterizer_inputs, kmeans_decode, kmeans_encode, morton_order, reorder_splats, sort_splats
+from .decode import decode_to_dynamic_inputs, decode_to_rasterizer_inputs, kmeans_decode, kmeans_encode, morton_order, reorder_splats, sort_splats
 from .png_compression import PngCompression, png_read, png_write
 from .ans import ans_decode, ans_encode, normalize_frequencies, symbol_histogram
 from .entropy_coding_compression import EntropyCodingCompression
+from .stg_compression import STGPngCompression
 from .grid_sort import grid_sort_order, sort_splats_grid
 from .grid_codec import (
     compress_to_arrays,
@@ -39,4 +45,5 @@ from .grid_codec import (
 __all__ = ["quantize_grid", "dequantize_grid", "compress_to_arrays", "decompress_from_arrays", "log_transform",
            "inverse_log_transform", "decode_to_rasterizer_inputs", "kmeans_decode", "kmeans_encode", "morton_order",
            "sort_splats", "reorder_splats", "PngCompression", "png_read", "png_write", "EntropyCodingCompression", "ans_encode",
-           "ans_decode", "normalize_frequencies", "symbol_histogram", "grid_sort_order", "sort_splats_grid"]
+           "ans_decode", "normalize_frequencies", "symbol_histogram", "grid_sort_order", "sort_splats_grid", "STGPngCompression",
+           "decode_to_dynamic_inputs"]

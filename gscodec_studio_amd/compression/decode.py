@@ -68,6 +68,92 @@ def decode_to_rasterizer_inputs(arrays: Dict[str, List[Tensor]], meta: Dict[str,
     return out
 
 
+# the spacetime attributes of the reference's STG map (gsplat/compression/stg_compression.py:47-83) in the order of
+# gs_decode_dynamic_splats, with their channel counts; the last two are optional (absent with SH colours)
+DYNAMIC_ATTRIBUTES = (("means", 3), ("scales", 3), ("quats", 4), ("opacities", 1), ("trbf_center", 1), ("trbf_scale", 1),
+                      ("motion", 9), ("omega", 4), ("colors", 3), ("features_dir", 3), ("features_time", 3))
+_DYNAMIC_OPTIONAL = ("features_dir", "features_time")
+_DYNAMIC_PLANE_SLOT = {"means": 0, "scales": 2, "quats": 3, "opacities": 4, "trbf_center": 5, "trbf_scale": 6, "motion": 7,
+                       "omega": 10, "colors": 11, "features_dir": 12, "features_time": 13}
+
+
+def _checked_dynamic_planes(name: str, width: int, n: int, planes, m: Dict[str, Any]) -> Tuple[List[Tensor], int]:
+    """The planes of one attribute as uint8 tensors and its bit depth, or ValueError: the planes are file contents, and a
+    size that does not fit ``n`` must not become a read past a buffer."""
+    planes = [p if torch.is_tensor(p) else torch.as_tensor(np.ascontiguousarray(p)) for p in planes]
+    for p in planes:
+        if p.dtype != torch.uint8:
+            raise ValueError(f"decode_to_dynamic_inputs: {name}: planes must be uint8, got {p.dtype}")
+    if name == "means":
+        want = [n * 3, n * 3]
+    elif name == "motion":
+        num_img = int(m.get("num_img", 3))
+        if num_img != 3 or len(planes) not in (1, num_img):
+            raise ValueError(f"decode_to_dynamic_inputs: motion: {len(planes)} plane(s) with num_img = {num_img}; nine channels "
+                             "are three images of three channels, or one joined plane")
+        want = [n * 9] if len(planes) == 1 else [n * 3] * 3
+    else:
+        want = [n * width]
+    if [int(p.numel()) for p in planes] != want:
+        raise ValueError(f"decode_to_dynamic_inputs: {name}: plane sizes {[int(p.numel()) for p in planes]} bytes, expected {want} "
+                         f"for {n} splats")
+    for key in ("mins", "maxs"):
+        if key not in m or np.atleast_1d(np.asarray(m[key])).shape != (width,):
+            raise ValueError(f"decode_to_dynamic_inputs: {name}: meta {key!r} must have {width} entries")
+    if int(np.prod(m["shape"])) != n * width:
+        raise ValueError(f"decode_to_dynamic_inputs: {name}: shape {list(m['shape'])} does not hold {n} x {width} values")
+    bits = 16 if name == "means" else int(m.get("quantization", 8))
+    if name != "means" and not 1 <= bits <= 8:
+        raise ValueError(f"decode_to_dynamic_inputs: {name}: quantization {bits} outside 1..8")
+    return planes, bits
+
+
+@torch.no_grad()
+def decode_to_dynamic_inputs(arrays: Dict[str, List[Tensor]], meta: Dict[str, Any], device="cuda") -> Dict[str, Tensor]:
+    """The planes of a spacetime splat file (``STGPngCompression``) decoded by ONE kernel into the RAW parameter dict that
+    ``dynamic.render_dynamic(splats, t, ...)`` takes: means (log transform undone), scales, quats, opacities, trbf_center,
+    trbf_scale, motion, omega, colors and, when present, features_dir / features_time -- no activation, no quaternion
+    normalisation: bit for bit what ``dequantize_grid`` per attribute + ``inverse_log_transform`` give and what the reference's
+    ``decompress`` returns.
+
+    ``arrays[name]``: the uint8 planes of one attribute, host or device -- two for the means (low, high byte), the three images
+    of the motion or its one joined ``[n, 9]`` plane, one otherwise; ``meta[name]``: its ``meta.json`` entry.  Everything is
+    validated on the host before the launch (ValueError naming the attribute)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("decode_to_dynamic_inputs: the HIP path needs a GPU device (no CPU fallback)")
+    if "means" not in meta:
+        raise ValueError("decode_to_dynamic_inputs: means: no meta entry")
+    n = int(np.prod(meta["means"]["shape"][:-1]))
+    present, bits, mins, maxs = {}, [], [], []
+    for name, width in DYNAMIC_ATTRIBUTES:
+        if name not in arrays or name not in meta:
+            if name in _DYNAMIC_OPTIONAL and name not in arrays and name not in meta:
+                bits.append(8)
+                mins += [0.0] * width
+                maxs += [0.0] * width
+                continue
+            raise ValueError(f"decode_to_dynamic_inputs: {name}: planes and meta entry are both required")
+        present[name], b = _checked_dynamic_planes(name, width, n, arrays[name], meta[name])
+        bits.append(b)
+        mins += [float(np.float32(v)) for v in np.atleast_1d(meta[name]["mins"])]
+        maxs += [float(np.float32(v)) for v in np.atleast_1d(meta[name]["maxs"])]
+    out = {name: torch.empty(list(meta[name]["shape"]), dtype=torch.float32, device=dev) for name in present}
+    if n:
+        planes = {name: [p.to(dev).contiguous() for p in ps] for name, ps in present.items()}
+        slots = [None] * 14
+        for name, ps in planes.items():
+            for k, p in enumerate(ps):
+                slots[_DYNAMIC_PLANE_SLOT[name] + k] = B.ptr(p)
+        c_planes = (ctypes.c_void_p * 14)(*slots)
+        c_outs = (ctypes.c_void_p * 11)(*[B.ptr(out[name]) if name in out else None for name, _ in DYNAMIC_ATTRIBUTES])
+        c_mins, c_maxs, c_bits = (ctypes.c_float * 35)(*mins), (ctypes.c_float * 35)(*maxs), (ctypes.c_uint32 * 11)(*bits)
+        with torch.cuda.device(dev):
+            B.call("gs_decode_dynamic_splats", n, ctypes.addressof(c_planes), ctypes.addressof(c_mins), ctypes.addressof(c_maxs),
+                   ctypes.addressof(c_bits), ctypes.addressof(c_outs), _stream(out["means"]))
+    return {name: v.to(getattr(torch, meta[name]["dtype"])) for name, v in out.items()}
+
+
 @torch.no_grad()
 def kmeans_decode(centroids_quant: Tensor, labels: Tensor, meta: Dict[str, Any], device="cuda", mask: Optional[Tensor] = None) -> Tensor:
     """``_decompress_kmeans`` / ``_decompress_masked_kmeans`` (png_compression.py:487-520, 603-640) on the GPU, bit-exact:

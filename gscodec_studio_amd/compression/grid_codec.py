@@ -19,13 +19,21 @@ def log_transform(x: Tensor) -> Tensor:
     return torch.sign(x) * torch.log1p(torch.abs(x))
 
 
-def inverse_log_transform(y: Tensor) -> Tensor:
-    """sign(y) expm1(|y|)  (gsplat/utils.py:40-41)."""
-    return torch.sign(y) * torch.expm1(torch.abs(y))
-
-
 def _stream(t: Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def inverse_log_transform(y: Tensor) -> Tensor:
+    """sign(y) expm1(|y|)  (gsplat/utils.py:40-41).  Device tensors go through ``gs_inverse_log_transform``, whose expm1 rounds as
+    torch's does on the CPU -- where the reference decodes -- so the decoded means are the reference's bit for bit (torch's expm1
+    on the GPU is the device library's and differs in the last bit for about one value in eight)."""
+    if not y.is_cuda:
+        return torch.sign(y) * torch.expm1(torch.abs(y))
+    src = y.detach().float().contiguous()
+    out = torch.empty_like(src)
+    with torch.cuda.device(src.device):
+        B.call("gs_inverse_log_transform", src.numel(), B.ptr(src), B.ptr(out), _stream(src))
+    return out.to(y.dtype)
 
 
 @torch.no_grad()

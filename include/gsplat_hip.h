@@ -843,6 +843,26 @@ int32_t gs_decode_splats(
     const uint8_t *opacities, const uint8_t *sh0, const float *mins14, const float *maxs14, const uint32_t *bits5,
     int32_t normalize_quats, int32_t activate, float *means_out, float *scales_out, float *quats_out, float *opacities_out,
     float *sh0_out, gs_stream_t stream);
+/* The inverse log transform of the means, out = sign(y) * expm1(|y|) (gsplat/utils.py:40-41), n floats, in place allowed.  The expm1
+ * is evaluated as torch evaluates it on the CPU, where the reference decodes (a float-float sequence of fp32 adds, multiplies and
+ * fmas), not with the device library's expm1f: bit-identical to the reference's decoded means, and the one function every decode
+ * here shares (gs_decode_splats, gs_decode_dynamic_splats, compression.inverse_log_transform). */
+int32_t gs_inverse_log_transform(uint64_t n, const float *y, float *out, gs_stream_t stream);
+/* Decode of a spacetime splat file (STGPngCompression, gsplat/compression/stg_compression.py:124-143) STRAIGHT INTO
+ * render_dynamic()'s RAW parameter dict by one kernel: every attribute of the STG map dequantized with the arithmetic of
+ * gs_grid_dequantize (bit-identical), the means followed by the inverse log transform; no activation, no quaternion
+ * normalisation.  Attribute order (11): means(3, 16-bit) scales(3) quats(4) opacities(1) trbf_center(1) trbf_scale(1) motion(9)
+ * omega(4) colors(3) features_dir(3) features_time(3): 38 bytes read and 35 floats written per splat.
+ *   planes14 (HOST array of 14 device pointers, [n, C] row-major uint8 each): means_l means_u scales quats opacities
+ *     trbf_center trbf_scale motion motion_1 motion_2 omega colors features_dir features_time.  The motion is either ONE
+ *     joined [n, 9] plane (motion_1 = motion_2 = NULL) or the three [n, 3] images of the file.  features_dir / features_time
+ *     are optional: a NULL plane skips the attribute.
+ *   mins35 / maxs35 (HOST): the per-channel bounds of meta.json in attribute order; bits11 (HOST): bit depth per attribute,
+ *     means = 16, the others 1..8 (value in the top bits of the byte); outs11 (HOST array of 11 device pointers): [n, C] fp32.
+ * n = 0 returns 0 without touching any pointer.  Queued on `stream`, no host wait. */
+int32_t gs_decode_dynamic_splats(
+    uint64_t n, const uint8_t *const *planes14, const float *mins35, const float *maxs35, const uint32_t *bits11,
+    float *const *outs11, gs_stream_t stream);
 /* K-means codebook decode of the higher SH bands (png_compression.py:487-520): out[r, :] =
  * centroids_quant[labels[r], :] / (2^bits - 1) * (maxs - mins) + mins (float64 arithmetic like the reference).
  * labels are file contents: one outside [0, n_centroids) (where the reference's centroids[labels] raises IndexError)
