@@ -12,6 +12,10 @@
   library's own integer algorithm on the GPU (csrc/grid_sort.hip: box blur, random groups through the radix sort, best-of-24
   assignment), defined by the numpy code ``grid_sort_reference`` that the kernels match element for element;
   ``use_sort="grid"`` of the two codecs below.
+* ``kmeans``: ``kmeans_fit`` / ``KMeans``, the clustering behind the shN codebook that the reference takes from ``torchpq``
+  (manhattan distance), in 24-bit fixed point on the GPU (csrc/kmeans.hip: one v_sad_u32 per element of the assignment, integer
+  atomics in the update), defined by the numpy code ``kmeans_reference`` that the kernels match element for element;
+  ``kmeans_encode(method="fixed")`` and ``kmeans_method="fixed"`` of the two codecs below.
 
 * ``png_compression``: the file level -- ``PngCompression.compress(dir, splats)`` / ``decompress(dir)`` with the reference's
   directory layout (PNG image grids, ``shN.npz`` + ``mask.bin``, ``meta.json``) and a self-contained 8-bit PNG reader /
@@ -33,6 +37,7 @@ from .ans import ans_decode, ans_encode, normalize_frequencies, symbol_histogram
 from .entropy_coding_compression import EntropyCodingCompression
 from .stg_compression import STGPngCompression
 from .grid_sort import grid_sort_order, sort_splats_grid
+from .kmeans import KMeans, kmeans_fit
 from .grid_codec import (
     compress_to_arrays,
     decompress_from_arrays,
@@ -46,4 +51,4 @@ __all__ = ["quantize_grid", "dequantize_grid", "compress_to_arrays", "decompress
            "inverse_log_transform", "decode_to_rasterizer_inputs", "kmeans_decode", "kmeans_encode", "morton_order",
            "sort_splats", "reorder_splats", "PngCompression", "png_read", "png_write", "EntropyCodingCompression", "ans_encode",
            "ans_decode", "normalize_frequencies", "symbol_histogram", "grid_sort_order", "sort_splats_grid", "STGPngCompression",
-           "decode_to_dynamic_inputs"]
+           "decode_to_dynamic_inputs", "KMeans", "kmeans_fit"]

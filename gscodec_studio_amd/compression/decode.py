@@ -16,6 +16,7 @@ import torch
 from torch import Tensor
 
 from .. import _backend as B
+from .kmeans import kmeans_fit
 
 _ORDER = ("means", "scales", "quats", "opacities", "sh0")
 _WIDTH = {"means": 3, "scales": 3, "quats": 4, "opacities": 1, "sh0": 3}
@@ -190,28 +191,35 @@ def kmeans_decode(centroids_quant: Tensor, labels: Tensor, meta: Dict[str, Any],
 
 
 @torch.no_grad()
-def kmeans_encode(params: Tensor, n_clusters: int = 65536, quantization: int = 8, iters: int = 10, seed: int = 0
-                  ) -> Tuple[Tensor, Tensor, Dict[str, Any]]:
+def kmeans_encode(params: Tensor, n_clusters: int = 65536, quantization: int = 8, iters: int = 10, seed: int = 0,
+                  method: str = "torch") -> Tuple[Tensor, Tensor, Dict[str, Any]]:
     """Codebook for the higher SH bands in the reference's on-disk form (``_compress_kmeans``, png_compression.py:420-484):
     returns (centroids_quant uint8 [k, w], labels int32 [n], meta).  The reference clusters with ``torchpq``'s K-means
     (manhattan distance, random initialisation) -- a package that is not in the image and whose result is not
-    reproducible run to run; the clustering here is a plain Lloyd iteration in torch with the same distance and a seeded
-    initialisation (device tensors, chunked assignment).  Everything AFTER the clustering -- the scalar min / max of the
+    reproducible run to run; the clustering here is a Lloyd iteration with the same distance and a seeded initialisation:
+    ``method="torch"`` (the default) in float with torch operators (device or host tensors, chunked assignment),
+    ``method="fixed"`` in fixed point by the kernels of csrc/kmeans.hip (``kmeans_fit``: device tensors only, the same start,
+    reproducible bit for bit).  Everything AFTER the clustering -- the scalar min / max of the
     centroids, ``round((c - min) / (max - min) * (2^q - 1))`` in fp32, uint16-range labels -- is the reference's arithmetic,
     so ``kmeans_decode`` reads files written by either."""
+    if method not in ("torch", "fixed"):
+        raise ValueError(f"kmeans_encode: method must be \"torch\" or \"fixed\", got {method!r}")
     x = params.reshape(params.shape[0], -1).float()
     n, w = x.shape
     k = int(min(n_clusters, n))
-    g = torch.Generator(device=x.device).manual_seed(seed)
-    cent = x[torch.randperm(n, device=x.device, generator=g)[:k]].clone()
-    labels = torch.zeros(n, dtype=torch.int64, device=x.device)
-    chunk = max(1, (1 << 24) // max(k, 1))
-    for _ in range(max(iters, 1)):
-        for s in range(0, n, chunk):
-            labels[s:s + chunk] = torch.cdist(x[s:s + chunk], cent, p=1).argmin(1)
-        sums = torch.zeros_like(cent).index_add_(0, labels, x)
-        cnts = torch.zeros(k, device=x.device).index_add_(0, labels, torch.ones(n, device=x.device))
-        cent = torch.where(cnts[:, None] > 0, sums / cnts.clamp(min=1)[:, None], cent)
+    if method == "fixed":
+        cent, labels = kmeans_fit(x, n_clusters, iters=iters, seed=seed)
+    else:
+        g = torch.Generator(device=x.device).manual_seed(seed)
+        cent = x[torch.randperm(n, device=x.device, generator=g)[:k]].clone()
+        labels = torch.zeros(n, dtype=torch.int64, device=x.device)
+        chunk = max(1, (1 << 24) // max(k, 1))
+        for _ in range(max(iters, 1)):
+            for s in range(0, n, chunk):
+                labels[s:s + chunk] = torch.cdist(x[s:s + chunk], cent, p=1).argmin(1)
+            sums = torch.zeros_like(cent).index_add_(0, labels, x)
+            cnts = torch.zeros(k, device=x.device).index_add_(0, labels, torch.ones(n, device=x.device))
+            cent = torch.where(cnts[:, None] > 0, sums / cnts.clamp(min=1)[:, None], cent)
     mins, maxs = cent.min(), cent.max()
     norm = (cent - mins) / (maxs - mins)
     cq = (norm.cpu().numpy() * (2**quantization - 1)).round().astype(np.uint8)

@@ -93,8 +93,8 @@ def _decompress_gaussian_ans(*args, **kwargs):
 
 
 def _compress_masked_kmeans(compress_dir: str, param_name: str, params: Tensor, n_sidelen: int, n_clusters: int = 32768,
-                            **kwargs) -> Dict[str, Any]:
-    return compress_masked_kmeans(compress_dir, param_name, params, n_clusters)
+                            kmeans_method: str = "torch", **kwargs) -> Dict[str, Any]:
+    return compress_masked_kmeans(compress_dir, param_name, params, n_clusters, kmeans_method)
 
 
 def _decompress_masked_kmeans(compress_dir: str, param_name: str, meta: Dict[str, Any], device="cuda") -> Tensor:
@@ -125,7 +125,9 @@ class EntropyCodingCompression:
     ``attribute_codec_registry`` maps an
     attribute to ``{"encode": <name>, "decode": <name>}`` with the reference's function names as strings, e.g.
     ``{"scales": {"encode": "_compress_png", "decode": "_decompress_png"}}``.  Works on detached copies; the caller's dictionary
-    is not written to.  A channel with ``maxs == mins`` is coded as symbol 0 and decodes to ``mins``."""
+    is not written to.  A channel with ``maxs == mins`` is coded as symbol 0 and decodes to ``mins``.  ``kmeans_method`` as in
+    ``PngCompression``: "torch" or "fixed" clustering of the shN codebook; it reaches every compress function as the keyword
+    ``kmeans_method``, next to ``n_sidelen``, ``n_clusters`` and ``verbose`` (they all take ``**kwargs``)."""
 
     use_sort: Union[bool, str] = True
     verbose: bool = True
@@ -139,6 +141,7 @@ class EntropyCodingCompression:
     decompress_fn_map: Dict[str, str] = field(default_factory=lambda: {
         "means": "_decompress_png_16bit", "scales": "_decompress_factorized_ans", "quats": "_decompress_factorized_ans",
         "opacities": "_decompress_png", "sh0": "_decompress_png", "shN": "_decompress_masked_kmeans"})
+    kmeans_method: str = "torch"
 
     def __post_init__(self, attribute_codec_registry):
         for attr_name, attr_codec in (attribute_codec_registry or {}).items():
@@ -169,7 +172,7 @@ class EntropyCodingCompression:
                 meta[name] = _meta_of(value)
             else:
                 meta[name] = self._get_compress_fn(name)(compress_dir, name, value, n_sidelen=side, n_clusters=self.n_clusters,
-                                                         verbose=self.verbose)
+                                                         verbose=self.verbose, kmeans_method=self.kmeans_method)
         with open(os.path.join(compress_dir, "meta.json"), "w") as f:
             json.dump(meta, f)
 

@@ -137,9 +137,9 @@ def prepare_splats(splats: Dict[str, Tensor], opacity_threshold: float, use_sort
     return splats, side
 
 
-def compress_masked_kmeans(compress_dir: str, param_name: str, params: Tensor, n_clusters: int) -> Dict[str, Any]:
-    """png_compression.py:521-600: the splats with any positive higher-band coefficient are clustered, the rest is a bit
-    in mask.bin."""
+def compress_masked_kmeans(compress_dir: str, param_name: str, params: Tensor, n_clusters: int, method: str = "torch") -> Dict[str, Any]:
+    """png_compression.py:521-600: the splats with any positive higher-band coefficient are clustered (``method``: see
+    ``kmeans_encode``), the rest is a bit in mask.bin."""
     mask = (params > 0).any(dim=1).any(dim=1).reshape(-1)
     n = int(mask.numel())
     np.packbits(mask.cpu().numpy().astype(bool))[: (n + 7) // 8].tofile(os.path.join(compress_dir, "mask.bin"))
@@ -148,7 +148,7 @@ def compress_masked_kmeans(compress_dir: str, param_name: str, params: Tensor, n
                             labels=np.zeros(0, np.uint16))
         meta = {**_meta_of(params), "mins": 0.0, "maxs": 0.0, "quantization": 8}
     else:
-        cq, labels, meta = kmeans_encode(params[mask], n_clusters=n_clusters)
+        cq, labels, meta = kmeans_encode(params[mask], n_clusters=n_clusters, method=method)
         np.savez_compressed(os.path.join(compress_dir, f"{param_name}.npz"), centroids=cq.cpu().numpy(),
                             labels=labels.cpu().numpy().astype(np.uint16))
     meta.update({"shape": list(params.shape), "mask_bits": n, "mask_byte": (n + 7) // 8})
@@ -169,12 +169,14 @@ def decompress_masked_kmeans(compress_dir: str, param_name: str, m: Dict[str, An
 class PngCompression:
     """The reference's ``PngCompression`` (same constructor arguments, same files).  ``use_sort``: True = PLAS (external
     package, as in the reference), "morton" = the deterministic Morton order, "grid" = the library's grid sort, False = keep
-    the order."""
+    the order.  ``kmeans_method``: how the shN codebook is clustered, "torch" (float Lloyd iteration in torch) or "fixed" (the
+    fixed-point kernels of csrc/kmeans.hip, reproducible bit for bit); the files have the same form."""
 
     use_sort: Union[bool, str] = True
     verbose: bool = True
     n_clusters: int = 16384  # of the shN codebook (png_compression.py:132)
     opacity_threshold: float = 0.005  # outlier filter: sigmoid(opacity) below it is dropped (outlier_filter.py:8-9, 32-37)
+    kmeans_method: str = "torch"
 
     @torch.no_grad()
     def compress(self, compress_dir: str, splats: Dict[str, Tensor], entropy_models=None) -> None:
@@ -194,7 +196,7 @@ class PngCompression:
                 for fn, plane in zip(files, planes):
                     png_write(os.path.join(compress_dir, fn), plane.cpu().numpy())
             elif name == "shN":
-                meta[name] = compress_masked_kmeans(compress_dir, name, value, self.n_clusters)
+                meta[name] = compress_masked_kmeans(compress_dir, name, value, self.n_clusters, self.kmeans_method)
             else:
                 np.savez_compressed(os.path.join(compress_dir, f"{name}.npz"), arr=value.cpu().numpy())
                 meta[name] = _meta_of(value)

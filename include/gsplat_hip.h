@@ -48,7 +48,8 @@ extern "C" {
  * (gs_gridsort_blur, gs_gridsort_keys, gs_gridsort_assign), and the 2D Gaussian splatting entries (gs_projection_2dgs_fwd / _bwd,
  * gs_rasterize_2dgs_fwd / _bwd, gs_depth_to_normal_fwd / _bwd), and the spacetime colour decoder's (gs_stg_decode_fwd / _bwd,
  * gs_stg_decode_partial_rows), and the appearance module's (gs_appearance_fwd / _bwd, gs_appearance_partial_rows,
- * gs_appearance_partial_cols). */
+ * gs_appearance_partial_cols), and the K-means entries (gs_kmeans_padded_width, gs_kmeans_default_slices, gs_kmeans_assign,
+ * gs_kmeans_update). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -935,6 +936,31 @@ int32_t gs_gridsort_blur(uint32_t S, uint32_t C, uint32_t r, const uint16_t *q, 
 int32_t gs_gridsort_keys(uint32_t S, uint32_t b, uint32_t seed, uint32_t k, int64_t *keys, int32_t *vals, gs_stream_t stream);
 int32_t gs_gridsort_assign(uint32_t S, uint32_t C, const uint16_t *q, const uint16_t *target, const int64_t *sorted_keys,
                            const int32_t *sorted_pos, const int32_t *order_in, int32_t *order_out, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * K-means codebook (kmeans.hip): the Lloyd steps behind the shN codec -- the role of `torchpq.clustering.KMeans` (manhattan
+ * distance) in the reference (gsplat/compression/png_compression.py:420-484), as an algorithm of this project's own whose
+ * definition is the numpy code gscodec_studio_amd/compression/kmeans_reference.py.  Integer arithmetic only: the kernels'
+ * results equal the reference's element for element.  1 <= n < 2^31 points of 1 <= w <= 64 channels, 1 <= k <= 2^20 clusters;
+ * q int32 [w, n] (channel-major), values in [0, 2^24 - 1]; cent int32 [k, wp] with wp = gs_kmeans_padded_width(w) (the next of
+ * 4, 8, 16, 32, 48, 64; 0 for a w outside 1..64) and the channels w <= c < wp ZERO: the caller zero-fills them once, nothing
+ * here writes them.  Every launch goes to `stream`, nothing waits on the host.
+ *
+ * gs_kmeans_assign: labels[i] = the lowest j with the least d(i, j) = sum over c of |q[c, i] - cent[j, c]| (< 2^30), and
+ *   n_changed[0] = the number of i whose label differs from the one labels[i] held on entry (labels is read, then written; the
+ *   counter is zeroed here).  k_slices (1 <= k_slices <= min(k, 65535)) cuts the centroids into that many slices walked by
+ *   different workgroups that meet in a 64-bit atomic minimum over d << 32 | j in keys uint64 [n] (may be NULL with one slice);
+ *   the labels do not depend on it.  gs_kmeans_default_slices: one slice when n alone fills the chip, otherwise as many as
+ *   bring the grid to about four workgroups per CU, of 64 centroids at least (0 for a shape outside the bounds above).
+ * gs_kmeans_update: sums[j, c] = the sum of q[c, i] over labels[i] == j (uint64 [k, w], scratch), counts[j] = their number
+ *   (uint32 [k], left for the caller to read), cent[j, c] = (2 sums + counts) / (2 counts) for c < w where counts[j] > 0; the
+ *   centroid of an empty cluster is not written.  A label outside [0, k) adds nowhere. */
+uint32_t gs_kmeans_padded_width(uint32_t w);
+uint32_t gs_kmeans_default_slices(uint32_t n, uint32_t w, uint32_t k);
+int32_t gs_kmeans_assign(uint32_t n, uint32_t w, uint32_t k, const int32_t *q, const int32_t *cent, uint32_t k_slices,
+                         uint64_t *keys, int32_t *labels, uint32_t *n_changed, gs_stream_t stream);
+int32_t gs_kmeans_update(uint32_t n, uint32_t w, uint32_t k, const int32_t *q, const int32_t *labels, uint64_t *sums,
+                         uint32_t *counts, int32_t *cent, gs_stream_t stream);
 
 
 /* ------------------------------------------------------------------------

@@ -12,6 +12,9 @@ typedef float float2v __attribute__((ext_vector_type(2)));
 template <int MODE> __global__ void __launch_bounds__(256) k(float *out, float seed) {
     float a0 = seed + threadIdx.x, a1 = a0 + 1.f, a2 = a0 + 2.f, a3 = a0 + 3.f, a4 = a0 + 4.f, a5 = a0 + 5.f, a6 = a0 + 6.f, a7 = a0 + 7.f;
     const float m = 0.999f, c = 1e-3f;
+    uint32_t u0 = threadIdx.x, u1 = u0 + 1u, u2 = u0 + 2u, u3 = u0 + 3u, u4 = u0 + 4u, u5 = u0 + 5u, u6 = u0 + 6u, u7 = u0 + 7u;
+    const uint32_t su = __float_as_uint(seed); // a kernel argument: wave-uniform, lives in an SGPR
+    const uint32_t uc = threadIdx.x * 3u;      // a constant VGPR: the addend of the independent v_sad_u32
     for (int r = 0; r < REP; ++r) {
         if (MODE == 0) { // 8 independent v_fma_f32
             asm volatile("v_fma_f32 %0, %0, %8, %9\n v_fma_f32 %1, %1, %8, %9\n v_fma_f32 %2, %2, %8, %9\n v_fma_f32 %3, %3, %8, %9\n"
@@ -67,8 +70,21 @@ template <int MODE> __global__ void __launch_bounds__(256) k(float *out, float s
             asm volatile("v_mul_f32 %0, %0, %8\n s_nop 0\n v_mul_f32 %1, %1, %8\n s_nop 0\n v_mul_f32 %2, %2, %8\n s_nop 0\n v_mul_f32 %3, %3, %8\n s_nop 0\n"
                          "v_mul_f32 %4, %4, %8\n s_nop 0\n v_mul_f32 %5, %5, %8\n s_nop 0\n v_mul_f32 %6, %6, %8\n s_nop 0\n v_mul_f32 %7, %7, %8\n s_nop 0\n"
                          : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(m));
+        } else if (MODE == 11) { // 8 independent v_sad_u32, second source an SGPR (the K-means assignment, csrc/kmeans.hip)
+            asm volatile("v_sad_u32 %0, %0, %8, %9\n v_sad_u32 %1, %1, %8, %9\n v_sad_u32 %2, %2, %8, %9\n v_sad_u32 %3, %3, %8, %9\n"
+                         "v_sad_u32 %4, %4, %8, %9\n v_sad_u32 %5, %5, %8, %9\n v_sad_u32 %6, %6, %8, %9\n v_sad_u32 %7, %7, %8, %9\n"
+                         : "+v"(u0), "+v"(u1), "+v"(u2), "+v"(u3), "+v"(u4), "+v"(u5), "+v"(u6), "+v"(u7) : "s"(su), "v"(uc));
+        } else if (MODE == 12) { // two dependent chains of 4 v_sad_u32 (two points of one lane against one centroid quad)
+            asm volatile("v_sad_u32 %0, %2, %6, %0\n v_sad_u32 %1, %2, %6, %1\n v_sad_u32 %0, %3, %6, %0\n v_sad_u32 %1, %3, %6, %1\n"
+                         "v_sad_u32 %0, %4, %6, %0\n v_sad_u32 %1, %4, %6, %1\n v_sad_u32 %0, %5, %6, %0\n v_sad_u32 %1, %5, %6, %1\n"
+                         : "+v"(u0), "+v"(u1) : "v"(u2), "v"(u3), "v"(u4), "v"(u5), "s"(su));
+        } else if (MODE == 13) { // 8 independent v_sad_u32, every source a VGPR
+            asm volatile("v_sad_u32 %0, %0, %8, %8\n v_sad_u32 %1, %1, %8, %8\n v_sad_u32 %2, %2, %8, %8\n v_sad_u32 %3, %3, %8, %8\n"
+                         "v_sad_u32 %4, %4, %8, %8\n v_sad_u32 %5, %5, %8, %8\n v_sad_u32 %6, %6, %8, %8\n v_sad_u32 %7, %7, %8, %8\n"
+                         : "+v"(u0), "+v"(u1), "+v"(u2), "+v"(u3), "+v"(u4), "+v"(u5), "+v"(u6), "+v"(u7) : "v"(su));
         }
     }
+    a0 += (float)(u0 ^ u1 ^ u2 ^ u3 ^ u4 ^ u5 ^ u6 ^ u7);
     out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7;
 }
 
@@ -107,6 +123,9 @@ int main() {
         run<8>("v_fma_f32 dependent x8", w);
         run<9>("v_mfma_f32_4x4x1 x8", w);
         run<10>("v_mul + s_nop x8", w);
+        run<11>("v_sad_u32 v,s,v x8 indep", w);
+        run<12>("v_sad_u32 v,s,v 2 chains x4", w);
+        run<13>("v_sad_u32 v,v,v x8 indep", w);
     }
     return 0;
 }
