@@ -12,7 +12,9 @@ Public surface (mirrors the reference's ``gsplat`` package for this path only):
   ``dynamic.{Sandwich, getcolormodel, decode_colors, trbfunction}`` (``from gscodec_studio_amd.dynamic import getcolormodel, trbfunction``
   in place of ``from helper.STG.helper_model import ...``; ``dynamic.render_dynamic(..., decoder=, rays=)`` applies it after the render),
   and the static trainer's appearance module ``appearance.AppearanceOptModule`` (``from gscodec_studio_amd.appearance import
-  AppearanceOptModule`` in place of ``from utils import AppearanceOptModule``; ``module.colors(...)`` is the fused form of its call site).
+  AppearanceOptModule`` in place of ``from utils import AppearanceOptModule``; ``module.colors(...)`` is the fused form of its call site),
+  and the trainers' neighbour search ``utils.{knn, knn_search, init_scales}`` (``knn.py``: ``from gscodec_studio_amd.utils import knn``
+  in place of ``from utils import knn``; exact grid k-NN on the GPU, ``init_scales`` is the three lines that size the initial splats).
 """
 from ._wrapper import (
     accumulate,

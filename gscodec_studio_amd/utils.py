@@ -5,6 +5,9 @@
 * ``depth_to_normal(depths, camtoworlds, Ks, z_depth=True)`` -- world-space surface normals from the central differences of those
   points.  The reference builds them from ~15 torch launches over ``[C, H, W, 3]`` temporaries; here it is ONE kernel each way
   (``csrc/surfel.hip``: ``gs_depth_to_normal_fwd`` / ``_bwd``), GPU only, with the gradient going to ``depths``.
+
+and the trainers' neighbour search (reference ``examples/utils.py:142``), re-exported from ``knn``: ``knn(x, K=4)``,
+``knn_search``, ``init_scales`` (exact grid k-NN on the GPU, ``csrc/knn.hip``).
 """
 from __future__ import annotations
 
@@ -12,9 +15,10 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor
 
+from .knn import init_scales, knn, knn_search
 from .surfel import depth_to_normal
 
-__all__ = ["depth_to_points", "depth_to_normal"]
+__all__ = ["depth_to_points", "depth_to_normal", "knn", "knn_search", "init_scales"]
 
 
 def depth_to_points(depths: Tensor, camtoworlds: Tensor, Ks: Tensor, z_depth: bool = True) -> Tensor:

@@ -49,7 +49,7 @@ extern "C" {
  * gs_rasterize_2dgs_fwd / _bwd, gs_depth_to_normal_fwd / _bwd), and the spacetime colour decoder's (gs_stg_decode_fwd / _bwd,
  * gs_stg_decode_partial_rows), and the appearance module's (gs_appearance_fwd / _bwd, gs_appearance_partial_rows,
  * gs_appearance_partial_cols), and the K-means entries (gs_kmeans_padded_width, gs_kmeans_default_slices, gs_kmeans_assign,
- * gs_kmeans_update). */
+ * gs_kmeans_update), and the nearest-neighbour entries (gs_knn_cells, gs_knn_finish_grid, gs_knn_search). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -961,6 +961,34 @@ int32_t gs_kmeans_assign(uint32_t n, uint32_t w, uint32_t k, const int32_t *q, c
                          uint64_t *keys, int32_t *labels, uint32_t *n_changed, gs_stream_t stream);
 int32_t gs_kmeans_update(uint32_t n, uint32_t w, uint32_t k, const int32_t *q, const int32_t *labels, uint64_t *sums,
                          uint32_t *counts, int32_t *cent, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Nearest neighbours (knn.hip): the exact K nearest points of 3-D float32 points -- the role of `knn` in the reference's trainers
+ * (examples/utils.py:142-146: sklearn's NearestNeighbors on the host), as an algorithm of this project's own whose definition is
+ * the numpy code gscodec_studio_amd/knn_reference.py: a uniform grid of rx x ry x rz cells of side h from the corner lo (`box`: four
+ * float64 in HOST memory, lo x, y, z and h, read during the call; 1 <= r <= 1024 per axis, h > 0), the cell of a point
+ * clamp(floor((double(p) - lo) / h), 0, r - 1) per axis, its id (cz ry + cy) rx + cx; border cells reach to infinity.
+ * 1 <= n, m < 2^31.  The host chooses lo, h and r (knn_reference.cell_size) and sorts (cell id, index) between the first two
+ * calls (gs_sort_pairs_u64_i32 over the bits of the largest id).  Every launch goes to `stream`, nothing waits on the host, no
+ * atomics.
+ *
+ * gs_knn_cells: cell_ids[i] = the id of xyz[i] (float [n, 3]), ids[i] = i: the pairs to sort.
+ * gs_knn_finish_grid: sorted_xyzi float [n, 4] (16-byte aligned) = (xyz[order[p]], the bits of order[p]) for every position p;
+ *   and, with ncells > 0, cell_starts int32 [ncells + 1]: cell_starts[c] = the number of sorted_ids below c (ncells = 0: the
+ *   sorted copy of a query list, sorted_ids and cell_starts may be NULL).
+ * gs_knn_search: for the m queries of queries_xyzi float [m, 4] (xyz and, as bits in w, the row < m each result goes to; in
+ *   cell-sorted order for speed, any order for the result; the same array as sorted_xyzi for the neighbours of the points
+ *   themselves), the K (1 <= K <= min(16, n)) points of sorted_xyzi with the least (d^2, index), d^2 = (dx dx + dy dy) + dz dz in
+ *   float32 without contraction: dist float [m, K] = sqrtf(d^2) ascending, idx int64 [m, K] (both or neither), and / or
+ *   log_scales float [m, 3] = log(sqrt(mean of d^2 over columns 1 .. K - 1) * init_scale) in every column (K >= 2; the mean
+ *   and what follows in float64; -inf where the mean is zero).  The kernel is instantiated for K padded to 4, 8 and 16. */
+int32_t gs_knn_cells(uint32_t n, const float *xyz, const double *box, uint32_t rx, uint32_t ry, uint32_t rz, int64_t *cell_ids,
+                     int32_t *ids, gs_stream_t stream);
+int32_t gs_knn_finish_grid(uint32_t n, uint32_t ncells, const float *xyz, const int64_t *sorted_ids, const int32_t *order,
+                           float *sorted_xyzi, int32_t *cell_starts, gs_stream_t stream);
+int32_t gs_knn_search(uint32_t n, uint32_t m, uint32_t K, const float *sorted_xyzi, const int32_t *cell_starts,
+                      const float *queries_xyzi, const double *box, uint32_t rx, uint32_t ry, uint32_t rz, float *dist,
+                      int64_t *idx, float *log_scales, float init_scale, gs_stream_t stream);
 
 
 /* ------------------------------------------------------------------------
