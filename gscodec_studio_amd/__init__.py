@@ -14,7 +14,10 @@ Public surface (mirrors the reference's ``gsplat`` package for this path only):
   and the static trainer's appearance module ``appearance.AppearanceOptModule`` (``from gscodec_studio_amd.appearance import
   AppearanceOptModule`` in place of ``from utils import AppearanceOptModule``; ``module.colors(...)`` is the fused form of its call site),
   and the trainers' neighbour search ``utils.{knn, knn_search, init_scales}`` (``knn.py``: ``from gscodec_studio_amd.utils import knn``
-  in place of ``from utils import knn``; exact grid k-NN on the GPU, ``init_scales`` is the three lines that size the initial splats).
+  in place of ``from utils import knn``; exact grid k-NN on the GPU, ``init_scales`` is the three lines that size the initial splats),
+  and ``.ply`` files in the INRIA 3DGS layout without plyfile: ``utils.{load_ply, save_ply, load_ply_to_rasterizer_inputs,
+  read_ply_header}`` (``ply.py``, ``csrc/ply.hip``), with ``utils.{rgb_to_sh, set_random_seed}`` beside them, so that
+  ``from utils import knn, rgb_to_sh, set_random_seed, load_ply`` reads ``from gscodec_studio_amd.utils import ...``.
 """
 from ._wrapper import (
     accumulate,

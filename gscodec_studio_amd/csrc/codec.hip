@@ -11,6 +11,7 @@
 // read and 14 floats written per splat: HBM-bound streaming.  The K-means decode of the higher SH bands is a codebook
 // gather (labels -> dequantized centroid rows).
 #include "gs_common.h"
+#include "decode_act_dev.h"
 
 namespace {
 
@@ -101,13 +102,13 @@ __global__ void __launch_bounds__(GS_BLOCK) decode_splats_kernel(uint64_t n, Dec
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float v = dequant((uint32_t)a.scales[i * 3 + c] >> a.shift[1], a.levels[1], a.mins[3 + c], a.maxs[3 + c]);
-        a.scales_out[i * 3 + c] = a.activate ? expf(v) : v;
+        a.scales_out[i * 3 + c] = a.activate ? decode_act_scale(v) : v;
     }
     float q4[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) q4[c] = dequant((uint32_t)a.quats[i * 4 + c] >> a.shift[2], a.levels[2], a.mins[6 + c], a.maxs[6 + c]);
     if (a.normalize_quats) { // F.normalize(dim=-1): x / max(||x||, 1e-12)
-        const float nrm = fmaxf(sqrtf(q4[0] * q4[0] + q4[1] * q4[1] + q4[2] * q4[2] + q4[3] * q4[3]), 1e-12f);
+        const float nrm = decode_norm_divisor(decode_sumsq(decode_sumsq(decode_sumsq(q4[0] * q4[0], q4[1]), q4[2]), q4[3]));
 #pragma unroll
         for (int c = 0; c < 4; ++c) q4[c] = q4[c] / nrm;
     }
@@ -115,7 +116,7 @@ __global__ void __launch_bounds__(GS_BLOCK) decode_splats_kernel(uint64_t n, Dec
     for (int c = 0; c < 4; ++c) a.quats_out[i * 4 + c] = q4[c];
     {
         const float v = dequant((uint32_t)a.opacities[i] >> a.shift[3], a.levels[3], a.mins[10], a.maxs[10]);
-        a.opac_out[i] = a.activate ? 1.f / (1.f + expf(-v)) : v;
+        a.opac_out[i] = a.activate ? decode_act_opacity(v) : v;
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c)

@@ -7,18 +7,39 @@
   (``csrc/surfel.hip``: ``gs_depth_to_normal_fwd`` / ``_bwd``), GPU only, with the gradient going to ``depths``.
 
 and the trainers' neighbour search (reference ``examples/utils.py:142``), re-exported from ``knn``: ``knn(x, K=4)``,
-``knn_search``, ``init_scales`` (exact grid k-NN on the GPU, ``csrc/knn.hip``).
+``knn_search``, ``init_scales`` (exact grid k-NN on the GPU, ``csrc/knn.hip``), and the other names the trainers import from
+``examples/utils.py``: ``rgb_to_sh``, ``set_random_seed`` (plain restatements, lines 149-157) and ``load_ply`` with ``save_ply``
+and ``load_ply_to_rasterizer_inputs`` beside it, re-exported from ``ply`` (``.ply`` files without plyfile, ``csrc/ply.hip``) -- so
+``from utils import knn, rgb_to_sh, set_random_seed, load_ply`` becomes ``from gscodec_studio_amd.utils import ...``.
 """
 from __future__ import annotations
 
+import random
+
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import Tensor
 
 from .knn import init_scales, knn, knn_search
+from .ply import load_ply, load_ply_to_rasterizer_inputs, read_ply_header, save_ply
 from .surfel import depth_to_normal
 
-__all__ = ["depth_to_points", "depth_to_normal", "knn", "knn_search", "init_scales"]
+__all__ = ["depth_to_points", "depth_to_normal", "knn", "knn_search", "init_scales", "rgb_to_sh", "set_random_seed", "load_ply",
+           "save_ply", "load_ply_to_rasterizer_inputs", "read_ply_header"]
+
+
+def rgb_to_sh(rgb: Tensor) -> Tensor:
+    """Colours in [0, 1] to the degree-0 SH coefficient that renders them (reference ``examples/utils.py:149-151``)."""
+    C0 = 0.28209479177387814
+    return (rgb - 0.5) / C0
+
+
+def set_random_seed(seed: int) -> None:
+    """Seed ``random``, numpy and torch (reference ``examples/utils.py:154-157``)."""
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
 
 
 def depth_to_points(depths: Tensor, camtoworlds: Tensor, Ks: Tensor, z_depth: bool = True) -> Tensor:

@@ -49,7 +49,8 @@ extern "C" {
  * gs_rasterize_2dgs_fwd / _bwd, gs_depth_to_normal_fwd / _bwd), and the spacetime colour decoder's (gs_stg_decode_fwd / _bwd,
  * gs_stg_decode_partial_rows), and the appearance module's (gs_appearance_fwd / _bwd, gs_appearance_partial_rows,
  * gs_appearance_partial_cols), and the K-means entries (gs_kmeans_padded_width, gs_kmeans_default_slices, gs_kmeans_assign,
- * gs_kmeans_update), and the nearest-neighbour entries (gs_knn_cells, gs_knn_finish_grid, gs_knn_search). */
+ * gs_kmeans_update), and the nearest-neighbour entries (gs_knn_cells, gs_knn_finish_grid, gs_knn_search), and the
+ * PLY entries (gs_ply_unpack, gs_ply_pack, gs_ply_max_stride, gs_ply_max_columns, gs_ply_block_rows). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -989,6 +990,36 @@ int32_t gs_knn_finish_grid(uint32_t n, uint32_t ncells, const float *xyz, const 
 int32_t gs_knn_search(uint32_t n, uint32_t m, uint32_t K, const float *sorted_xyzi, const int32_t *cell_starts,
                       const float *queries_xyzi, const double *box, uint32_t rx, uint32_t ry, uint32_t rz, float *dist,
                       int64_t *idx, float *log_scales, float init_scale, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * PLY splat files (ply.hip): the vertex rows of a `binary_little_endian 1.0` .ply in the INRIA 3DGS layout -- what the reference
+ * reads and writes on the host through the plyfile package (examples/simple_trainer.py:414-510 save_ply / load_ply) -- to and
+ * from the six splat tensors, by one kernel each way.  `rows`: n rows of `stride` bytes (1 <= stride <= gs_ply_max_stride() =
+ * 1024), DEVICE memory, 16-byte aligned.  The tensors are six groups in the order means, sh0, shN, opacities, scales, quats:
+ * widths6 (HOST, six counts of floats per row; 0: no such tensor, its pointer is not looked at) and outs6 / ins6 (HOST array of
+ * six DEVICE pointers, float [n, width] each).  cols (HOST, sum of the widths <= gs_ply_max_columns() = 128 entries): for every
+ * float of a row of group 0, then of group 1, ..., the byte offset inside the file's row it comes from (bits 0..15), bit 16 set
+ * for a `double` column (read as float64, rounded to float32 to nearest even), every other bit zero.  The caller builds the
+ * table from the file's header, so property order, skipped columns and the channel-major f_dc_* / f_rest_* to [K, 3]
+ * transposition are all in the table.  A workgroup stages gs_ply_block_rows(stride) rows (256, 128 or 64: the most that fit
+ * 64 KB) in LDS; both sides of the transposition are contiguous in global memory.
+ *
+ * gs_ply_unpack: rows -> tensors.  activate = 1: group 4 (scales) = exp(.), group 3 (opacities) = sigmoid(.);
+ *   normalize_quats = 1: group 5 (quats) = q / max(||q||, 1e-12) -- the arithmetic of gs_decode_splats.  With both 0 every
+ *   float column is a move of bits (NaN payloads, -0 and denormals survive).  Offsets and stride all multiples of 4: word
+ *   reads from LDS; anything else, or force_bytes = 1: byte-wise assembly.
+ * gs_ply_pack: tensors -> rows; float columns only, stride and offsets multiples of 4, no two entries the same offset; bytes of
+ *   a row that no entry covers are written as zero.
+ * Both return a status without launching for a null pointer, n = 0 or n >= 2^31, a stride of 0 or above the limit, rows that
+ * are not 16-byte aligned, too many columns, an unknown flag bit or an offset whose value does not end inside the stride.
+ * Queued on `stream`, no host wait. */
+uint32_t gs_ply_max_stride(void);
+uint32_t gs_ply_max_columns(void);
+uint32_t gs_ply_block_rows(uint32_t stride); /* 0 for a stride outside 1 .. gs_ply_max_stride() */
+int32_t gs_ply_unpack(uint32_t n, uint32_t stride, const uint8_t *rows, const uint32_t *cols, const uint32_t *widths6,
+                      float *const *outs6, int32_t activate, int32_t normalize_quats, int32_t force_bytes, gs_stream_t stream);
+int32_t gs_ply_pack(uint32_t n, uint32_t stride, const uint32_t *cols, const uint32_t *widths6, const float *const *ins6,
+                    uint8_t *rows, gs_stream_t stream);
 
 
 /* ------------------------------------------------------------------------
