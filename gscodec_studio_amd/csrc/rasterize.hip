@@ -1,51 +1,48 @@
-// rasterize.hip -- R5: per-tile front-to-back alpha compositing, fwd + bwd, wave-per-tile
-// kernels for gfx950.
+// rasterize.hip -- per-tile front-to-back alpha compositing, forward and backward, for gfx950.
 //
-// Replaces gsplat/cuda/csrc/rasterize_to_pixels_fwd.cu:16-185 and
-// rasterize_to_pixels_bwd.cu:17-277.  Same per-pixel arithmetic and decisions
-// (alpha = min(0.999, o * exp(-sigma)); skip sigma < 0 or alpha < 1/255; exclusive stop when
-// T (1 - alpha) <= 1e-4; last_ids; alpha-clamp gradient gate -- splat_sample and the constants beside it in
-// rasterize_dev.h, the one definition every kernel here and in rasterize_wide.hip uses), different mapping:
+// Replaces gsplat/cuda/csrc/rasterize_to_pixels_fwd.cu:16-185 and rasterize_to_pixels_bwd.cu:17-277.  Same per-pixel arithmetic
+// and decisions (alpha = min(0.999, o * exp(-sigma)); skip sigma < 0 or alpha < 1/255; exclusive stop when T (1 - alpha) <= 1e-4;
+// last_ids; alpha-clamp gradient gate -- splat_sample and the constants beside it in rasterize_dev.h, the one definition every
+// kernel here and in rasterize_wide.hip uses), different mapping.  Common to every kernel:
 //
-//   * ONE WAVE64 OWNS ONE 16x16 TILE; lane (lx, ly) of an 8x8 grid owns FOUR pixels, one in
-//     each 8x8 quadrant.  No workgroup barriers (the reference's 256-thread block needs two
-//     __syncthreads per 256 splats); a splat record is fetched from LDS once per 256 pixel
-//     evaluations (register blocking over pixels: with one pixel per lane the broadcast
-//     ds_read_b128 traffic alone would saturate the LDS pipe); the four pixels give four
-//     independent dependency chains per lane, and in the backward the cross-lane reduction
-//     is paid once per (tile, splat) on partial sums of 4 pixels.
-//   * LDS-STAGED, COMPACTED SPLAT LISTS: each lane gathers one splat of the tile's sorted
-//     list (flatten_ids -> means2d / conics / opacities / colours) and converts it to what the
-//     inner loop wants: the conic pre-scaled by -log2(e)/2 so that
+//   * A tile of up to 16x16 pixels is four 8x8 QUADRANTS; one wave64 composites one quadrant, lane (lx, ly) = one pixel.
+//   * LDS-STAGED, CULLED SPLAT LISTS: a lane gathers one splat of the tile's sorted list (flatten_ids -> means2d / conics /
+//     opacities / colours) and converts it to what the inner loop wants: the conic pre-scaled by -log2(e)/2 so that
 //         alpha = exp2(dx (a' dx + b' dy) + c' dy^2 + log2 o)      (5 FMA + v_exp_f32).
-//     While a lane holds its splat it computes the axis-aligned extent of the
-//     { alpha >= 1/255 } ellipse (half extents sqrt(2 ln(255 o) Sigma_xx), Sigma = conic^-1) and
-//     tests it against the tile's live pixel rectangle; a __ballot + mbcnt prefix compacts the
-//     survivors, in order, into the LDS record array.  Splats whose 3-sigma bbox touches the
-//     tile but whose visible ellipse does not are never looked at again.  Culling is
-//     conservative (margins below), hence exact: a culled splat has alpha < 1/255 at every
-//     pixel of the tile, which the reference skips too.  The next batch's gathers are issued
-//     before the current batch is processed (software prefetch), and inside a batch the next
-//     record is read while the current one is evaluated.
-//   * The longest lists bound the critical path (their waves run alone at the end of the kernel), so those
-//     waves run at raised priority (s_setprio) and, in the tile forward, without per-batch barriers (SOLO).
-//   * Backward, per (pixel, splat) with the running transmittance T and
+//     While it holds the splat it tests, exactly, whether { alpha >= 1/255 } reaches the live pixel rectangle of a quadrant
+//     (cull_prepare / rect_touch); only the survivors are written to LDS, in list order.  A culled splat has alpha < 1/255 at
+//     every pixel of the rectangle, which the reference skips too.  The next batch's gathers are issued before the current
+//     batch is walked (software prefetch).
+//   * The longest lists bound the critical path (their waves run alone at the end of a kernel): those waves run at raised
+//     priority (s_setprio).
+//
+// Three kernel families:
+//
+//   1. TILE FORWARD, raster_tile_fwd_kernel<CDIM, CKPT>: one 256-thread workgroup per tile, wave q composites quadrant q, the
+//      colours travel in the LDS record.  1..4 channels in one launch (CDIM = channels), 5..16 in one launch of the wide
+//      instances (8, 9, 12, 16), 17..32 as two launches over halves.  The four waves stage cooperatively, or -- the longest
+//      lists -- each for itself (SOLO).  CKPT: per-pixel checkpoints every `seg` list entries and the cost of every
+//      (tile, segment) item, for the segmented backward.  Its stages (pixel of a lane, masked tile, priority, record write,
+//      checkpoint cursor, list index of a record, epilogue) are defined once, in rasterize_dev.h.
+//   2. GENERIC WAVE FORWARD / BACKWARD, raster_wave_fwd_kernel<CDIM> / raster_wave_bwd_kernel<CDIM, CMODE, ABS>: one
+//      independent wave per (tile, quadrant), no workgroup barriers, colours of 5 and more channels read from global memory at
+//      wave-uniform addresses.  The forward without a plan (a C-ABI caller without scratch) and beyond 32 channels, in exact
+//      chunks of 32; the backward whenever there are no checkpoints, and beyond 32 channels in ONE pass (v_out re-read per
+//      splat) so that v_alpha -- and therefore absgrad -- sees every channel, as the reference's single kernel does.
+//   3. SEGMENTED BACKWARDS, raster_seg_bwd_kernel<CDIM, ABS, DET> here (1..4 channels) and raster_seg_bwd_wide_kernel in
+//      rasterize_wide.hip (5..32): one wave per (tile, segment) item restarts from the forward's checkpoint; the items run
+//      longest first (seg_items_build_kernel).  Their shared stages: rasterize_seg_dev.h.
+//
+// Backward, per (pixel, splat) with the running transmittance T and
 //         D = sum_k colour_k v_out_k,   B = sum_{splats behind} fac D   (a scalar),
-//     v_alpha = D T + (T_final (v_alpha_out - bg . v_out) - B) / (1 - alpha) -- the reference's
-//     per-channel "buffer" vector (rasterize_to_pixels_bwd.cu:203-241) collapses to the scalar
-//     B, so the per-pixel state does not grow with the channel count.  Every lane accumulates
-//     over its pixels the moments
+//     v_alpha = D T + (T_final (v_alpha_out - bg . v_out) - B) / (1 - alpha) -- the reference's per-channel "buffer" vector
+//     (rasterize_to_pixels_bwd.cu:203-241) collapses to the scalar B, so the per-pixel state does not grow with the channel
+//     count.  Every lane accumulates the moments
 //       S0 = sum v_sigma, Sx = sum v_sigma dx, Sy, Sxx, Sxy, Syy   and   C_k = sum fac v_out_k;
 //     one DPP reduction per value per (tile, splat), then
 //       v_xy = (a Sx + b Sy, b Sx + c Sy), v_conic = (Sxx/2, Sxy, Syy/2), v_opacity = -S0 / o,
-//     v_colour = C: algebraically the reference's formulas (bwd.cu:221-236) with the per-pixel
-//     conic products hoisted out of the pixel loop.
-//
-// Channel counts: 1..4 use 4 pixels per lane with colours in the LDS record; 5..32 use one
-// quadrant per wave (NQ = 1) with colours read from global memory at wave-uniform addresses;
-// more than 32 channels: forward in exact chunks of 32, backward in ONE pass of the generic
-// kernel (v_out re-read per splat) so that v_alpha -- and therefore absgrad -- sees every
-// channel, as the reference's single CDIM-templated kernel does.
+//     v_colour = C: algebraically the reference's formulas (bwd.cu:221-236) with the per-pixel conic products hoisted out of
+//     the pixel loop.
 #include "gs_common.h"
 #include "rasterize_common.h"
 #include "dpp_reduce.h"
@@ -59,100 +56,47 @@
 namespace {
 
 // ---------------------------------------------------------------------------
-// forward
-//   NQ   : pixels per lane (4: whole tile, one pixel per quadrant; 1: quadrant = blockIdx.y)
-//   CDIM : channels of this launch; COLOR_LDS: colours travel in the LDS record (CDIM <= 4)
-// record: R0 = (mx, my, a', b')  R1 = (c', log2 o, col0, col1)  R2 = (col2, col3, idx, g)
+// generic forward (no plan, or more than 32 channels in chunks of 32): one wave per quadrant (vitem & 3) of a tile, the
+// colours of channels [ch_off, ch_off + cnt), cnt <= CDIM, read from global memory at wave-uniform addresses
+// record: R0 = (mx, my, a', b')  R1 = (c', log2 o, 0, 0)  R2 = (0, 0, idx, g)
 // ---------------------------------------------------------------------------
-// CKPT: write per-pixel checkpoints (T, accumulated colour) "before list entry b" for every
-// b = k * seg strictly inside the tile's range, planar: ckpt[k][c][256] with c = 0 (T), 1..CDIM.
-template <int NQ, int CDIM, bool COLOR_LDS, bool CKPT>
-__global__ void __launch_bounds__(GS_WAVE) raster_wave_fwd_kernel(RasterArgs a, uint32_t cnt, uint32_t ch_off, float *__restrict__ ckpt, int32_t seg) {
+template <int CDIM>
+__global__ void __launch_bounds__(GS_WAVE) raster_wave_fwd_kernel(RasterArgs a, uint32_t cnt, uint32_t ch_off) {
     constexpr int REC = 3;
     __shared__ float4 s_rec[(GS_WAVE + 1) * REC];
     const uint32_t lane = threadIdx.x;
     const uint32_t lx = lane & 7u, ly = lane >> 3;
     const uint32_t vitem = xcd_remap(blockIdx.x, gridDim.x, a.xcd_group);
-    const TileGeom tg = tile_geom(a, (NQ == 4) ? vitem : (vitem >> 2));
-    const uint32_t q_first = (NQ == 4) ? 0u : (vitem & 3u);
+    const TileGeom tg = tile_geom(a, vitem >> 2);
+    const uint32_t q = vitem & 3u;
     const float *bg = a.backgrounds ? a.backgrounds + (size_t)tg.cam * a.channels + ch_off : nullptr;
 
-    bool inside[NQ];
-    float px[NQ], py[NQ];
-    size_t pix[NQ];
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        const uint32_t q = q_first + i;
-        const uint32_t ox = lx + 8u * (q & 1u), oy = ly + 8u * (q >> 1);
-        const uint32_t x = tg.px0 + ox, y = tg.py0 + oy;
-        inside[i] = ox < a.tile_size && oy < a.tile_size && x < a.image_width && y < a.image_height;
-        px[i] = (float)x + 0.5f;
-        py[i] = (float)y + 0.5f;
-        pix[i] = ((size_t)tg.cam * a.image_height + y) * a.image_width + x;
-    }
+    const LanePixel p = lane_pixel(a, tg, q, lx, ly);
+    const float px = p.px, py = p.py;
 
     if (a.masks != nullptr && !a.masks[tg.lin]) {
-#pragma unroll
-        for (int i = 0; i < NQ; ++i)
-            if (inside[i])
-                for (uint32_t k = 0; k < cnt; ++k) a.render_colors[pix[i] * a.channels + ch_off + k] = bg ? bg[k] : 0.f;
+        if (p.inside) store_masked_pixel<0>(a.render_colors, p.pix, a.channels, ch_off, cnt, bg);
         return;
     }
 
-    float T[NQ], Tkeep[NQ], out[NQ][CDIM];
-    int32_t cur[NQ];
-    bool done[NQ];
+    float T = 1.f, Tkeep = 1.f, out[CDIM];
+    int32_t cur = 0;
+    bool done = !p.inside;
 #pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        T[i] = 1.f;
-        Tkeep[i] = 1.f;
-        cur[i] = 0;
-        done[i] = !inside[i];
-#pragma unroll
-        for (int k = 0; k < CDIM; ++k) out[i][k] = 0.f;
-    }
+    for (int k = 0; k < CDIM; ++k) out[k] = 0.f;
 
-    const Rect rect = wave_rect<NQ>(a, tg, q_first);
+    const Rect rect = wave_rect(a, tg, q);
     const int32_t n = rect.empty ? 0 : tg.range_end - tg.range_start;
-    // Batches are aligned to multiples of 64 of the GLOBAL list index (the first one is partial), so
-    // that a checkpoint boundary (a multiple of seg, itself a multiple of 64) always coincides with
-    // a batch start: no per-record boundary test inside the hot loop.
     const int32_t base0 = tg.range_start & ~(GS_WAVE - 1);
     const int32_t num_batches = n > 0 ? (tg.range_end - base0 + GS_WAVE - 1) / GS_WAVE : 0;
-    if (n >= 4 * HEAVY_TILE) __builtin_amdgcn_s_setprio(3);
-    else if (n >= 2 * HEAVY_TILE) __builtin_amdgcn_s_setprio(2);
-    else if (n >= HEAVY_TILE) __builtin_amdgcn_s_setprio(1);
+    raise_priority_for(n);
     auto in_range = [&](int32_t idx) { return idx >= tg.range_start && idx < tg.range_end && n > 0; };
 
     SplatRaw nxt = gather_splat(a, base0 + (int32_t)lane, in_range(base0 + (int32_t)lane));
-    float ncol[COLOR_LDS ? CDIM : 1];
-    if (COLOR_LDS) {
-#pragma unroll
-        for (int k = 0; k < CDIM; ++k)
-            ncol[k] = (in_range(base0 + (int32_t)lane) && (uint32_t)k < cnt) ? a.colors[(size_t)nxt.g * a.s_color + ch_off + k] : 0.f;
-    }
     const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    // next checkpoint boundary strictly inside (range_start, range_end), and its slot
-    int32_t next_b = CKPT ? (tg.range_start / seg + 1) * seg : 0x7fffffff;
-    int32_t next_k = CKPT ? next_b / seg : 0;
-    auto store_ckpt = [&]() {
-        float *base = ckpt + (size_t)next_k * (CDIM + 1) * 256;
-#pragma unroll
-        for (int i = 0; i < NQ; ++i) {
-            const uint32_t p = (q_first + i) * 64u + lane;
-            base[p] = done[i] ? Tkeep[i] : T[i];
-#pragma unroll
-            for (int k = 0; k < CDIM; ++k) base[(k + 1) * 256 + p] = out[i][k];
-        }
-    };
 
     for (int32_t b = 0; b < num_batches; ++b) {
         const int32_t batch_start = base0 + b * GS_WAVE;
-        if (CKPT && batch_start == next_b && next_b < tg.range_end) { // state before list entry next_b
-            store_ckpt();
-            next_b += seg;
-            next_k += 1;
-        }
         // ---- cull + compact the prefetched splats into LDS
         SplatRaw s = nxt;
         CullSplat cs;
@@ -162,26 +106,13 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_fwd_kernel(RasterArgs a, 
         const int count = __popcll(lm);
         if (live) {
             const int slot = __popcll(lm & lt_mask);
-            float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f;
-            if (COLOR_LDS) {
-                c0 = ncol[0];
-                if (CDIM > 1) c1 = ncol[CDIM > 1 ? 1 : 0];
-                if (CDIM > 2) c2 = ncol[CDIM > 2 ? 2 : 0];
-                if (CDIM > 3) c3 = ncol[CDIM > 3 ? 3 : 0];
-            }
-            s_rec[slot * REC + 0] = make_float4(s.mx, s.my, -0.5f * LOG2E * s.ca, -LOG2E * s.cb);
-            s_rec[slot * REC + 1] = make_float4(-0.5f * LOG2E * s.cc, __log2f(s.opac), c0, c1);
-            s_rec[slot * REC + 2] = make_float4(c2, c3, __int_as_float(batch_start + (int32_t)lane), __int_as_float(s.g));
+            write_record<0>(&s_rec[slot * REC], s, nullptr); // the colours stay in global memory
+            s_rec[slot * REC + 2] = make_float4(0.f, 0.f, __int_as_float(batch_start + (int32_t)lane), __int_as_float(s.g));
         }
         // ---- prefetch the next batch
         if (b + 1 < num_batches) {
             const int32_t ni = batch_start + GS_WAVE + (int32_t)lane;
             nxt = gather_splat(a, ni, in_range(ni));
-            if (COLOR_LDS) {
-#pragma unroll
-                for (int k = 0; k < CDIM; ++k)
-                    ncol[k] = (in_range(ni) && (uint32_t)k < cnt) ? a.colors[(size_t)nxt.g * a.s_color + ch_off + k] : 0.f;
-            }
         }
         __builtin_amdgcn_wave_barrier();
 
@@ -189,78 +120,47 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_fwd_kernel(RasterArgs a, 
         // is ONE fma per record (T <- T - T a): a finished pixel keeps multiplying (its
         // contributions are masked by `done`, its final transmittance is parked in Tkeep), so the
         // alpha evaluation of the next records overlaps the composite of the current one.
-        auto composite = [&](const float4 &c0, const float4 &c1, const float4 &c2, bool rec_ok) {
+        auto composite = [&](const float4 &c0, const float4 &c1, const float4 &c2) {
             float col[CDIM];
-            if (COLOR_LDS) {
-                col[0] = c1.z;
-                if (CDIM > 1) col[CDIM > 1 ? 1 : 0] = c1.w;
-                if (CDIM > 2) col[CDIM > 2 ? 2 : 0] = c2.x;
-                if (CDIM > 3) col[CDIM > 3 ? 3 : 0] = c2.y;
-            } else {
-                const float *cp = a.colors + (size_t)__float_as_int(c2.w) * a.s_color + ch_off;
+            const float *cp = a.colors + (size_t)__float_as_int(c2.w) * a.s_color + ch_off;
 #pragma unroll
-                for (int k = 0; k < CDIM; ++k) col[k] = ((uint32_t)k < cnt && rec_ok) ? cp[k] : 0.f;
-            }
+            for (int k = 0; k < CDIM; ++k) col[k] = (uint32_t)k < cnt ? cp[k] : 0.f;
             const int32_t idx = __float_as_int(c2.z);
+            const float dx = c0.x - px, dy = c0.y - py;
+            SplatSample sm;
+            const bool ok = splat_sample(dx, dy, c0.z, c0.w, c1.x, c1.y, sm);
+            const float a_eff = ok ? sm.alpha : 0.f;
+            const float Tj = T;
+            const float next_T = Tj - Tj * a_eff;     // the loop-carried chain
+            const bool stop = ok && (next_T <= T_MIN); // exclusive stop
+            const bool use = !done && !stop;           // this record is composited
+            Tkeep = done ? Tkeep : Tj;                 // transmittance before the stopping splat
+            const float vis = use ? a_eff * Tj : 0.f;
 #pragma unroll
-            for (int i = 0; i < NQ; ++i) {
-                const float dx = c0.x - px[i], dy = c0.y - py[i];
-                SplatSample sm;
-                const bool ok = splat_sample(dx, dy, c0.z, c0.w, c1.x, c1.y, sm, rec_ok);
-                const float a_eff = ok ? sm.alpha : 0.f;
-                const float Tj = T[i];
-                const float next_T = Tj - Tj * a_eff;         // the loop-carried chain
-                const bool stop = ok && (next_T <= T_MIN);     // exclusive stop
-                const bool live = !done[i] && !stop;          // this record is composited
-                Tkeep[i] = done[i] ? Tkeep[i] : Tj;           // transmittance before the stopping splat
-                const float vis = live ? a_eff * Tj : 0.f;
-#pragma unroll
-                for (int k = 0; k < CDIM; ++k) out[i][k] += col[k] * vis;
-                cur[i] = (live && ok) ? idx : cur[i];
-                done[i] = done[i] || stop;
-                T[i] = next_T;
-            }
+            for (int k = 0; k < CDIM; ++k) out[k] += col[k] * vis;
+            cur = (use && ok) ? idx : cur;
+            done = done || stop;
+            T = next_T;
         };
         {
             int j = 0;
             for (; j + 1 < count; j += 2) {
                 const float4 a0 = s_rec[j * REC + 0], a1 = s_rec[j * REC + 1], a2 = s_rec[j * REC + 2];
                 const float4 b0 = s_rec[j * REC + 3], b1 = s_rec[j * REC + 4], b2 = s_rec[j * REC + 5];
-                composite(a0, a1, a2, true);
-                composite(b0, b1, b2, true);
+                composite(a0, a1, a2);
+                composite(b0, b1, b2);
             }
             if (j < count) {
                 const float4 a0 = s_rec[j * REC + 0], a1 = s_rec[j * REC + 1], a2 = s_rec[j * REC + 2];
-                composite(a0, a1, a2, true);
+                composite(a0, a1, a2);
             }
         }
         // ---- early exit when every pixel of the wave is finished
-        bool all_done = true;
-#pragma unroll
-        for (int i = 0; i < NQ; ++i) all_done = all_done && done[i];
-        if (__all(all_done)) break;
+        if (__all(done)) break;
         __builtin_amdgcn_wave_barrier();
     }
 
-    if (CKPT && !rect.empty) {
-        // boundaries after the last live record (or after an early exit) carry the final state
-        while (next_b < tg.range_end) {
-            store_ckpt();
-            next_b += seg;
-            next_k += 1;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        if (!inside[i]) continue;
-        const float Tf = done[i] ? Tkeep[i] : T[i];
-        a.render_alphas[pix[i]] = 1.f - Tf;
-#pragma unroll
-        for (int k = 0; k < CDIM; ++k)
-            if ((uint32_t)k < cnt)
-                a.render_colors[pix[i] * a.channels + ch_off + k] = bg ? out[i][k] + Tf * bg[k] : out[i][k];
-        a.last_ids[pix[i]] = cur[i];
-    }
+    if (p.inside) store_pixel<CDIM>(a, p.pix, a.channels, ch_off, cnt, true, done ? Tkeep : T, out, cur, bg);
 }
 
 // ---------------------------------------------------------------------------
@@ -268,8 +168,9 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_fwd_kernel(RasterArgs a, 
 // composites quadrant q, and the four waves STAGE COOPERATIVELY: per batch of 256 list entries
 // every thread gathers ONE entry, tests it exactly against all four quadrant rectangles
 // (rect_touch) and writes its record once; four ballots per wave give one 64-bit mask per
-// (64-entry sub-batch, quadrant).  After one barrier, wave q walks the set bits of "its" four
-// masks (s_ff1 on SGPRs) and reads the records as LDS broadcasts.
+// (64-entry sub-batch, quadrant) and, through mbcnt, a compacted list of record offsets per
+// (sub-batch, quadrant).  After one barrier, wave q walks "its" four lists and reads the records
+// as LDS broadcasts.
 // Why (measured with per-wave timestamps): with one independent wave per
 // quadrant the kernel's duration was the life of the heaviest waves (list 5-6k entries, 311 us of
 // a 320 us kernel), and ~60% of that was the exposed latency of the two dependent gathers
@@ -277,7 +178,7 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_fwd_kernel(RasterArgs a, 
 // evaluate per batch.  Here a heavy tile takes 4x fewer, 4x larger batches, the gathers are
 // prefetched two levels deep (ids two batches ahead, splat data one batch ahead) and are hidden
 // behind ~60 record evaluations, and every entry is gathered once per tile instead of four times.
-// LDS is double-buffered so that one __syncthreads per batch suffices.
+// LDS is double-buffered so that one LDS-only barrier per batch suffices.
 // Sub-batches are aligned to multiples of 64 of the GLOBAL list index, so a checkpoint boundary
 // (multiple of seg) always coincides with a sub-batch start.
 // ---------------------------------------------------------------------------
@@ -321,14 +222,13 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
     const bool cost_owner = !WIDE || ch_off == 0u;
     if (CKPT && cost_owner && blockIdx.x == 0 && tid < (uint32_t)COST_CLASSES) class_count[tid] = 0u;
     const TileGeom tg = tile_geom(a, a.tile_order != nullptr ? a.tile_order[blockIdx.x] : xcd_remap(blockIdx.x, gridDim.x, a.xcd_group));
-    const float *bg = a.backgrounds ? a.backgrounds + (size_t)tg.cam * a.channels + (WIDE ? ch_off : 0u) : nullptr;
-    const uint32_t CH = WIDE ? a.channels : (uint32_t)CDIM; // channels of the output image / checkpoint planes
+    // the channel window [ch0, ch0 + nch) of this launch in the CH channels of the output image / checkpoint planes
+    const uint32_t CH = WIDE ? a.channels : (uint32_t)CDIM, ch0 = WIDE ? ch_off : 0u, nch = WIDE ? cnt : (uint32_t)CDIM;
+    const float *bg = a.backgrounds ? a.backgrounds + (size_t)tg.cam * a.channels + ch0 : nullptr;
 
-    const uint32_t ox = lx + 8u * (w & 1u), oy = ly + 8u * (w >> 1);
-    const uint32_t x = tg.px0 + ox, y = tg.py0 + oy;
-    const bool inside = ox < a.tile_size && oy < a.tile_size && x < a.image_width && y < a.image_height;
-    const float px = (float)x + 0.5f, py = (float)y + 0.5f;
-    const size_t pix = ((size_t)tg.cam * a.image_height + y) * a.image_width + x;
+    const LanePixel p = lane_pixel(a, tg, w, lx, ly);
+    const bool inside = p.inside;
+    const float px = p.px, py = p.py;
 
     // Side job: this workgroup's slice of the buffer the matching backward will accumulate into (zf, see gs_rasterize_fwd).
     // Issued as the workgroup's LAST instructions: nothing waits for the stores, and the memory pipes are mostly idle
@@ -345,11 +245,7 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
     };
 
     if (a.masks != nullptr && !a.masks[tg.lin]) {
-        if (inside) {
-#pragma unroll
-            for (int k = 0; k < CDIM; ++k)
-                if (!WIDE || (uint32_t)k < cnt) a.render_colors[pix * CH + (WIDE ? ch_off : 0u) + k] = bg ? bg[k] : 0.f;
-        }
+        if (inside) store_masked_pixel<CDIM>(a.render_colors, p.pix, CH, ch0, nch, bg);
         zero_fill_slice();
         return;
     }
@@ -358,7 +254,7 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
     bool qdone[4]; // block-uniform: quadrant finished (or empty)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const Rect r = wave_rect<1>(a, tg, (uint32_t)q);
+        const Rect r = wave_rect(a, tg, (uint32_t)q);
         qx0[q] = r.x0; qx1[q] = r.x1; qy0[q] = r.y0; qy1[q] = r.y1;
         qdone[q] = r.empty;
     }
@@ -372,10 +268,7 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
     const int32_t n = tg.range_end - tg.range_start;
     const int32_t base0 = tg.range_start & ~(GS_WAVE - 1);
     const int32_t num_batches = n > 0 ? (tg.range_end - base0 + BATCH - 1) / BATCH : 0;
-    // graded issue priority: the longest lists bound the kernel, they must win arbitration on their SIMD
-    if (n >= 4 * HEAVY_TILE) __builtin_amdgcn_s_setprio(3);
-    else if (n >= 2 * HEAVY_TILE) __builtin_amdgcn_s_setprio(2);
-    else if (n >= HEAVY_TILE) __builtin_amdgcn_s_setprio(1);
+    raise_priority_for(n);
     auto in_range = [&](int32_t idx) { return idx >= tg.range_start && idx < tg.range_end; };
     auto load_id = [&](int32_t idx) { return in_range(idx) ? a.flatten_ids[idx] : -1; };
     struct Staged {
@@ -392,48 +285,37 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
             else fetch_splat<CDIM>(a, g, o.s, o.col);
         }
     };
-    // the record of one staged entry (R0, R1 and the colour float4s behind them)
-    auto write_rec = [&](float4 *r, const Staged &st) {
-        r[0] = make_float4(st.s.mx, st.s.my, -0.5f * LOG2E * st.s.ca, -LOG2E * st.s.cb);
-        r[1] = make_float4(-0.5f * LOG2E * st.s.cc, __log2f(st.s.opac), st.col[0], st.col[CDIM > 1 ? 1 : 0]);
-#pragma unroll
-        for (int j = 0; j < NCW; ++j) {
-            auto c = [&](int k) { return k < CDIM ? st.col[k < CDIM ? k : 0] : 0.f; };
-            r[2 + j] = make_float4(c(2 + 4 * j), c(3 + 4 * j), c(4 + 4 * j), c(5 + 4 * j));
-        }
-    };
     int32_t id_cur = load_id(base0 + (int32_t)tid);
     int32_t id_nxt = load_id(base0 + BATCH + (int32_t)tid);
     Staged nxt;
     gather(id_cur, nxt);
 
-    // first boundary this workgroup stores: strictly inside the list
-    int32_t next_b = CKPT ? (tg.range_start / seg + 1) * seg : 0x7fffffff;
-    int32_t next_k = CKPT ? next_b / seg : 0;
+    CkptCursor ck;
+    ck.first(CKPT, tg.range_start, seg);
     // COST of every backward work item (tile, segment) = records this wave evaluated inside the segment: the backward's
     // work list is ordered by it, longest first (seg_items_sorted_kernel).  The tile's first segment reports into
     // cost_head[tile][wave]; a later segment k owns boundary k * seg and reports into cost_body[k][wave] -- written once
     // per (item, wave), no zero-fill and no atomics.
     uint32_t evals = 0;
     bool first_seg = true;
-    auto store_cost = [&]() { // the segment in front of boundary next_k has ended
+    auto store_cost = [&]() { // the segment in front of boundary ck.next_k has ended
         if (lane == 0 && cost_owner) {
             if (first_seg) cost_head[tg.lin * 4u + w] = evals;
             else {
-                cost_body[(size_t)(next_k - 1) * 4u + w] = evals;
-                if (w == 0u) body_tile[next_k - 1] = tg.lin; // the tile that owns boundary (next_k - 1) * seg
+                cost_body[(size_t)(ck.next_k - 1) * 4u + w] = evals;
+                if (w == 0u) body_tile[ck.next_k - 1] = tg.lin; // the tile that owns boundary (ck.next_k - 1) * seg
             }
         }
         evals = 0;
         first_seg = false;
     };
     auto store_ckpt = [&]() {
-        float *base = ckpt + (size_t)next_k * (CH + 1) * 256;
-        const uint32_t p = w * 64u + lane;
-        if (!WIDE || ch_off == 0u) base[p] = T;
+        float *base = ckpt + (size_t)ck.next_k * (CH + 1) * 256;
+        const uint32_t slot = w * 64u + lane;
+        if (cost_owner) base[slot] = T;
 #pragma unroll
         for (int k = 0; k < CDIM; ++k)
-            if (!WIDE || (uint32_t)k < cnt) base[((WIDE ? ch_off : 0u) + k + 1) * 256 + p] = out[k];
+            if ((uint32_t)k < nch) base[(ch0 + k + 1) * 256 + slot] = out[k];
         store_cost();
     };
 
@@ -448,89 +330,89 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
     // all evaluations; the padding is still written (harmless) but no longer walked)
     auto group = [&](auto gtag, const list_t *offs, uint32_t &cur_off) {
         constexpr int G = decltype(gtag)::value;
-                float4 c0[G], c1[G];
-                float c2x[G], c2y[G]; // colours 2, 3 (only what CDIM needs is read)
-                float4 cw[G][WIDE ? NCW : 1]; // WIDE: colours 2 .. CDIM - 1
-                uint32_t off[G];
-                {
+        float4 c0[G], c1[G];
+        float c2x[G], c2y[G]; // colours 2, 3 (only what CDIM needs is read)
+        float4 cw[G][WIDE ? NCW : 1]; // WIDE: colours 2 .. CDIM - 1
+        uint32_t off[G];
+        {
 #pragma unroll
-                    for (int g = 0; g < G; ++g) off[g] = offs[g];
+            for (int g = 0; g < G; ++g) off[g] = offs[g];
 #pragma unroll
-                    for (int g = 0; g < G; ++g) {
-                        const float4 *r = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_rec) + off[g]);
-                        c0[g] = r[0];
-                        c1[g] = r[1];
-                        c2x[g] = c2y[g] = 0.f;
-                        if constexpr (WIDE) {
+            for (int g = 0; g < G; ++g) {
+                const float4 *r = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_rec) + off[g]);
+                c0[g] = r[0];
+                c1[g] = r[1];
+                c2x[g] = c2y[g] = 0.f;
+                if constexpr (WIDE) {
 #pragma unroll
-                            for (int j = 0; j < NCW; ++j) cw[g][j] = r[2 + j];
-                        }
-                        if (CDIM == 3) c2x[g] = reinterpret_cast<const float *>(r + 2)[0];
-                        if (CDIM == 4) {
-                            const float2 v = reinterpret_cast<const float2 *>(r + 2)[0];
-                            c2x[g] = v.x;
-                            c2y[g] = v.y;
-                        }
-                    }
+                    for (int j = 0; j < NCW; ++j) cw[g][j] = r[2 + j];
                 }
-                // The forward is ~80 % VALU-issue bound (every extra instruction per record costs ~6 us of the kernel, round 2):
-                // the selects are merged (one for the alpha actually applied, one for the last contributor, both on the same
-                // condition) and the conditions themselves combined on the scalar unit.
-                float alpha[G];
-                bool ok[G];
-#pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    const float dx = c0[g].x - px, dy = c0[g].y - py;
-                    SplatSample sm;
-                    ok[g] = splat_sample(dx, dy, c0[g].z, c0[g].w, c1[g].x, c1[g].y, sm);
-                    alpha[g] = sm.alpha;
+                if (CDIM == 3) c2x[g] = reinterpret_cast<const float *>(r + 2)[0];
+                if (CDIM == 4) {
+                    const float2 v = reinterpret_cast<const float2 *>(r + 2)[0];
+                    c2x[g] = v.x;
+                    c2y[g] = v.y;
                 }
-                // T is FROZEN at the stopping splat (= the transmittance in front of it, what the epilogue and the
-                // checkpoints need), so a live pixel always has T > 1e-4 and a rejected record (a_eff = 0) cannot stop it
+            }
+        }
+        // The forward is ~80 % VALU-issue bound (every extra instruction per record costs ~6 us of the kernel, round 2):
+        // the selects are merged (one for the alpha actually applied, one for the last contributor, both on the same
+        // condition) and the conditions themselves combined on the scalar unit.
+        float alpha[G];
+        bool ok[G];
 #pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    // exclusive stop: the record that would take T to <= 1e-4 is not composited and ends the pixel.  ONE
-                    // select (the alpha actually applied: 0 for a finished or finishing pixel) instead of separate selects
-                    // for the weight and for T -- T is then recomputed with it (a second fma is cheaper than a select)
-                    const float Tj = T;
-                    const bool stop = ok[g] && (__builtin_fmaf(-Tj, alpha[g], Tj) <= T_MIN);
-                    done = done || stop;
-                    const bool use = ok[g] && !done; // composited: accepted, and the pixel neither finished nor finishing
-                    const float a_use = use ? alpha[g] : 0.f;
-                    const float vis = a_use * Tj;
-                    out[0] += c1[g].z * vis;
-                    if (CDIM > 1) out[CDIM > 1 ? 1 : 0] += c1[g].w * vis;
-                    if constexpr (WIDE) {
+        for (int g = 0; g < G; ++g) {
+            const float dx = c0[g].x - px, dy = c0[g].y - py;
+            SplatSample sm;
+            ok[g] = splat_sample(dx, dy, c0[g].z, c0[g].w, c1[g].x, c1[g].y, sm);
+            alpha[g] = sm.alpha;
+        }
+        // T is FROZEN at the stopping splat (= the transmittance in front of it, what the epilogue and the
+        // checkpoints need), so a live pixel always has T > 1e-4 and a rejected record (a_eff = 0) cannot stop it
 #pragma unroll
-                        for (int k = 2; k < CDIM; ++k) {
-                            const float4 v = cw[g][(k - 2) / 4];
-                            const int e = (k - 2) % 4;
-                            out[k] += (e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w) * vis;
-                        }
-                    } else {
-                    if (CDIM > 2) out[CDIM > 2 ? 2 : 0] += c2x[g] * vis;
-                    if (CDIM > 3) out[CDIM > 3 ? 3 : 0] += c2y[g] * vis;
-                    }
-                    cur_off = use ? off[g] : cur_off;
-                    T = __builtin_fmaf(-Tj, a_use, Tj);
+        for (int g = 0; g < G; ++g) {
+            // exclusive stop: the record that would take T to <= 1e-4 is not composited and ends the pixel.  ONE
+            // select (the alpha actually applied: 0 for a finished or finishing pixel) instead of separate selects
+            // for the weight and for T -- T is then recomputed with it (a second fma is cheaper than a select)
+            const float Tj = T;
+            const bool stop = ok[g] && (__builtin_fmaf(-Tj, alpha[g], Tj) <= T_MIN);
+            done = done || stop;
+            const bool use = ok[g] && !done; // composited: accepted, and the pixel neither finished nor finishing
+            const float a_use = use ? alpha[g] : 0.f;
+            const float vis = a_use * Tj;
+            out[0] += c1[g].z * vis;
+            if (CDIM > 1) out[CDIM > 1 ? 1 : 0] += c1[g].w * vis;
+            if constexpr (WIDE) {
+#pragma unroll
+                for (int k = 2; k < CDIM; ++k) {
+                    const float4 v = cw[g][(k - 2) / 4];
+                    const int e = (k - 2) % 4;
+                    out[k] += (e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w) * vis;
                 }
+            } else {
+                if (CDIM > 2) out[CDIM > 2 ? 2 : 0] += c2x[g] * vis;
+                if (CDIM > 3) out[CDIM > 3 ? 3 : 0] += c2y[g] * vis;
+            }
+            cur_off = use ? off[g] : cur_off;
+            T = __builtin_fmaf(-Tj, a_use, Tj);
+        }
     };
     auto walk = [&](const list_t *lst, const uint32_t cnt, uint32_t &cur_off) {
-            // FOUR records per iteration, in one basic block: a lone wave issues one instruction per
-            // ~5 cycles and a record is a ~25-deep dependent chain, so one record at a time costs
-            // ~390 cycles (measured) against ~40 instructions x 5 cycles of issue.  The four alpha
-            // evaluations are independent; only T <- T - T a (one fma) is carried from record to record.
-            // The records come from the compacted list of this (sub-batch, quadrant): no bit scan, no validity flags.
-            // (No explicit prefetch of the next group: it cost 40 VGPRs, i.e. two waves per SIMD, and the
-            // kernel's duration is rounds of workgroups x their lifetime, not the walk of one list.)
-            const uint32_t full = cnt & ~(uint32_t)(GW - 1);
-            Pack pk_next = *reinterpret_cast<const Pack *>(lst); // GW record offsets, one broadcast read
-            for (uint32_t j = 0; j < full; j += GW) {
-                const Pack pk = pk_next;
-                pk_next = *reinterpret_cast<const Pack *>(lst + j + GW); // next group's offsets (row is 72 long: in bounds)
-                group(std::integral_constant<int, GW>{}, pk.v, cur_off);
-            }
-            for (uint32_t j = full; j < cnt; ++j) group(std::integral_constant<int, 1>{}, lst + j, cur_off);
+        // FOUR records per iteration, in one basic block: a lone wave issues one instruction per
+        // ~5 cycles and a record is a ~25-deep dependent chain, so one record at a time costs
+        // ~390 cycles (measured) against ~40 instructions x 5 cycles of issue.  The four alpha
+        // evaluations are independent; only T <- T - T a (one fma) is carried from record to record.
+        // The records come from the compacted list of this (sub-batch, quadrant): no bit scan, no validity flags.
+        // (No explicit prefetch of the next group: it cost 40 VGPRs, i.e. two waves per SIMD, and the
+        // kernel's duration is rounds of workgroups x their lifetime, not the walk of one list.)
+        const uint32_t full = cnt & ~(uint32_t)(GW - 1);
+        Pack pk_next = *reinterpret_cast<const Pack *>(lst); // GW record offsets, one broadcast read
+        for (uint32_t j = 0; j < full; j += GW) {
+            const Pack pk = pk_next;
+            pk_next = *reinterpret_cast<const Pack *>(lst + j + GW); // next group's offsets (row is 72 long: in bounds)
+            group(std::integral_constant<int, GW>{}, pk.v, cur_off);
+        }
+        for (uint32_t j = full; j < cnt; ++j) group(std::integral_constant<int, 1>{}, lst + j, cur_off);
     };
 
     // ---- SOLO path for the longest lists.  A tile's lifetime under the cooperative scheme is the sum over its batches
@@ -569,17 +451,7 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
                 }
                 m = __ballot(touch);
                 if (touch) {
-                    float4 *r = &s_rec[slot * REC];
-                    if constexpr (WIDE) write_rec(r, st);
-                    else {
-                    float c0 = st.col[0], c1 = 0.f, c2 = 0.f, c3 = 0.f;
-                    if (CDIM > 1) c1 = st.col[CDIM > 1 ? 1 : 0];
-                    if (CDIM > 2) c2 = st.col[CDIM > 2 ? 2 : 0];
-                    if (CDIM > 3) c3 = st.col[CDIM > 3 ? 3 : 0];
-                    r[0] = make_float4(st.s.mx, st.s.my, -0.5f * LOG2E * st.s.ca, -LOG2E * st.s.cb);
-                    r[1] = make_float4(-0.5f * LOG2E * st.s.cc, __log2f(st.s.opac), c0, c1);
-                    if (CDIM > 2) r[2] = make_float4(c2, c3, 0.f, 0.f);
-                    }
+                    write_record<CDIM>(&s_rec[slot * REC], st.s, st.col);
                     const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
                     s_list[buf][w][w][below] = (list_t)(slot * REC * 16u);
                 }
@@ -590,17 +462,12 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
             if (sbi + 1 < n_sb) gather(sid_cur, snx);
             sid_nxt = (sbi + 2 < n_sb) ? load_id(sb_start + 2 * GS_WAVE + (int32_t)lane) : -1;
             __builtin_amdgcn_wave_barrier(); // (LDS operations of one wave complete in order)
-            if (CKPT && sb_start == next_b && next_b < tg.range_end) { // state before list entry next_b
-                store_ckpt();
-                next_b += seg;
-                next_k += 1;
-            }
+            if (CKPT) ck.before(sb_start, tg.range_end, seg, store_ckpt);
             if (m == 0ull) continue;
             uint32_t cur_off = 0xffffffffu;
             if (CKPT) evals += (uint32_t)__popcll(m);
             walk(&s_list[buf][w][w][0], (uint32_t)__popcll(m), cur_off);
-            if (cur_off != 0xffffffffu)
-                cur = sb_start + (int32_t)((WIDE ? (cur_off >> 4) / (uint32_t)REC : (((cur_off >> 4) * 43691u) >> 17)) & 63u);
+            if (cur_off != 0xffffffffu) cur = sb_start + (int32_t)(record_index<REC>(cur_off >> 4) & 63u); // (slot & 63 = the staging lane)
             if (__all(done)) break;
         }
     } else
@@ -623,19 +490,7 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
                 any_touch |= touch;
                 m[q] = __ballot(touch);
             }
-            if (any_touch) {
-                float4 *r = &s_rec[(buf * BATCH + tid) * REC];
-                if constexpr (WIDE) write_rec(r, st);
-                else {
-                float c0 = st.col[0], c1 = 0.f, c2 = 0.f, c3 = 0.f;
-                if (CDIM > 1) c1 = st.col[CDIM > 1 ? 1 : 0];
-                if (CDIM > 2) c2 = st.col[CDIM > 2 ? 2 : 0];
-                if (CDIM > 3) c3 = st.col[CDIM > 3 ? 3 : 0];
-                r[0] = make_float4(st.s.mx, st.s.my, -0.5f * LOG2E * st.s.ca, -LOG2E * st.s.cb);
-                r[1] = make_float4(-0.5f * LOG2E * st.s.cc, __log2f(st.s.opac), c0, c1);
-                if (CDIM > 2) r[2] = make_float4(c2, c3, 0.f, 0.f);
-                }
-            }
+            if (any_touch) write_record<CDIM>(&s_rec[(buf * BATCH + tid) * REC], st.s, st.col);
             {
                 // compacted lists: a lone wave issues one instruction per ~5 cycles WHATEVER its kind, so the consumer
                 // must not spend a dozen scalar instructions per record on bit scans -- it reads ready-made offsets
@@ -672,11 +527,7 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
         for (int sub = 0; sub < 4; ++sub) {
             const int32_t sb_start = batch_start + sub * GS_WAVE;
             if (sb_start >= tg.range_end) break;
-            if (CKPT && sb_start == next_b && next_b < tg.range_end) { // state before list entry next_b
-                store_ckpt();
-                next_b += seg;
-                next_k += 1;
-            }
+            if (CKPT) ck.before(sb_start, tg.range_end, seg, store_ckpt);
             unsigned long long m = s_mask[buf][sub][w];
             m = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(m >> 32)) << 32) |
                 (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)m); // (the builtin returns int: no sign extension)
@@ -685,29 +536,19 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
             walk(&s_list[buf][sub][w][0], (uint32_t)__popcll(m), cur_off);
             if (__all(done)) break;
         }
-        if (cur_off != 0xffffffffu) // offset -> list index: (offset / 16 - buffer base) / 3, exact for these small multiples of 3
-            cur = batch_start + (int32_t)(WIDE ? ((cur_off >> 4) - buf * (uint32_t)(BATCH * REC)) / (uint32_t)REC
-                                               : ((((cur_off >> 4) - buf * (uint32_t)(BATCH * REC)) * 43691u) >> 17));
+        if (cur_off != 0xffffffffu) cur = batch_start + (int32_t)record_index<REC>((cur_off >> 4) - buf * (uint32_t)(BATCH * REC));
         if (NBUF == 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // nobody restages while a wave still walks this batch
     }
 
     if (CKPT && n > 0) {
         // boundaries after the last composited record (or after an early exit) carry the final state
-        while (next_b < tg.range_end) {
+        while (ck.next_b < tg.range_end) {
             store_ckpt();
-            next_b += seg;
-            next_k += 1;
+            ck.advance(seg);
         }
         store_cost(); // the tile's last segment
     }
-    if (inside) {
-        const float Tf = T;
-        if (!WIDE || ch_off == 0u) a.render_alphas[pix] = 1.f - Tf;
-#pragma unroll
-        for (int k = 0; k < CDIM; ++k)
-            if (!WIDE || (uint32_t)k < cnt) a.render_colors[pix * CH + (WIDE ? ch_off : 0u) + k] = bg ? out[k] + Tf * bg[k] : out[k];
-        if (!WIDE || ch_off == 0u) a.last_ids[pix] = cur;
-    }
+    if (inside) store_pixel<CDIM>(a, p.pix, CH, ch0, nch, cost_owner, T, out, cur, bg);
     zero_fill_slice();
 }
 
@@ -781,17 +622,13 @@ void launch_tile_fwd(const RasterArgs &a, const RasterScratch &v, int32_t solo_m
 }
 
 // ---------------------------------------------------------------------------
-// backward
+// generic backward (no checkpoints, or more than 32 channels): one wave per quadrant of a tile, the whole list back to front
 //   CMODE: 0 = colours in the LDS record (CDIM <= 4, v_out in registers)
 //          1 = colours from global, v_out in registers (CDIM <= 32)
 //          2 = any channel count: colours and v_out from global per splat (CDIM unused)
 // record: R0, R1 as forward; R2 = (col2, col3, idx, g); R3 = (a, b, c, o)
 // ---------------------------------------------------------------------------
-// SEG: blockIdx.x indexes a work item (tile, k): the list entries [k*seg, (k+1)*seg) of that
-// tile.  The state at the item's far end comes from the forward's checkpoint k+1
-// (T, accumulated colour) and the final render: B = v_out . (colour_final - colour_ckpt).
-
-template <int NQ, int CDIM, int CMODE, bool ABS>
+template <int CDIM, int CMODE, bool ABS>
 __global__ void __launch_bounds__(GS_WAVE) raster_wave_bwd_kernel(RasterArgs a, RasterGradArgs ga, uint32_t cnt, uint32_t ch_off, int use_v_alpha) {
     constexpr int REC = 4;
     constexpr int CR = (CMODE == 2) ? 1 : CDIM; // registers for v_out / colour sums
@@ -799,51 +636,38 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_bwd_kernel(RasterArgs a, 
     const uint32_t lane = threadIdx.x;
     const uint32_t lx = lane & 7u, ly = lane >> 3;
     const uint32_t vitem = xcd_remap(blockIdx.x, gridDim.x, a.xcd_group);
-    const TileGeom tg = tile_geom(a, (NQ == 4) ? vitem : (vitem >> 2));
+    const TileGeom tg = tile_geom(a, vitem >> 2);
     if (a.masks != nullptr && !a.masks[tg.lin]) return;
-    const uint32_t q_first = (NQ == 4) ? 0u : (vitem & 3u);
-    const Rect rect = wave_rect<NQ>(a, tg, q_first);
+    const uint32_t q = vitem & 3u;
+    const Rect rect = wave_rect(a, tg, q);
     if (rect.empty || tg.range_end <= tg.range_start) return;
 
-    bool inside[NQ];
-    float px[NQ], py[NQ], T[NQ], Tw[NQ], Bq[NQ], vc[NQ][CR];
-    int32_t bin_final[NQ];
-    size_t pixv[NQ];
-    int64_t vpix[NQ]; // the same pixel in v_render_colors (its own strides)
     const float *bg = a.backgrounds ? a.backgrounds + (size_t)tg.cam * a.channels + ch_off : nullptr;
-    int32_t bin_max = -1;
+    // (not lane_pixel: an outside lane's pixel index is 0 here, and with the select behind the function every instance grows by 1 .. 8 instructions)
+    const uint32_t ox = lx + 8u * (q & 1u), oy = ly + 8u * (q >> 1);
+    const uint32_t x = tg.px0 + ox, y = tg.py0 + oy;
+    const bool inside = ox < a.tile_size && oy < a.tile_size && x < a.image_width && y < a.image_height;
+    const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+    const size_t pix = inside ? ((size_t)tg.cam * a.image_height + y) * a.image_width + x : 0;
+    const int64_t vpix = (int64_t)pix * ga.s_vrc_pix + (int64_t)ch_off * ga.s_vrc_ch; // the same pixel in v_render_colors (its own strides)
+    const float T_final = inside ? 1.f - ga.render_alphas[pix] : 1.f;
+    float T = T_final, Bq = 0.f, vc[CR];
+    float bg_dot = 0.f;
+    if (CMODE != 2) {
 #pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-        const uint32_t q = q_first + i;
-        const uint32_t ox = lx + 8u * (q & 1u), oy = ly + 8u * (q >> 1);
-        const uint32_t x = tg.px0 + ox, y = tg.py0 + oy;
-        inside[i] = ox < a.tile_size && oy < a.tile_size && x < a.image_width && y < a.image_height;
-        px[i] = (float)x + 0.5f;
-        py[i] = (float)y + 0.5f;
-        const size_t pix = inside[i] ? ((size_t)tg.cam * a.image_height + y) * a.image_width + x : 0;
-        pixv[i] = pix * a.channels + ch_off;
-        vpix[i] = (int64_t)pix * ga.s_vrc_pix + (int64_t)ch_off * ga.s_vrc_ch;
-        const float T_final = inside[i] ? 1.f - ga.render_alphas[pix] : 1.f;
-        T[i] = T_final;
-        Bq[i] = 0.f;
-        float bg_dot = 0.f;
-        if (CMODE != 2) {
-#pragma unroll
-            for (int k = 0; k < CR; ++k) {
-                vc[i][k] = (inside[i] && (uint32_t)k < cnt) ? ga.v_render_colors[vpix[i] + k * ga.s_vrc_ch] : 0.f;
-                if (bg != nullptr && (uint32_t)k < cnt) bg_dot += bg[k] * vc[i][k];
-            }
-        } else {
-            vc[i][0] = 0.f;
-            if (bg != nullptr && inside[i])
-                for (uint32_t k = 0; k < cnt; ++k) bg_dot += bg[k] * ga.v_render_colors[vpix[i] + k * ga.s_vrc_ch];
+        for (int k = 0; k < CR; ++k) {
+            vc[k] = (inside && (uint32_t)k < cnt) ? ga.v_render_colors[vpix + k * ga.s_vrc_ch] : 0.f;
+            if (bg != nullptr && (uint32_t)k < cnt) bg_dot += bg[k] * vc[k];
         }
-        const float v_a = (inside[i] && use_v_alpha) ? ga.v_render_alphas[pix] : 0.f;
-        Tw[i] = T_final * (v_a - bg_dot);
-        bin_final[i] = inside[i] ? ga.last_ids[pix] : -1; // never matches
-        bin_max = max(bin_max, bin_final[i]);
+    } else {
+        vc[0] = 0.f;
+        if (bg != nullptr && inside)
+            for (uint32_t k = 0; k < cnt; ++k) bg_dot += bg[k] * ga.v_render_colors[vpix + k * ga.s_vrc_ch];
     }
-    bin_max = wave_max_i32(bin_max);
+    const float v_a = (inside && use_v_alpha) ? ga.v_render_alphas[pix] : 0.f;
+    const float Tw = T_final * (v_a - bg_dot);
+    const int32_t bin_final = inside ? ga.last_ids[pix] : -1; // never matches
+    const int32_t bin_max = wave_max_i32(max(-1, bin_final));
     if (bin_max < tg.range_start) return; // nothing was composited in this wave's pixels
     // nothing behind bin_max contributes: start there and walk back to front
     const int32_t first = min(tg.range_end - 1, bin_max);
@@ -918,56 +742,47 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_bwd_kernel(RasterArgs a, 
             float Cs[CR];
 #pragma unroll
             for (int k = 0; k < CR; ++k) Cs[k] = 0.f;
-            float facs[NQ];
-            bool any_valid = false;
+            const float dx = c0.x - px, dy = c0.y - py;
+            SplatSample sm;
+            const bool valid = splat_sample(dx, dy, c0.z, c0.w, c1.x, c1.y, sm, idx <= bin_final);
+            const float araw = sm.araw, alpha = sm.alpha;
+            const float ra = __builtin_amdgcn_rcpf(1.f - alpha);
+            const float Tn = T * ra;
+            const float facv = valid ? alpha * Tn : 0.f;
+            float D = 0.f;
+            if (CMODE == 2) {
+                if (valid)
+                    for (uint32_t k = 0; k < cnt; ++k) D += cp[k] * ga.v_render_colors[vpix + k * ga.s_vrc_ch];
+            } else {
 #pragma unroll
-            for (int i = 0; i < NQ; ++i) {
-                const float dx = c0.x - px[i], dy = c0.y - py[i];
-                SplatSample sm;
-                const bool valid = splat_sample(dx, dy, c0.z, c0.w, c1.x, c1.y, sm, idx <= bin_final[i]);
-                const float araw = sm.araw, alpha = sm.alpha;
-                any_valid |= valid;
-                const float ra = __builtin_amdgcn_rcpf(1.f - alpha);
-                const float Tn = T[i] * ra;
-                const float facv = valid ? alpha * Tn : 0.f;
-                float D = 0.f;
-                if (CMODE == 2) {
-                    if (valid)
-                        for (uint32_t k = 0; k < cnt; ++k) D += cp[k] * ga.v_render_colors[vpix[i] + k * ga.s_vrc_ch];
-                } else {
-#pragma unroll
-                    for (int k = 0; k < CR; ++k) {
-                        D += col[k] * vc[i][k];
-                        Cs[k] += facv * vc[i][k];
-                    }
-                }
-                facs[i] = facv;
-                const float v_alpha = D * Tn + (Tw[i] - Bq[i]) * ra;
-                // gradient gate: nothing for conic / xy / opacity when o * vis > ALPHA_MAX (`&`: see seg_sample)
-                const float v_sigma = (valid & (araw <= ALPHA_MAX)) ? -araw * v_alpha : 0.f;
-                Bq[i] += facv * D;
-                T[i] = valid ? Tn : T[i];
-                const float sdx = v_sigma * dx, sdy = v_sigma * dy;
-                S0 += v_sigma;
-                Sx += sdx;
-                Sy += sdy;
-                Sxx += sdx * dx;
-                Sxy += sdx * dy;
-                Syy += sdy * dy;
-                if (ABS) {
-                    Ax += fabsf(c3.x * sdx + c3.y * sdy);
-                    Ay += fabsf(c3.y * sdx + c3.z * sdy);
+                for (int k = 0; k < CR; ++k) {
+                    D += col[k] * vc[k];
+                    Cs[k] += facv * vc[k];
                 }
             }
-            if (!__any(any_valid)) continue;
+            const float v_alpha = D * Tn + (Tw - Bq) * ra;
+            // gradient gate: nothing for conic / xy / opacity when o * vis > ALPHA_MAX (`&`: see seg_sample)
+            const float v_sigma = (valid & (araw <= ALPHA_MAX)) ? -araw * v_alpha : 0.f;
+            Bq += facv * D;
+            T = valid ? Tn : T;
+            const float sdx = v_sigma * dx, sdy = v_sigma * dy;
+            S0 += v_sigma;
+            Sx += sdx;
+            Sy += sdy;
+            Sxx += sdx * dx;
+            Sxy += sdx * dy;
+            Syy += sdy * dy;
+            if (ABS) {
+                Ax += fabsf(c3.x * sdx + c3.y * sdy);
+                Ay += fabsf(c3.y * sdx + c3.z * sdy);
+            }
+            if (!__any(valid)) continue;
             float *vcol = ga.v_colors + (size_t)g * ga.s_color + ch_off;
             if (CMODE == 2) {
                 // any channel count: one reduction + atomic per channel
                 for (uint32_t k = 0; k < cnt; ++k) {
-                    float c = 0.f;
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i) c += facs[i] * (inside[i] ? ga.v_render_colors[vpix[i] + k * ga.s_vrc_ch] : 0.f);
-                    c = wave_reduce_sum_dpp(c);
+                    // (0.f +: the sum used to start from zero -- one fma, a -0 product enters the reduction as +0)
+                    const float c = wave_reduce_sum_dpp(0.f + facv * (inside ? ga.v_render_colors[vpix + k * ga.s_vrc_ch] : 0.f));
                     if (lane == GS_WAVE - 1) unsafeAtomicAdd(vcol + k, c); // (more than 4 channels: no deterministic mode, checked by the caller)
                 }
             } else {
@@ -1011,16 +826,16 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_bwd_kernel(RasterArgs a, 
 template <int CDIM>
 void launch_fwd(const RasterArgs &a, uint32_t cnt, uint32_t off, hipStream_t st) {
     dim3 grid(a.C * a.tile_width * a.tile_height * 4);
-    hipLaunchKernelGGL((raster_wave_fwd_kernel<1, CDIM, false, false>), grid, dim3(GS_WAVE), 0, st, a, cnt, off, (float *)nullptr, 0);
+    hipLaunchKernelGGL((raster_wave_fwd_kernel<CDIM>), grid, dim3(GS_WAVE), 0, st, a, cnt, off);
 }
 
 template <int CDIM, int CMODE>
 void launch_bwd(const RasterArgs &a, const RasterGradArgs &ga, uint32_t cnt, uint32_t off, int use_va, hipStream_t st) {
     dim3 grid(a.C * a.tile_width * a.tile_height * 4);
     if (ga.v_means2d_abs != nullptr)
-        hipLaunchKernelGGL((raster_wave_bwd_kernel<1, CDIM, CMODE, true>), grid, dim3(GS_WAVE), 0, st, a, ga, cnt, off, use_va);
+        hipLaunchKernelGGL((raster_wave_bwd_kernel<CDIM, CMODE, true>), grid, dim3(GS_WAVE), 0, st, a, ga, cnt, off, use_va);
     else
-        hipLaunchKernelGGL((raster_wave_bwd_kernel<1, CDIM, CMODE, false>), grid, dim3(GS_WAVE), 0, st, a, ga, cnt, off, use_va);
+        hipLaunchKernelGGL((raster_wave_bwd_kernel<CDIM, CMODE, false>), grid, dim3(GS_WAVE), 0, st, a, ga, cnt, off, use_va);
 }
 
 // ---------------------------------------------------------------------------

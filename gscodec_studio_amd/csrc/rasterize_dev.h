@@ -1,7 +1,8 @@
 // rasterize_dev.h -- device helpers shared by the compositing kernels of rasterize.hip (1..4 channels, generic route) and
 // rasterize_wide.hip (5..32 channels): the sample decision (splat_sample: exponent, alpha, accept -- its ONE definition, with
-// the thresholds ALPHA_MIN / ALPHA_MAX / T_MIN), splat fetch, exact rectangle culling, XCD remap, tile geometry, the segmented
-// backward's arguments.  The stages of the two segmented backwards themselves: rasterize_seg_dev.h.
+// the thresholds ALPHA_MIN / ALPHA_MAX / T_MIN), splat fetch, exact rectangle culling, XCD remap, tile geometry, the stages of
+// the forward kernels (pixel of a lane, masked tile, priority, record write, checkpoint cursor, list index, epilogue), the
+// segmented backward's arguments.  The stages of the two segmented backwards themselves: rasterize_seg_dev.h.
 #pragma once
 
 #include "gs_common.h"
@@ -223,17 +224,15 @@ GS_DEV TileGeom tile_geom(const RasterArgs &a, uint32_t slot) {
     return g;
 }
 
-// Pixel rectangle (centres) covered by this wave: the tile (NQ == 4) or one quadrant,
-// clipped to the tile size and the image.  Wave-uniform.
+// Pixel rectangle (centres) covered by the wave of quadrant q, clipped to the tile size and the image.  Wave-uniform.
 struct Rect {
     float x0, x1, y0, y1;
     bool empty;
 };
 
-template <int NQ>
-GS_DEV Rect wave_rect(const RasterArgs &a, const TileGeom &tg, uint32_t q_first) {
-    uint32_t ox0 = (NQ == 4) ? 0u : 8u * (q_first & 1u), oy0 = (NQ == 4) ? 0u : 8u * (q_first >> 1);
-    uint32_t ox1 = (NQ == 4) ? 16u : ox0 + 8u, oy1 = (NQ == 4) ? 16u : oy0 + 8u;
+GS_DEV Rect wave_rect(const RasterArgs &a, const TileGeom &tg, uint32_t q) {
+    uint32_t ox0 = 8u * (q & 1u), oy0 = 8u * (q >> 1);
+    uint32_t ox1 = ox0 + 8u, oy1 = oy0 + 8u;
     ox1 = min(ox1, a.tile_size);
     oy1 = min(oy1, a.tile_size);
     uint32_t X0 = tg.px0 + ox0, Y0 = tg.py0 + oy0;
@@ -245,6 +244,100 @@ GS_DEV Rect wave_rect(const RasterArgs &a, const TileGeom &tg, uint32_t q_first)
     r.x1 = (float)X1 - 0.5f;
     r.y1 = (float)Y1 - 0.5f;
     return r;
+}
+
+// ---------------------------------------------------------------------------
+// The stages of the forward kernels (raster_tile_fwd_kernel, raster_wave_fwd_kernel), each defined once.
+// ---------------------------------------------------------------------------
+
+// The pixel of lane (lx, ly) of the wave that composites quadrant q of the tile.
+struct LanePixel {
+    bool inside; // inside the tile (tile_size < 16) and the image
+    float px, py; // pixel centre
+    size_t pix;   // index into the [C, H, W] images
+};
+GS_DEV LanePixel lane_pixel(const RasterArgs &a, const TileGeom &tg, uint32_t q, uint32_t lx, uint32_t ly) {
+    const uint32_t ox = lx + 8u * (q & 1u), oy = ly + 8u * (q >> 1);
+    const uint32_t x = tg.px0 + ox, y = tg.py0 + oy;
+    LanePixel p;
+    p.inside = ox < a.tile_size && oy < a.tile_size && x < a.image_width && y < a.image_height;
+    p.px = (float)x + 0.5f;
+    p.py = (float)y + 0.5f;
+    p.pix = ((size_t)tg.cam * a.image_height + y) * a.image_width + x;
+    return p;
+}
+
+// A masked tile: the background (or zeros) in channels [ch_off, ch_off + cnt) of pixel `pix` of an image of `channels`
+// channels; bg points at the background of channel ch_off (or is null).  CDIM > 0: cnt <= CDIM, unrolled; CDIM == 0: any cnt.
+template <int CDIM>
+GS_DEV void store_masked_pixel(float *render_colors, size_t pix, uint32_t channels, uint32_t ch_off, uint32_t cnt, const float *bg) {
+    if constexpr (CDIM > 0) {
+#pragma unroll
+        for (int k = 0; k < CDIM; ++k)
+            if ((uint32_t)k < cnt) render_colors[pix * channels + ch_off + k] = bg ? bg[k] : 0.f;
+    } else {
+        for (uint32_t k = 0; k < cnt; ++k) render_colors[pix * channels + ch_off + k] = bg ? bg[k] : 0.f;
+    }
+}
+
+// Graded issue priority by list length: the longest lists bound the kernel, they must win arbitration on their SIMD.
+GS_DEV void raise_priority_for(int32_t n) {
+    if (n >= 4 * HEAVY_TILE) __builtin_amdgcn_s_setprio(3);
+    else if (n >= 2 * HEAVY_TILE) __builtin_amdgcn_s_setprio(2);
+    else if (n >= HEAVY_TILE) __builtin_amdgcn_s_setprio(1);
+}
+
+// The LDS record of one staged splat: R0 = (mx, my, a', b'), R1 = (c', log2 o, col0, col1) with the conic pre-scaled for
+// splat_sample, then (CDIM + 1) / 4 float4s of colours 2 .. CDIM - 1, zero-padded (none for CDIM <= 2; CDIM == 0: no colours
+// travel in the record, col is not read).
+template <int CDIM>
+GS_DEV void write_record(float4 *r, const SplatRaw &s, const float *col) {
+    auto c = [&](int k) { return k < CDIM ? col[k < CDIM ? k : 0] : 0.f; };
+    r[0] = make_float4(s.mx, s.my, -0.5f * LOG2E * s.ca, -LOG2E * s.cb);
+    r[1] = make_float4(-0.5f * LOG2E * s.cc, __log2f(s.opac), c(0), c(1));
+#pragma unroll
+    for (int j = 0; j < (CDIM + 1) / 4; ++j) r[2 + j] = make_float4(c(2 + 4 * j), c(3 + 4 * j), c(4 + 4 * j), c(5 + 4 * j));
+}
+
+// Index of the record that starts at float4 `slot4` of a buffer of REC-float4 records (REC == 3: multiply-shift, exact for
+// the multiples of 3 below 2^15 that occur).
+template <int REC>
+GS_DEV uint32_t record_index(uint32_t slot4) {
+    return REC == 3 ? (slot4 * 43691u) >> 17 : slot4 / (uint32_t)REC;
+}
+
+// Checkpoint cursor of a tile: the next list boundary b = k * seg the forward stores a checkpoint for (the state "before list
+// entry b"), for every boundary strictly inside (range_start, range_end).
+struct CkptCursor {
+    int32_t next_b, next_k;
+    GS_DEV void first(bool on, int32_t range_start, int32_t seg) { // on == false: never a boundary
+        next_b = on ? (range_start / seg + 1) * seg : 0x7fffffff;
+        next_k = on ? next_b / seg : 0;
+    }
+    GS_DEV void advance(int32_t seg) {
+        next_b += seg;
+        next_k += 1;
+    }
+    // store() the state before list entry next_b when the sub-batch that starts at sb_start is the one behind that boundary
+    template <class Store>
+    GS_DEV void before(int32_t sb_start, int32_t range_end, int32_t seg, Store &&store) {
+        if (sb_start == next_b && next_b < range_end) {
+            store();
+            advance(seg);
+        }
+    }
+};
+
+// A finished pixel: render_alphas and last_ids (the launch that `owner`s them) and channels [ch_off, ch_off + cnt), cnt <= CDIM,
+// of render_colors, the background (bg: at channel ch_off, or null) behind the final transmittance Tf.
+template <int CDIM>
+GS_DEV void store_pixel(const RasterArgs &a, size_t pix, uint32_t channels, uint32_t ch_off, uint32_t cnt, bool owner, float Tf,
+                        const float *out, int32_t last_id, const float *bg) {
+    if (owner) a.render_alphas[pix] = 1.f - Tf;
+#pragma unroll
+    for (int k = 0; k < CDIM; ++k)
+        if ((uint32_t)k < cnt) a.render_colors[pix * channels + ch_off + k] = bg ? out[k] + Tf * bg[k] : out[k];
+    if (owner) a.last_ids[pix] = last_id;
 }
 
 // the segmented backward's work list (built by seg_items_build_kernel inside gs_rasterize_fwd) and the forward's checkpoints

@@ -1,6 +1,8 @@
 """End-to-end GPU parity of rasterization() against the CPU oracle (the reference's
 tests/test_rasterization.py:17-89 compares rasterization() with its torch twin the same way),
 plus size-independent properties at BASELINE config-2 size."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -292,6 +294,66 @@ def test_solo_waves_match_cooperative_tiles():
             assert np.array_equal(rc1, rc0) and np.array_equal(ra1, ra0), thr
             for a, b, name in zip(g1, g0, ("means", "quats", "scales", "opacities", "colors")):
                 assert rel_l2(a, b) < 3e-4, (thr, name, rel_l2(a, b))  # (float atomics: the summation order varies run to run)
+
+
+@functools.lru_cache(maxsize=None)
+def _long_list_case(tile_size):
+    """Two 72 x 40 cameras over 900 enlarged garden splats (5 x 3 tiles of 16 with a half-width last column and a half-height
+    last row): every tile list is several cooperative batches long.  Projected and binned once per tile size, by the oracle."""
+    W, H, C = 72, 40, 2
+    fx = garden(900, scale_mult=16.0)
+    Ks = fx["Ks"][:C].copy()
+    Ks[:, 0, :] *= W / fx["width"]
+    Ks[:, 1, :] *= H / fx["height"]
+    radii, means2d, depths, conics, _ = O.projection_fwd(fx["means"], None, fx["quats"], fx["scales"], fx["viewmats"][:C], Ks, W, H)
+    tw, th = -(-W // tile_size), -(-H // tile_size)
+    _, ids, flat = O.isect_tiles(means2d, radii, depths, tile_size, tw, th)
+    offs = O.isect_offset_encode(ids, C, tw, th)
+    opac = np.broadcast_to(fx["opacities"][None], (C, 900)).copy()
+    masks = np.ones((C, th, tw), bool)
+    masks[0, 0, 1] = masks[0, th - 1, tw - 1] = masks[1, 1, 0] = False  # an interior, a clipped corner and an edge tile
+    return dict(means2d=means2d, conics=conics, opacities=opac, offs=offs, flat=flat, masks=masks, W=W, H=H, C=C)
+
+
+@pytest.mark.parametrize("channels,tile_size", [(3, 16), (9, 16), (16, 16), (3, 8)])
+def test_forward_stages_solo_cooperative_and_checkpoints_agree(channels, tile_size):
+    """The forward's stages are shared by the solo and the cooperative loop, the narrow (3) and the wide instances (9; 16 with
+    its single record buffer and second barrier), with and without checkpoints.  On lists of several cooperative batches with a
+    partial first sub-batch, a checkpoint at every 64-entry sub-batch (raster_seg = 64), masked tiles, clipped tiles and
+    backgrounds: the image and the alphas (outside the masked tiles, whose alphas are not written) are IDENTICAL between solo
+    and cooperative tiles and between a forward that writes checkpoints (a backward can follow) and one that does not
+    (torch.no_grad()); the gradients of the two loops agree to the float-atomic bound of
+    test_solo_waves_match_cooperative_tiles."""
+    from gscodec_studio_amd import rasterize_to_pixels
+    from util import tuned
+
+    c = _long_list_case(tile_size)
+    lens = np.diff(np.concatenate([c["offs"].reshape(-1), [c["flat"].size]]))
+    assert np.median(lens[lens > 0]) > 256 and lens.max() > 512, (np.median(lens[lens > 0]), lens.max())
+    rs = np.random.RandomState(channels)
+    colors, bg = rs.rand(c["C"], 900, channels).astype(np.float32), T(rs.rand(c["C"], channels).astype(np.float32))
+    offs, flat, masks = T(c["offs"]), T(c["flat"]), T(c["masks"])
+    names = ("means2d", "conics", "colors", "opacities")
+    kept = np.repeat(np.repeat(c["masks"], tile_size, 1), tile_size, 2)[:, :c["H"], :c["W"]]  # a masked tile's alphas are unwritten
+    kept_t = T(kept)
+
+    def run(solo_min, grad):
+        ps = [T(a, grad) for a in (c["means2d"], c["conics"], colors, c["opacities"])]
+        with tuned({"raster_seg": 64, "raster_solo_min": solo_min}), torch.set_grad_enabled(grad):
+            rc, ra = rasterize_to_pixels(*ps, c["W"], c["H"], tile_size, offs, flat, backgrounds=bg, masks=masks)
+            if grad:
+                w = torch.linspace(0.5, 1.5, rc.numel(), device="cuda").reshape(rc.shape)
+                ((rc * w).sum() + 0.3 * ra[kept_t].sum()).backward()
+        return N(rc), N(ra)[kept], [N(p.grad) for p in ps] if grad else None
+
+    rc0, ra0, g0 = run(0, True)  # every tile cooperative, checkpoints written
+    assert np.isfinite(rc0).all() and float(ra0.max()) > 0.5
+    for solo_min, grad in ((1, True), (0, False), (1, False)):  # every tile solo / no checkpoints / both
+        rc1, ra1, g1 = run(solo_min, grad)
+        assert np.array_equal(rc1, rc0) and np.array_equal(ra1, ra0), (solo_min, grad)  # (the alphas: where they are written)
+        if grad:
+            for a, b, name in zip(g1, g0, names):
+                assert rel_l2(a, b) < 3e-4, (name, rel_l2(a, b))  # (float atomics: the summation order varies run to run)
 
 
 def test_full_size_linearity_determinism_and_adjoint():

@@ -18,7 +18,11 @@ def kernels(path):
     for ln in open(path):
         m = re.match(r'^[0-9a-f]+ <(.+)>:$', ln.strip())
         if m:
-            cur = re.sub(r'8ZeroFilljj$', '8ZeroFill', m.group(1)); out[cur] = []
+            cur = re.sub(r'8ZeroFilljj$', '8ZeroFill', m.group(1))
+            # the generic wave kernels before they lost their pixels-per-lane / colour-in-LDS / checkpoint axes
+            cur = re.sub(r'raster_wave_fwd_kernelILi1E(Li\d+E)Lb0ELb0EEEv10RasterArgsjjPfi', r'raster_wave_fwd_kernelI\1EEv10RasterArgsjj', cur)
+            cur = re.sub(r'raster_wave_bwd_kernelILi1E(Li\d+ELi\d+ELb[01]E)', r'raster_wave_bwd_kernelI\1', cur)
+            out[cur] = []
         elif cur is not None and ln.strip():
             out[cur].append(re.sub(r'<[^>]*>', '<L>', ln.strip()))
     return out
