@@ -79,6 +79,9 @@ def test_projection_vs_golden_and_oracle(ops, camera_model, calc_compensations):
 
 
 def test_projection_covars_path_and_radius_clip(ops):
+    """Clip planes, radius_clip and the covars route's agreement with the quats + scales route.  The 2e-3 on v_covars below (fp32 oracle,
+    pinhole, a cotangent on the conics alone) is a smoke check: the bar for v_covars -- float64, 1e-4, three camera models, all four
+    cotangents, pose gradients, the row and packed forms -- is the covars cases of tests/test_gpu_projection_routes.py."""
     fx = garden(1500, scale_mult=3.0)
     means, quats, scales = T(fx["means"]), T(fx["quats"]), T(fx["scales"])
     viewmats, Ks = T(fx["viewmats"]), T(fx["Ks"])
