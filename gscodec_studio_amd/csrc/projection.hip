@@ -81,13 +81,10 @@ __global__ void __launch_bounds__(GS_BLOCK) projection_fwd_kernel(
     radii[idx] = s.radius;
     if (s.radius <= 0) return;
     if (ROWS) {
-        float *row = means2d + GS_ROW_FLOATS * idx;
         depths[idx] = s.depth;
         float op = rx.opacities != nullptr ? rx.opacities[n] : 0.f;
         if (rx.antialiased) op *= s.comp;
-        reinterpret_cast<float4 *>(row)[0] = make_float4(s.mx, s.my, s.ca, s.cb);
-        if (rx.colors != nullptr || rx.sh_coeffs != nullptr) {
-            float c0, c1, c2;
+        store_splat_row(means2d + GS_ROW_FLOATS * idx, s, op, rx.colors != nullptr || rx.sh_coeffs != nullptr, [&](float &c0, float &c1, float &c2) {
             if (SHMODE >= 0) {
                 // view direction = mean - camera centre (the centre from the view matrix, wave-uniform), colour =
                 // clamp_min(SH + 0.5, 0): gsplat/rendering.py:368-392 of the reference
@@ -109,13 +106,7 @@ __global__ void __launch_bounds__(GS_BLOCK) projection_fwd_kernel(
                 const float *cp = rx.colors + 3 * (size_t)n;
                 c0 = cp[0]; c1 = cp[1]; c2 = cp[2];
             }
-            reinterpret_cast<float4 *>(row)[1] = make_float4(s.cc, op, c0, c1);
-            reinterpret_cast<float4 *>(row)[2] = make_float4(c2, s.depth, __int_as_float(s.radius), s.comp);
-        } else { // the colour columns belong to the SH kernel (gs_sh_view_fwd writes them into the same rows)
-            reinterpret_cast<float2 *>(row)[2] = make_float2(s.cc, op);
-            row[GS_ROW_DEPTH] = s.depth;
-            reinterpret_cast<float2 *>(row)[5] = make_float2(__int_as_float(s.radius), s.comp);
-        }
+        });
         return;
     }
     means2d[2 * idx] = s.mx;
@@ -131,62 +122,42 @@ __global__ void __launch_bounds__(GS_BLOCK) projection_fwd_kernel(
 // backward
 // ---------------------------------------------------------------------------
 
-// write the per-gaussian gradient rows
-GS_DEV void store_gaussian_grads(
-    const ProjGrad &g, uint32_t n, bool any,
-    const float *__restrict__ covars, const float *__restrict__ quats,
-    const float *__restrict__ scales,
-    float *__restrict__ v_means, float *__restrict__ v_covars,
-    float *__restrict__ v_quats, float *__restrict__ v_scales, const float *__restrict__ v_means_add) {
-    if (v_means != nullptr) {
-        // v_means_add: a contribution to d/d means that reached the caller by another path (the view directions of the SH
-        // colours); summed here instead of by a separate elementwise pass over [N,3]
-        float ax = 0.f, ay = 0.f, az = 0.f;
-        if (v_means_add != nullptr) {
-            ax = v_means_add[3 * (size_t)n]; ay = v_means_add[3 * (size_t)n + 1]; az = v_means_add[3 * (size_t)n + 2];
-        }
-        v_means[3 * (size_t)n] = g.v_px + ax;
-        v_means[3 * (size_t)n + 1] = g.v_py + ay;
-        v_means[3 * (size_t)n + 2] = g.v_pz + az;
-    }
-    if (covars != nullptr) {
-        if (v_covars != nullptr) {
-            float *o = v_covars + 6 * (size_t)n;
-            // off-diagonals carry both (i,j) and (j,i): fully_fused_projection_bwd.cu:217-222
-            o[0] = g.v_S.xx; o[1] = 2.f * g.v_S.xy; o[2] = 2.f * g.v_S.xz;
-            o[3] = g.v_S.yy; o[4] = 2.f * g.v_S.yz; o[5] = g.v_S.zz;
-        }
-    } else {
-        float vq[4] = {0.f, 0.f, 0.f, 0.f}, vs[3] = {0.f, 0.f, 0.f};
-        if (any) {
-            const float *q = quats + 4 * (size_t)n;
-            const float *s = scales + 3 * (size_t)n;
-            Mat3 R = quat_to_rotmat(q[0], q[1], q[2], q[3]);
-            covar_vjp_quat_scale(q[0], q[1], q[2], q[3], s[0], s[1], s[2], R, sym3_to_mat3(g.v_S), vq, vs);
-        }
-        if (v_quats != nullptr) {
-            float *o = v_quats + 4 * (size_t)n;
-            o[0] = vq[0]; o[1] = vq[1]; o[2] = vq[2]; o[3] = vq[3];
-        }
-        if (v_scales != nullptr) {
-            float *o = v_scales + 3 * (size_t)n;
-            o[0] = vs[0]; o[1] = vs[1]; o[2] = vs[2];
-        }
-    }
-}
+// The backward's per-(camera, gaussian) inputs come from one of two sources, a template policy of the kernel: each reads its pair
+// and runs the projection's VJP on it, keeps what else it sums over the cameras in its Sums, and stores that per gaussian.
 
-// Row form of the backward (rg.rows != NULL): conics / compensations come from the splat rows, the gradients of mean2d /
-// conic / opacity / colour from the compositing backward's gradient rows (same columns); this kernel then also sums the
-// opacity and colour gradients over the cameras (what autograd's `opacities.repeat(C, 1)` / `colors.expand` backward and
-// the antialias multiply did in passes of their own).
-struct RowGrads {
-    const float *rows;      // [C,N,16] or NULL (array form)
+// Array form: conics / compensations and the gradients of means2d / conics / compensations as arrays over [C,N] (the gradient
+// arrays with a row stride of their own: views into wider rows).  Every gaussian's rows are written.
+struct ArrayPairs {
+    const float *conics, *compensations;
+    const float *v_means2d, *v_depths, *v_conics, *v_compensations;
+    uint32_t s_m2, s_cn;
+    struct Sums {};
+    GS_DEV bool prefilled() const { return false; }
+    template <bool NEED_VIEW>
+    GS_DEV void pair_vjp(const Camera &cam, float px, float py, float pz, const Sym3 &S, int W, int H, float eps2d, int camera_model,
+                         uint32_t n, size_t idx, Sums &, ProjGrad &g) const {
+        bool has_comp = v_compensations != nullptr;
+        project_one_vjp<NEED_VIEW>(
+            cam, px, py, pz, S, W, H, eps2d, camera_model,
+            conics[3 * idx], conics[3 * idx + 1], conics[3 * idx + 2],
+            has_comp ? compensations[idx] : 0.f, has_comp ? v_compensations[idx] : 0.f, has_comp,
+            v_means2d[s_m2 * idx], v_means2d[s_m2 * idx + 1], v_depths != nullptr ? v_depths[idx] : 0.f,
+            v_conics[s_cn * idx], v_conics[s_cn * idx + 1], v_conics[s_cn * idx + 2], g);
+    }
+    GS_DEV void store_sums(uint32_t, const Sums &) const {}
+};
+
+// Row form: conics / compensations come from the splat rows, the gradients of mean2d / conic / opacity / colour from the
+// compositing backward's gradient rows (same columns); the kernel then also sums the opacity and colour gradients over the cameras.
+struct RowPairs {
+    const float *rows;      // [C,N,16]
     const float *grad_rows; // [C,N,16]
+    const float *v_depths;  // [C,N] or NULL
     const float *opacities; // [N] (antialiased only)
     float *v_opacities;     // [N] or NULL
     float *v_colors;        // [N,3] or NULL
     int antialiased;
-    int prefilled;          // every per-gaussian output holds zeros already: gaussians no camera sees are not stored
+    int is_prefilled;       // every per-gaussian output holds zeros already: gaussians no camera sees are not stored
     // SH colours evaluated by the forward (gs_projection_rows_fwd with sh_coeffs): their backward runs in this pass too
     const float *sh_coeffs; // [N,K,3], or the DC band [N,1,3] with sh_rest
     const float *sh_rest;   // [N,K-1,3] or NULL
@@ -197,39 +168,51 @@ struct RowGrads {
     float sh_mask_temp;
     int sh_mask_binary;
     float *v_sh_mask_logits;     // [N] gradient of the logits (every entry written), or NULL
+    typedef RowSums Sums;
+    GS_DEV bool prefilled() const { return is_prefilled != 0; }
+    template <bool NEED_VIEW>
+    GS_DEV void pair_vjp(const Camera &cam, float px, float py, float pz, const Sym3 &S, int W, int H, float eps2d, int camera_model,
+                         uint32_t n, size_t idx, Sums &sum, ProjGrad &g) const {
+        row_pair_vjp<NEED_VIEW>(cam, px, py, pz, S, W, H, eps2d, camera_model, rows, grad_rows, v_depths, idx, antialiased != 0,
+                                antialiased ? opacities[n] : 0.f, v_colors != nullptr, sum, g);
+    }
+    GS_DEV void store_sums(uint32_t n, const Sums &sum) const {
+        if (v_opacities != nullptr) v_opacities[n] = sum.v_op;
+        if (v_colors != nullptr) {
+            v_colors[3 * (size_t)n] = sum.v_c0;
+            v_colors[3 * (size_t)n + 1] = sum.v_c1;
+            v_colors[3 * (size_t)n + 2] = sum.v_c2;
+        }
+    }
 };
 
 // SHDEG >= 0 (row form, shared coefficients, fixed poses): the SH backward of the colours the forward evaluated runs FIRST in
 // the same lane (sh_bwd_lane.h: v_sh rows out, d/d view direction kept in three registers), then the projection chain --
 // one pass over radii / means / the two row buffers instead of two, and no [N,3] round trip for the direction gradient
 // (sh_bwd_kernel 40.4 us + projection_bwd_kernel 20.4 us -> 52.3 us at BASELINE config 2).
-template <bool NEED_VIEW, int SHDEG = -1>
+template <bool NEED_VIEW, int SHDEG, class Pairs>
 __global__ void __launch_bounds__(GS_BLOCK) projection_bwd_kernel(
     uint32_t C, uint32_t N,
     const float *__restrict__ means, const float *__restrict__ covars,
     const float *__restrict__ quats, const float *__restrict__ scales,
     const float *__restrict__ viewmats, const float *__restrict__ Ks,
     int W, int H, float eps2d, int camera_model,
-    const int32_t *__restrict__ radii, const float *__restrict__ conics,
-    const float *__restrict__ compensations,
-    const float *__restrict__ v_means2d, const float *__restrict__ v_depths,
-    const float *__restrict__ v_conics, const float *__restrict__ v_compensations,
+    const int32_t *__restrict__ radii, Pairs src,
     float *__restrict__ v_means, float *__restrict__ v_covars, float *__restrict__ v_quats,
-    float *__restrict__ v_scales, float *__restrict__ v_viewmats, uint32_t s_m2, uint32_t s_cn,
-    const float *__restrict__ v_means_add, RowGrads rg) {
+    float *__restrict__ v_scales, float *__restrict__ v_viewmats, const float *__restrict__ v_means_add) {
     __shared__ float s_view[GS_BLOCK / GS_WAVE][12];
-    float v_op = 0.f, v_c0 = 0.f, v_c1 = 0.f, v_c2 = 0.f;
+    typename Pairs::Sums sums = {};
     uint32_t n = blockIdx.x * GS_BLOCK + threadIdx.x;
     bool in_range = n < N;
     float shx = 0.f, shy = 0.f, shz = 0.f; // d/d means through the SH view directions
-    if (SHDEG >= 0) {
-        const ShView view = {means, viewmats, radii, 1, 1, nullptr, nullptr, nullptr, 0u, nullptr, rg.sh_rest, rg.v_sh_rest,
-                             (uint32_t)GS_ROW_FLOATS, rg.prefilled, rg.sh_mask_logits, rg.sh_mask_temp, rg.sh_mask_binary,
-                             rg.v_sh_mask_logits};
+    if constexpr (SHDEG >= 0) {
+        const ShView view = {means, viewmats, radii, 1, 1, nullptr, nullptr, nullptr, 0u, nullptr, src.sh_rest, src.v_sh_rest,
+                             (uint32_t)GS_ROW_FLOATS, src.is_prefilled, src.sh_mask_logits, src.sh_mask_temp, src.sh_mask_binary,
+                             src.v_sh_mask_logits};
         bool any_sh;
-        sh_bwd_lane<(SHDEG >= 0 ? SHDEG : 0), true, true>(C, N, rg.sh_K, n, in_range, nullptr, rg.sh_coeffs, nullptr, rg.grad_rows + GS_ROW_COLOR,
-                                                          rg.v_sh, nullptr, view, rg.rows + GS_ROW_COLOR, (uint32_t)GS_ROW_FLOATS,
-                                                          v_means != nullptr, shx, shy, shz, any_sh);
+        sh_bwd_lane<SHDEG, true, true>(C, N, src.sh_K, n, in_range, nullptr, src.sh_coeffs, nullptr, src.grad_rows + GS_ROW_COLOR,
+                                       src.v_sh, nullptr, view, src.rows + GS_ROW_COLOR, (uint32_t)GS_ROW_FLOATS,
+                                       v_means != nullptr, shx, shy, shz, any_sh);
     }
     float px = 0.f, py = 0.f, pz = 0.f;
     Sym3 S = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -252,41 +235,13 @@ __global__ void __launch_bounds__(GS_BLOCK) projection_bwd_kernel(
                 loaded = true;
             }
             Camera cam = load_camera(viewmats, Ks, c);
-            if (rg.rows != nullptr) {
-                const float4 *r = reinterpret_cast<const float4 *>(rg.rows + GS_ROW_FLOATS * idx);
-                const float4 *gr = reinterpret_cast<const float4 *>(rg.grad_rows + GS_ROW_FLOATS * idx);
-                const float4 r0 = r[0], g0 = gr[0], g1 = gr[1];
-                const float cc = reinterpret_cast<const float *>(r)[GS_ROW_CONIC + 2];
-                const float comp = rg.antialiased ? reinterpret_cast<const float *>(r)[GS_ROW_COMPENSATION] : 1.f;
-                const float v_opac_cn = g1.y;
-                const float v_comp = rg.antialiased ? v_opac_cn * rg.opacities[n] : 0.f;
-                v_op += v_opac_cn * comp;
-                v_c0 += g1.z;
-                v_c1 += g1.w;
-                if (rg.v_colors != nullptr) v_c2 += reinterpret_cast<const float *>(gr)[GS_ROW_COLOR + 2];
-                project_one_vjp<NEED_VIEW>(cam, px, py, pz, S, W, H, eps2d, camera_model, r0.z, r0.w, cc, comp, v_comp,
-                                           rg.antialiased != 0, g0.x, g0.y, v_depths != nullptr ? v_depths[idx] : 0.f,
-                                           g0.z, g0.w, g1.x, g);
-            } else {
-            bool has_comp = v_compensations != nullptr;
-            project_one_vjp<NEED_VIEW>(
-                cam, px, py, pz, S, W, H, eps2d, camera_model,
-                conics[3 * idx], conics[3 * idx + 1], conics[3 * idx + 2],
-                has_comp ? compensations[idx] : 0.f, has_comp ? v_compensations[idx] : 0.f, has_comp,
-                v_means2d[s_m2 * idx], v_means2d[s_m2 * idx + 1], v_depths != nullptr ? v_depths[idx] : 0.f,
-                v_conics[s_cn * idx], v_conics[s_cn * idx + 1], v_conics[s_cn * idx + 2], g);
-            }
+            src.template pair_vjp<NEED_VIEW>(cam, px, py, pz, S, W, H, eps2d, camera_model, n, idx, sums, g);
             any = true;
         }
         if (NEED_VIEW) {
             // block reduce the 12 viewmat entries for camera c, one atomic set per block
             float vals[12];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) vals[4 * i + j] = g.v_W.m[i][j];
-                vals[4 * i + 3] = g.v_t[i];
-            }
+            view_grad_vals(g, vals);
             uint32_t wave = threadIdx.x / GS_WAVE, lane = threadIdx.x % GS_WAVE;
 #pragma unroll
             for (int k = 0; k < 12; ++k) {
@@ -303,15 +258,19 @@ __global__ void __launch_bounds__(GS_BLOCK) projection_bwd_kernel(
             __syncthreads();
         }
     }
-    if (in_range && (any || !rg.prefilled)) {
+    if (in_range && (any || !src.prefilled())) {
         if (SHDEG >= 0) { g.v_px += shx; g.v_py += shy; g.v_pz += shz; }
-        store_gaussian_grads(g, n, any, covars, quats, scales, v_means, v_covars, v_quats, v_scales, v_means_add);
-        if (rg.v_opacities != nullptr) rg.v_opacities[n] = v_op;
-        if (rg.v_colors != nullptr) {
-            rg.v_colors[3 * (size_t)n] = v_c0;
-            rg.v_colors[3 * (size_t)n + 1] = v_c1;
-            rg.v_colors[3 * (size_t)n + 2] = v_c2;
+        if (v_means != nullptr) {
+            // v_means_add: a contribution to d/d means that reached the caller by another path (the view directions of the SH
+            // colours); summed here instead of by a separate elementwise pass over [N,3]
+            float ax = 0.f, ay = 0.f, az = 0.f;
+            if (v_means_add != nullptr) {
+                ax = v_means_add[3 * (size_t)n]; ay = v_means_add[3 * (size_t)n + 1]; az = v_means_add[3 * (size_t)n + 2];
+            }
+            g.v_px += ax; g.v_py += ay; g.v_pz += az;
         }
+        store_gaussian_grads(g, n, n, any, covars, quats, scales, v_means, v_covars, v_quats, v_scales, PutStore());
+        src.store_sums(n, sums);
     }
 }
 
@@ -412,74 +371,14 @@ __global__ void __launch_bounds__(GS_BLOCK) projection_packed_bwd_kernel(
         v_means2d[2 * (size_t)idx], v_means2d[2 * (size_t)idx + 1], v_depths != nullptr ? v_depths[idx] : 0.f,
         v_conics[3 * (size_t)idx], v_conics[3 * (size_t)idx + 1], v_conics[3 * (size_t)idx + 2], g);
 
-    float vq[4] = {0.f, 0.f, 0.f, 0.f}, vs[3] = {0.f, 0.f, 0.f};
-    if (covars == nullptr) {
-        const float *q = quats + 4 * (size_t)n;
-        const float *s = scales + 3 * (size_t)n;
-        Mat3 R = quat_to_rotmat(q[0], q[1], q[2], q[3]);
-        covar_vjp_quat_scale(q[0], q[1], q[2], q[3], s[0], s[1], s[2], R, sym3_to_mat3(g.v_S), vq, vs);
-    }
-    if (sparse_grad) {
-        size_t o = idx;
-        if (v_means != nullptr) {
-            v_means[3 * o] = g.v_px; v_means[3 * o + 1] = g.v_py; v_means[3 * o + 2] = g.v_pz;
-        }
-        if (covars != nullptr) {
-            if (v_covars != nullptr) {
-                float *d = v_covars + 6 * o;
-                d[0] = g.v_S.xx; d[1] = 2.f * g.v_S.xy; d[2] = 2.f * g.v_S.xz;
-                d[3] = g.v_S.yy; d[4] = 2.f * g.v_S.yz; d[5] = g.v_S.zz;
-            }
-        } else {
-            if (v_quats != nullptr) {
-                float *d = v_quats + 4 * o;
-                d[0] = vq[0]; d[1] = vq[1]; d[2] = vq[2]; d[3] = vq[3];
-            }
-            if (v_scales != nullptr) {
-                float *d = v_scales + 3 * o;
-                d[0] = vs[0]; d[1] = vs[1]; d[2] = vs[2];
-            }
-        }
-    } else {
-        // dense: several cameras may hit the same gaussian row -> float atomics; with ONE camera every gaussian appears at
-        // most once and the (zero-filled) row is simply written
-        size_t o = n;
-        const bool one = C == 1u;
-        auto put = [&](float *dst, float v) {
-            if (one) *dst = v;
-            else atomicAdd(dst, v);
-        };
-        if (v_means != nullptr) {
-            put(v_means + 3 * o, g.v_px);
-            put(v_means + 3 * o + 1, g.v_py);
-            put(v_means + 3 * o + 2, g.v_pz);
-        }
-        if (covars != nullptr) {
-            if (v_covars != nullptr) {
-                float *d = v_covars + 6 * o;
-                put(d, g.v_S.xx); put(d + 1, 2.f * g.v_S.xy); put(d + 2, 2.f * g.v_S.xz);
-                put(d + 3, g.v_S.yy); put(d + 4, 2.f * g.v_S.yz); put(d + 5, g.v_S.zz);
-            }
-        } else {
-            if (v_quats != nullptr) {
-                float *d = v_quats + 4 * o;
-                put(d, vq[0]); put(d + 1, vq[1]); put(d + 2, vq[2]); put(d + 3, vq[3]);
-            }
-            if (v_scales != nullptr) {
-                float *d = v_scales + 3 * o;
-                put(d, vs[0]); put(d + 1, vs[1]); put(d + 2, vs[2]);
-            }
-        }
-    }
+    // sparse: the COO row is this lane's own.  Dense: several cameras may hit the same gaussian row -> float atomics; with ONE
+    // camera every gaussian appears at most once and the (zero-filled) row is simply written
+    const PutStoreOrAdd put = {sparse_grad || C == 1u};
+    store_gaussian_grads(g, n, sparse_grad ? (size_t)idx : (size_t)n, true, covars, quats, scales, v_means, v_covars, v_quats, v_scales, put);
     if (NEED_VIEW) {
         // rows are sorted by camera, so most waves are camera-uniform: reduce when they are
         float vals[12];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) vals[4 * i + j] = g.v_W.m[i][j];
-            vals[4 * i + 3] = g.v_t[i];
-        }
+        view_grad_vals(g, vals);
         uint32_t c0 = __builtin_amdgcn_readfirstlane(c);
         bool uniform = __all(c == c0) && (__popcll(__ballot(1)) == GS_WAVE);
         if (uniform) {
@@ -507,10 +406,7 @@ extern "C" int32_t gs_projection_fwd(
     int32_t camera_model, int32_t *radii, float *means2d, float *depths, float *conics,
     float *compensations, gs_stream_t stream) {
     if (C == 0 || N == 0) return 0;
-    GS_CHECK_ARG(means && viewmats && Ks && radii && means2d && depths && conics, "null pointer");
-    GS_CHECK_ARG((covars != nullptr) != (quats != nullptr && scales != nullptr),
-                 "exactly one of covars / (quats, scales) must be given");
-    GS_CHECK_ARG(camera_model >= 0 && camera_model <= 2, "bad camera_model");
+    GS_CHECK_GEOMETRY(means && viewmats && Ks && radii && means2d && depths && conics, covars, quats, scales, camera_model);
     dim3 grid(gs_div_up(N, GS_BLOCK), C);
     const RowExtras none = {nullptr, nullptr, 0, nullptr, nullptr, 0u, 0u, 0};
     hipLaunchKernelGGL((projection_fwd_kernel<false, -1>), grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N, means,
@@ -531,11 +427,8 @@ extern "C" int32_t gs_projection_rows_fwd(
     uint32_t tile_size, uint32_t tile_width, uint32_t tile_height, int32_t *tiles_per_gauss, int32_t *block_sums,
     int32_t *radii, float *depths, float *rows, gs_stream_t stream) {
     if (C == 0 || N == 0) return 0;
-    GS_CHECK_ARG(means && viewmats && Ks && radii && depths && rows, "null pointer");
+    GS_CHECK_GEOMETRY(means && viewmats && Ks && radii && depths && rows, covars, quats, scales, camera_model);
     GS_CHECK_ARG((uintptr_t)rows % 64 == 0, "the row buffer must be 64-byte aligned");
-    GS_CHECK_ARG((covars != nullptr) != (quats != nullptr && scales != nullptr),
-                 "exactly one of covars / (quats, scales) must be given");
-    GS_CHECK_ARG(camera_model >= 0 && camera_model <= 2, "bad camera_model");
     GS_CHECK_ARG(!antialiased || opacities != nullptr, "antialiased needs the opacities");
     GS_CHECK_ARG(sh_coeffs == nullptr || colors == nullptr, "colors and sh_coeffs exclude each other");
     GS_CHECK_ARG(sh_coeffs == nullptr || (sh_degree <= 4 && (sh_degree + 1) * (sh_degree + 1) <= sh_K), "bad SH degree / K");
@@ -575,17 +468,14 @@ extern "C" int32_t gs_projection_rows_bwd(
     float *v_sh_coeffs, float *v_sh_coeffs_rest, const float *sh_mask_logits, float sh_mask_temperature, int32_t sh_mask_binary,
     float *v_sh_mask_logits, int32_t outputs_prefilled, gs_stream_t stream) {
     if (N == 0) return 0;
-    GS_CHECK_ARG(means && viewmats && Ks && radii && rows && grad_rows, "null pointer");
+    GS_CHECK_GEOMETRY(means && viewmats && Ks && radii && rows && grad_rows, covars, quats, scales, camera_model);
     GS_CHECK_ARG((uintptr_t)rows % 16 == 0 && (uintptr_t)grad_rows % 16 == 0, "row buffers must be 16-byte aligned");
-    GS_CHECK_ARG((covars != nullptr) != (quats != nullptr && scales != nullptr),
-                 "exactly one of covars / (quats, scales) must be given");
     GS_CHECK_ARG(!antialiased || opacities != nullptr, "antialiased needs the opacities");
     dim3 grid(gs_div_up(N, GS_BLOCK));
-    RowGrads rg = {rows, grad_rows, opacities, v_opacities, v_colors, antialiased, outputs_prefilled != 0, nullptr, nullptr, 0u, nullptr, nullptr,
-                   nullptr, 1.f, 0, nullptr};
+    RowPairs rg = {rows, grad_rows, v_depths, opacities, v_opacities, v_colors, antialiased, outputs_prefilled != 0, nullptr, nullptr, 0u, nullptr,
+                   nullptr, nullptr, 1.f, 0, nullptr};
     GS_CHECK_ARG(sh_mask_logits == nullptr || (sh_coeffs != nullptr && sh_coeffs_rest != nullptr), "the shN mask needs the fused SH backward with split rows");
     GS_CHECK_ARG(v_sh_mask_logits == nullptr || (sh_mask_logits != nullptr && !sh_mask_binary), "v_sh_mask_logits needs the (training-mode) mask");
-    const float *nul = nullptr;
     if (sh_coeffs != nullptr) {
         // the SH backward in the same pass: the vectorised row form only (what gs_sh_view_bwd stages through LDS), fixed poses
         GS_CHECK_ARG(v_viewmats == nullptr && v_colors == nullptr, "fused SH backward: no camera-pose / per-gaussian colour gradients");
@@ -599,22 +489,16 @@ extern "C" int32_t gs_projection_rows_bwd(
         rg.v_sh_mask_logits = v_sh_mask_logits;
 #define GS_ROWS_BWD_SH(D)                                                                                                        \
     case D:                                                                                                                      \
-        hipLaunchKernelGGL((projection_bwd_kernel<false, D>), grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N, means, covars,  \
-                           quats, scales, viewmats, Ks, image_width, image_height, eps2d, camera_model, radii, nul, nul, nul,     \
-                           v_depths, nul, nul, v_means, v_covars, v_quats, v_scales, v_viewmats, 16u, 16u, v_means_add, rg);      \
+        hipLaunchKernelGGL((projection_bwd_kernel<false, D, RowPairs>), grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N, means, \
+                           covars, quats, scales, viewmats, Ks, image_width, image_height, eps2d, camera_model, radii, rg,       \
+                           v_means, v_covars, v_quats, v_scales, v_viewmats, v_means_add);                                       \
         break;
         switch (sh_degree) { GS_ROWS_BWD_SH(0) GS_ROWS_BWD_SH(1) GS_ROWS_BWD_SH(2) GS_ROWS_BWD_SH(3) GS_ROWS_BWD_SH(4) }
 #undef GS_ROWS_BWD_SH
-    } else if (v_viewmats != nullptr) {
-        hipLaunchKernelGGL(projection_bwd_kernel<true>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N,
-                           means, covars, quats, scales, viewmats, Ks, image_width, image_height, eps2d,
-                           camera_model, radii, nul, nul, nul, v_depths, nul, nul, v_means, v_covars, v_quats, v_scales,
-                           v_viewmats, 16u, 16u, v_means_add, rg);
     } else {
-        hipLaunchKernelGGL(projection_bwd_kernel<false>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N,
-                           means, covars, quats, scales, viewmats, Ks, image_width, image_height, eps2d,
-                           camera_model, radii, nul, nul, nul, v_depths, nul, nul, v_means, v_covars, v_quats, v_scales,
-                           v_viewmats, 16u, 16u, v_means_add, rg);
+        launch_flagged(v_viewmats != nullptr, projection_bwd_kernel<true, -1, RowPairs>, projection_bwd_kernel<false, -1, RowPairs>, grid, stream,
+                       C, N, means, covars, quats, scales, viewmats, Ks, image_width, image_height, eps2d, camera_model, radii, rg, v_means,
+                       v_covars, v_quats, v_scales, v_viewmats, v_means_add);
     }
     GS_CHECK_LAUNCH();
     return 0;
@@ -629,28 +513,15 @@ extern "C" int32_t gs_projection_bwd(
     float *v_covars, float *v_quats, float *v_scales, float *v_viewmats, uint32_t v_means2d_stride,
     uint32_t v_conics_stride, const float *v_means_add, gs_stream_t stream) {
     if (N == 0) return 0;
-    GS_CHECK_ARG(means && viewmats && Ks && radii && conics && v_means2d && v_conics,
-                 "null pointer");
+    GS_CHECK_GEOMETRY(means && viewmats && Ks && radii && conics && v_means2d && v_conics, covars, quats, scales, camera_model);
     GS_CHECK_ARG(v_means2d_stride >= 2 && v_conics_stride >= 3, "bad gradient row strides");
-    GS_CHECK_ARG((covars != nullptr) != (quats != nullptr && scales != nullptr),
-                 "exactly one of covars / (quats, scales) must be given");
     GS_CHECK_ARG((v_compensations == nullptr) || (compensations != nullptr),
                  "v_compensations given without compensations");
     dim3 grid(gs_div_up(N, GS_BLOCK));
-    const RowGrads rg = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0u, nullptr, nullptr, nullptr, 1.f, 0, nullptr};
-    if (v_viewmats != nullptr) {
-        hipLaunchKernelGGL(projection_bwd_kernel<true>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N,
-                           means, covars, quats, scales, viewmats, Ks, image_width, image_height, eps2d,
-                           camera_model, radii, conics, compensations, v_means2d, v_depths, v_conics,
-                           v_compensations, v_means, v_covars, v_quats, v_scales, v_viewmats, v_means2d_stride,
-                           v_conics_stride, v_means_add, rg);
-    } else {
-        hipLaunchKernelGGL(projection_bwd_kernel<false>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N,
-                           means, covars, quats, scales, viewmats, Ks, image_width, image_height, eps2d,
-                           camera_model, radii, conics, compensations, v_means2d, v_depths, v_conics,
-                           v_compensations, v_means, v_covars, v_quats, v_scales, v_viewmats, v_means2d_stride,
-                           v_conics_stride, v_means_add, rg);
-    }
+    const ArrayPairs src = {conics, compensations, v_means2d, v_depths, v_conics, v_compensations, v_means2d_stride, v_conics_stride};
+    launch_flagged(v_viewmats != nullptr, projection_bwd_kernel<true, -1, ArrayPairs>, projection_bwd_kernel<false, -1, ArrayPairs>, grid, stream,
+                   C, N, means, covars, quats, scales, viewmats, Ks, image_width, image_height, eps2d, camera_model, radii, src, v_means,
+                   v_covars, v_quats, v_scales, v_viewmats, v_means_add);
     GS_CHECK_LAUNCH();
     return 0;
 }
@@ -661,9 +532,7 @@ extern "C" int32_t gs_projection_packed_count(
     int32_t image_height, float eps2d, float near_plane, float far_plane, float radius_clip,
     int32_t camera_model, int32_t *block_cnts, gs_stream_t stream) {
     if (C == 0 || N == 0) return 0;
-    GS_CHECK_ARG(means && viewmats && Ks && block_cnts, "null pointer");
-    GS_CHECK_ARG((covars != nullptr) != (quats != nullptr && scales != nullptr),
-                 "exactly one of covars / (quats, scales) must be given");
+    GS_CHECK_GEOMETRY(means && viewmats && Ks && block_cnts, covars, quats, scales, camera_model);
     dim3 grid(gs_div_up(N, GS_BLOCK), C);
     hipLaunchKernelGGL(projection_packed_kernel<false>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N,
                        means, covars, quats, scales, viewmats, Ks, image_width, image_height, eps2d,
@@ -682,9 +551,7 @@ extern "C" int32_t gs_projection_packed_fill(
     int64_t *gaussian_ids, int32_t *radii, float *means2d, float *depths, float *conics,
     float *compensations, gs_stream_t stream) {
     if (C == 0 || N == 0) return 0;
-    GS_CHECK_ARG(means && viewmats && Ks && block_accum && indptr, "null pointer");
-    GS_CHECK_ARG((covars != nullptr) != (quats != nullptr && scales != nullptr),
-                 "exactly one of covars / (quats, scales) must be given");
+    GS_CHECK_GEOMETRY(means && viewmats && Ks && block_accum && indptr, covars, quats, scales, camera_model);
     dim3 grid(gs_div_up(N, GS_BLOCK), C);
     hipLaunchKernelGGL(projection_packed_kernel<true>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N,
                        means, covars, quats, scales, viewmats, Ks, image_width, image_height, eps2d,
@@ -703,24 +570,13 @@ extern "C" int32_t gs_projection_packed_bwd(
     const float *v_conics, const float *v_compensations, int32_t sparse_grad, float *v_means,
     float *v_covars, float *v_quats, float *v_scales, float *v_viewmats, gs_stream_t stream) {
     if (nnz == 0) return 0;
-    GS_CHECK_ARG(means && viewmats && Ks, "null pointer");
-    GS_CHECK_ARG((covars != nullptr) != (quats != nullptr && scales != nullptr),
-                 "exactly one of covars / (quats, scales) must be given");
-    GS_CHECK_ARG(camera_ids && gaussian_ids && conics && v_means2d && v_conics, "null pointer");
+    GS_CHECK_GEOMETRY(means && viewmats && Ks && camera_ids && gaussian_ids && conics && v_means2d && v_conics, covars, quats, scales,
+                      camera_model);
     dim3 grid(gs_div_up(nnz, GS_BLOCK));
-    if (v_viewmats != nullptr) {
-        hipLaunchKernelGGL(projection_packed_bwd_kernel<true>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream,
-                           C, N, nnz, means, covars, quats, scales, viewmats, Ks, image_width, image_height,
-                           eps2d, camera_model, camera_ids, gaussian_ids, conics, compensations, v_means2d,
-                           v_depths, v_conics, v_compensations, sparse_grad, v_means, v_covars, v_quats,
-                           v_scales, v_viewmats);
-    } else {
-        hipLaunchKernelGGL(projection_packed_bwd_kernel<false>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream,
-                           C, N, nnz, means, covars, quats, scales, viewmats, Ks, image_width, image_height,
-                           eps2d, camera_model, camera_ids, gaussian_ids, conics, compensations, v_means2d,
-                           v_depths, v_conics, v_compensations, sparse_grad, v_means, v_covars, v_quats,
-                           v_scales, v_viewmats);
-    }
+    launch_flagged(v_viewmats != nullptr, projection_packed_bwd_kernel<true>, projection_packed_bwd_kernel<false>, grid, stream, C, N, nnz,
+                   means, covars, quats, scales, viewmats, Ks, image_width, image_height, eps2d, camera_model, camera_ids, gaussian_ids,
+                   conics, compensations, v_means2d, v_depths, v_conics, v_compensations, sparse_grad, v_means, v_covars, v_quats, v_scales,
+                   v_viewmats);
     GS_CHECK_LAUNCH();
     return 0;
 }

@@ -1,6 +1,8 @@
 // projection_dev.h -- the per-(camera, gaussian) projection arithmetic and its VJP, shared by the kernels of projection.hip and
 // projection_dyn.hip (the temporal slice of dynamic splats evaluated in the projection's load phase): ONE definition, so that
-// every kernel that projects a splat computes bit-identical rows.  Device code only.
+// every kernel that projects a splat computes bit-identical rows.  So are the stages around the arithmetic that more than one route
+// has (the row store, the row-pair read of the backward, the per-gaussian gradient finish, the pose gradient pack) and, at the end,
+// what the entry points of both files share on the host: the geometry check and the launch by a bool template flag.
 //   reference: gsplat/cuda/csrc/fully_fused_projection_fwd.cu:22-196, fully_fused_projection_bwd.cu:24-263
 #pragma once
 #include "gs_common.h"
@@ -143,6 +145,27 @@ GS_DEV void rows_count_tiles(const Splat2D &s, bool in, size_t idx, int32_t *__r
     }
 }
 
+// The forward's 64-byte splat row (include/gsplat_hip.h "Splat rows"), written by every kernel that projects into rows: `op` is the
+// opacity column as the compositing kernels take it (x antialias compensation already).  With colours the 48 bytes behind the
+// mean2d / conic quad leave in two more full 16-byte stores; without, the colour columns belong to the SH kernel (gs_sh_view_fwd
+// writes them into the same rows) and are left alone.
+// `color(c0, c1, c2)` is only evaluated for rows with colour columns, and after the first quad has left: with the colours as
+// plain arguments mean2d / conic stay live across their evaluation (SH: + 4 .. 7 VGPRs, a wave per SIMD less at degree 3).
+template <class ColorFn>
+GS_DEV void store_splat_row(float *__restrict__ row, const Splat2D &s, float op, bool has_color, ColorFn color) {
+    reinterpret_cast<float4 *>(row)[0] = make_float4(s.mx, s.my, s.ca, s.cb);
+    if (has_color) {
+        float c0, c1, c2;
+        color(c0, c1, c2);
+        reinterpret_cast<float4 *>(row)[1] = make_float4(s.cc, op, c0, c1);
+        reinterpret_cast<float4 *>(row)[2] = make_float4(c2, s.depth, __int_as_float(s.radius), s.comp);
+    } else {
+        reinterpret_cast<float2 *>(row)[2] = make_float2(s.cc, op);
+        row[GS_ROW_DEPTH] = s.depth;
+        reinterpret_cast<float2 *>(row)[5] = make_float2(__int_as_float(s.radius), s.comp);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------
@@ -249,6 +272,122 @@ GS_DEV void grad_zero(ProjGrad &g) {
     g.v_S = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     g.v_W = mat3_zero();
     g.v_t[0] = g.v_t[1] = g.v_t[2] = 0.f;
+}
+
+// What the row form of the backward sums over the cameras next to the ProjGrad: the opacity and colour cotangents of one gaussian
+// (what autograd's `opacities.repeat(C, 1)` / `colors.expand` backward and the antialias multiply did in passes of their own).
+struct RowSums {
+    float v_op, v_c0, v_c1, v_c2;
+};
+
+// One (camera, gaussian) pair of the row form: conic / compensation from the splat row, the cotangents of mean2d / conic / opacity /
+// colour from the compositing backward's gradient row (same columns); adds to `sum` and, through the projection's VJP, to `g`.
+// `opacity` is what the forward multiplied by the compensation to get the row's opacity column (read when antialiased only).
+template <bool NEED_VIEW>
+GS_DEV void row_pair_vjp(
+    const Camera &cam, float px, float py, float pz, const Sym3 &S, int W, int H, float eps2d, int camera_model,
+    const float *__restrict__ rows, const float *__restrict__ grad_rows, const float *__restrict__ v_depths, size_t idx,
+    bool antialiased, float opacity, bool third_color, RowSums &sum, ProjGrad &g) {
+    const float4 *r = reinterpret_cast<const float4 *>(rows + GS_ROW_FLOATS * idx);
+    const float4 *gr = reinterpret_cast<const float4 *>(grad_rows + GS_ROW_FLOATS * idx);
+    const float4 r0 = r[0], g0 = gr[0], g1 = gr[1];
+    const float cc = reinterpret_cast<const float *>(r)[GS_ROW_CONIC + 2];
+    const float comp = antialiased ? reinterpret_cast<const float *>(r)[GS_ROW_COMPENSATION] : 1.f;
+    const float v_opac_cn = g1.y;
+    const float v_comp = antialiased ? v_opac_cn * opacity : 0.f;
+    sum.v_op += v_opac_cn * comp;
+    sum.v_c0 += g1.z;
+    sum.v_c1 += g1.w;
+    if (third_color) sum.v_c2 += reinterpret_cast<const float *>(gr)[GS_ROW_COLOR + 2];
+    project_one_vjp<NEED_VIEW>(cam, px, py, pz, S, W, H, eps2d, camera_model, r0.z, r0.w, cc, comp, v_comp, antialiased, g0.x, g0.y,
+                               v_depths != nullptr ? v_depths[idx] : 0.f, g0.z, g0.w, g1.x, g);
+}
+
+// The store operations of store_gaussian_grads: a row that one lane owns, or one that -- decided at run time -- is either that or
+// a (zero-filled) row that several (camera, gaussian) pairs add to with float atomics.
+struct PutStore {
+    GS_DEV void operator()(float *dst, float v) const { *dst = v; }
+};
+struct PutStoreOrAdd {
+    bool store;
+    GS_DEV void operator()(float *dst, float v) const {
+        if (store) *dst = v;
+        else atomicAdd(dst, v);
+    }
+};
+
+// The per-gaussian gradient finish: d/d means (g.v_p*), and d/d covars or -- through covar_vjp_quat_scale on gaussian n's quats /
+// scales -- d/d quats and scales, put into row `o` of the outputs.  any == false: nothing reached g, the quat / scale rows are zeros.
+template <class Put>
+GS_DEV void store_gaussian_grads(
+    const ProjGrad &g, uint32_t n, size_t o, bool any,
+    const float *__restrict__ covars, const float *__restrict__ quats, const float *__restrict__ scales,
+    float *__restrict__ v_means, float *__restrict__ v_covars, float *__restrict__ v_quats, float *__restrict__ v_scales, const Put &put) {
+    if (v_means != nullptr) {
+        put(v_means + 3 * o, g.v_px);
+        put(v_means + 3 * o + 1, g.v_py);
+        put(v_means + 3 * o + 2, g.v_pz);
+    }
+    if (covars != nullptr) {
+        if (v_covars != nullptr) {
+            float *d = v_covars + 6 * o;
+            // off-diagonals carry both (i,j) and (j,i): fully_fused_projection_bwd.cu:217-222
+            put(d, g.v_S.xx); put(d + 1, 2.f * g.v_S.xy); put(d + 2, 2.f * g.v_S.xz);
+            put(d + 3, g.v_S.yy); put(d + 4, 2.f * g.v_S.yz); put(d + 5, g.v_S.zz);
+        }
+    } else {
+        float vq[4] = {0.f, 0.f, 0.f, 0.f}, vs[3] = {0.f, 0.f, 0.f};
+        if (any) {
+            const float *q = quats + 4 * (size_t)n;
+            const float *s = scales + 3 * (size_t)n;
+            Mat3 R = quat_to_rotmat(q[0], q[1], q[2], q[3]);
+            covar_vjp_quat_scale(q[0], q[1], q[2], q[3], s[0], s[1], s[2], R, sym3_to_mat3(g.v_S), vq, vs);
+        }
+        if (v_quats != nullptr) {
+            float *d = v_quats + 4 * o;
+            put(d, vq[0]); put(d + 1, vq[1]); put(d + 2, vq[2]); put(d + 3, vq[3]);
+        }
+        if (v_scales != nullptr) {
+            float *d = v_scales + 3 * o;
+            put(d, vs[0]); put(d + 1, vs[1]); put(d + 2, vs[2]);
+        }
+    }
+}
+
+// The pose gradient of one lane as the 12 values v_W | v_t of the view matrix's first three rows (4 per row: rotation, translation)
+GS_DEV void view_grad_vals(const ProjGrad &g, float vals[12]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) vals[4 * i + j] = g.v_W.m[i][j];
+        vals[4 * i + 3] = g.v_t[i];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+
+// What every projection entry point checks about its geometry arguments, in this order: the message of the first failed check, or
+// NULL.  `pointers`: the entry's own required pointers are all there.  Entries that take no covars pass NULL for them.
+inline const char *projection_geometry_error(bool pointers, const float *covars, const float *quats, const float *scales, int32_t camera_model) {
+    if (!pointers) return "null pointer";
+    if ((covars != nullptr) == (quats != nullptr && scales != nullptr)) return "exactly one of covars / (quats, scales) must be given";
+    if (camera_model < 0 || camera_model > 2) return "bad camera_model";
+    return nullptr;
+}
+
+#define GS_CHECK_GEOMETRY(pointers, covars, quats, scales, camera_model)                                       \
+    do {                                                                                                       \
+        const char *m_ = projection_geometry_error(pointers, covars, quats, scales, camera_model);             \
+        GS_CHECK_ARG(m_ == nullptr, m_);                                                                       \
+    } while (0)
+
+// Launch the instantiation of a kernel that `flag` selects (NEED_VIEW, QUANT: a bool template parameter), GS_BLOCK threads per
+// workgroup: the two instantiations share their signature, and the arguments are written once.
+template <class... P, class... A>
+inline void launch_flagged(bool flag, void (*on)(P...), void (*off)(P...), dim3 grid, gs_stream_t stream, A... args) {
+    hipLaunchKernelGGL(flag ? on : off, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, static_cast<P>(args)...);
 }
 
 } // namespace

@@ -178,27 +178,20 @@ __global__ void __launch_bounds__(GS_BLOCK) projection_dyn_fwd_kernel(
     }
     radii[idx] = s.radius;
     if (s.radius <= 0) return;
-    float *row = rows + GS_ROW_FLOATS * idx;
-    depths[idx] = s.depth;
     float op = 0.f;
     if (rx.opacities != nullptr) {
         if (!QUANT) dyn_opacity<false>(dyn, rx.opacities, n, false, o);
         op = o.op_t;
     }
     if (rx.antialiased) op *= s.comp;
-    reinterpret_cast<float4 *>(row)[0] = make_float4(s.mx, s.my, s.ca, s.cb);
-    if (rx.colors != nullptr) {
-        if (!QUANT) {
+    depths[idx] = s.depth;
+    store_splat_row(rows + GS_ROW_FLOATS * idx, s, op, rx.colors != nullptr, [&](float &c0, float &c1, float &c2) {
+        if (!QUANT) { // (quantized: the colours went through the quantizer above, with every other hooked row)
             const float *cp = rx.colors + 3 * (size_t)n;
             col[0] = cp[0]; col[1] = cp[1]; col[2] = cp[2];
         }
-        reinterpret_cast<float4 *>(row)[1] = make_float4(s.cc, op, col[0], col[1]);
-        reinterpret_cast<float4 *>(row)[2] = make_float4(col[2], s.depth, __int_as_float(s.radius), s.comp);
-    } else {
-        reinterpret_cast<float2 *>(row)[2] = make_float2(s.cc, op);
-        row[GS_ROW_DEPTH] = s.depth;
-        reinterpret_cast<float2 *>(row)[5] = make_float2(__int_as_float(s.radius), s.comp);
-    }
+        c0 = col[0]; c1 = col[1]; c2 = col[2];
+    });
 }
 
 struct DynGradOut {
@@ -218,7 +211,7 @@ __global__ void __launch_bounds__(GS_BLOCK) projection_dyn_bwd_kernel(
     Sym3 S = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     ProjGrad g;
     grad_zero(g);
-    float v_op = 0.f, v_c0 = 0.f, v_c1 = 0.f, v_c2 = 0.f;
+    RowSums sums = {0.f, 0.f, 0.f, 0.f};
     bool any = false;
     for (uint32_t c = 0; c < C; ++c) {
         const size_t idx = (size_t)c * N + n;
@@ -237,19 +230,8 @@ __global__ void __launch_bounds__(GS_BLOCK) projection_dyn_bwd_kernel(
             any = true;
         }
         Camera cam = load_camera(viewmats, Ks, c);
-        const float4 *r = reinterpret_cast<const float4 *>(rows + GS_ROW_FLOATS * idx);
-        const float4 *gr = reinterpret_cast<const float4 *>(grad_rows + GS_ROW_FLOATS * idx);
-        const float4 r0 = r[0], g0 = gr[0], g1 = gr[1];
-        const float cc = reinterpret_cast<const float *>(r)[GS_ROW_CONIC + 2];
-        const float comp = antialiased ? reinterpret_cast<const float *>(r)[GS_ROW_COMPENSATION] : 1.f;
-        const float v_opac_cn = g1.y;
-        const float v_comp = antialiased ? v_opac_cn * o.op_t : 0.f;
-        v_op += v_opac_cn * comp;
-        v_c0 += g1.z;
-        v_c1 += g1.w;
-        if (out.v_colors != nullptr) v_c2 += reinterpret_cast<const float *>(gr)[GS_ROW_COLOR + 2];
-        project_one_vjp<false>(cam, o.mx, o.my, o.mz, S, W, H, eps2d, camera_model, r0.z, r0.w, cc, comp, v_comp, antialiased != 0, g0.x, g0.y,
-                               v_depths != nullptr ? v_depths[idx] : 0.f, g0.z, g0.w, g1.x, g);
+        row_pair_vjp<false>(cam, o.mx, o.my, o.mz, S, W, H, eps2d, camera_model, rows, grad_rows, v_depths, idx, antialiased != 0, o.op_t,
+                            out.v_colors != nullptr, sums, g);
     }
     if (!any && out.prefilled) return;
     float vq[4] = {0.f, 0.f, 0.f, 0.f}, vs[3] = {0.f, 0.f, 0.f}, vx[4] = {0.f, 0.f, 0.f, 0.f};
@@ -260,8 +242,8 @@ __global__ void __launch_bounds__(GS_BLOCK) projection_dyn_bwd_kernel(
         // ---- back through the slice (dynamic_dev.h; what gs_temporal_slice_bwd computes from v_means_t / v_quats_t / v_opacity_t)
         tau = o.st.tau; t2 = (tau * tau); t3 = (t2 * tau);
         slice_quat_vjp(o.x, vq, vx);
-        v_opac = (v_op * o.st.trbf);
-        slice_time_vjp(o.st, o.ts, (v_op * o.op_act), v_center, v_tscale);
+        v_opac = (sums.v_op * o.st.trbf);
+        slice_time_vjp(o.st, o.ts, (sums.v_op * o.op_act), v_center, v_tscale);
         // ---- back through the activations (the round STE in between is the identity, ops.py:73-75)
         if (dyn.raw & GS_DYN_RAW_SCALES) {
 #pragma unroll
@@ -296,9 +278,9 @@ __global__ void __launch_bounds__(GS_BLOCK) projection_dyn_bwd_kernel(
     if (out.v_center != nullptr) out.v_center[n] = v_center;
     if (out.v_tscale != nullptr) out.v_tscale[n] = v_tscale;
     if (out.v_colors != nullptr) {
-        out.v_colors[3 * (size_t)n] = v_c0;
-        out.v_colors[3 * (size_t)n + 1] = v_c1;
-        out.v_colors[3 * (size_t)n + 2] = v_c2;
+        out.v_colors[3 * (size_t)n] = sums.v_c0;
+        out.v_colors[3 * (size_t)n + 1] = sums.v_c1;
+        out.v_colors[3 * (size_t)n + 2] = sums.v_c2;
     }
 }
 
@@ -327,10 +309,9 @@ extern "C" int32_t gs_projection_rows_dyn_fwd(
     float radius_clip, int32_t camera_model, float *opacities, float *colors, int32_t antialiased, uint32_t tile_size, uint32_t tile_width,
     uint32_t tile_height, int32_t *tiles_per_gauss, int32_t *block_sums, int32_t *radii, float *depths, float *rows, gs_stream_t stream) {
     if (C == 0 || N == 0) return 0;
-    GS_CHECK_ARG(means && quats && scales && motion && omega && trbf_center && trbf_scale && viewmats && Ks && radii && depths && rows,
-                 "null pointer");
+    GS_CHECK_GEOMETRY(means && quats && scales && motion && omega && trbf_center && trbf_scale && viewmats && Ks && radii && depths && rows,
+                      nullptr, quats, scales, camera_model);
     GS_CHECK_ARG((uintptr_t)rows % 64 == 0, "the row buffer must be 64-byte aligned");
-    GS_CHECK_ARG(camera_model >= 0 && camera_model <= 2, "bad camera_model");
     GS_CHECK_ARG(!antialiased || opacities != nullptr, "antialiased needs the opacities");
     GS_CHECK_ARG(tiles_per_gauss != nullptr || block_sums == nullptr, "block_sums come with tiles_per_gauss");
     GS_CHECK_ARG(tiles_per_gauss == nullptr || tile_size > 0, "tile_size must be > 0");
@@ -343,12 +324,8 @@ extern "C" int32_t gs_projection_rows_dyn_fwd(
     d.alive_out = trbf_alive;
     const DynRowArgs rx = {opacities, colors, antialiased, tiles_per_gauss, block_sums, (float)tile_size, (int32_t)tile_width, (int32_t)tile_height};
     const dim3 grid(gs_div_up(N, GS_BLOCK), C);
-    if (d.quant)
-        hipLaunchKernelGGL(projection_dyn_fwd_kernel<true>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N, means, quats, scales, viewmats, Ks,
-                           image_width, image_height, eps2d, near_plane, far_plane, radius_clip, camera_model, radii, rows, depths, rx, d);
-    else
-        hipLaunchKernelGGL(projection_dyn_fwd_kernel<false>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N, means, quats, scales, viewmats, Ks,
-                           image_width, image_height, eps2d, near_plane, far_plane, radius_clip, camera_model, radii, rows, depths, rx, d);
+    launch_flagged(d.quant != 0u, projection_dyn_fwd_kernel<true>, projection_dyn_fwd_kernel<false>, grid, stream, C, N, means, quats, scales,
+                   viewmats, Ks, image_width, image_height, eps2d, near_plane, far_plane, radius_clip, camera_model, radii, rows, depths, rx, d);
     GS_CHECK_LAUNCH();
     return 0;
 }
@@ -362,10 +339,9 @@ extern "C" int32_t gs_projection_rows_dyn_bwd(
     float *v_scales, float *v_motion, float *v_omega, float *v_trbf_center, float *v_trbf_scale, float *v_opacities, float *v_colors,
     int32_t outputs_prefilled, gs_stream_t stream) {
     if (N == 0) return 0;
-    GS_CHECK_ARG(means && quats && scales && motion && omega && trbf_center && trbf_scale && viewmats && Ks && radii && rows && grad_rows,
-                 "null pointer");
+    GS_CHECK_GEOMETRY(means && quats && scales && motion && omega && trbf_center && trbf_scale && viewmats && Ks && radii && rows && grad_rows,
+                      nullptr, quats, scales, camera_model);
     GS_CHECK_ARG((uintptr_t)rows % 16 == 0 && (uintptr_t)grad_rows % 16 == 0, "row buffers must be 16-byte aligned");
-    GS_CHECK_ARG(camera_model >= 0 && camera_model <= 2, "bad camera_model");
     GS_CHECK_ARG(opacities != nullptr || (!antialiased && v_opacities == nullptr && v_trbf_center == nullptr && v_trbf_scale == nullptr),
                  "the opacity / trbf gradients (and antialiased) need the opacities");
     DynArgs d;
@@ -374,12 +350,8 @@ extern "C" int32_t gs_projection_rows_dyn_bwd(
     d.quant &= opacities != nullptr ? 15u : 11u;
     const DynGradOut out = {v_means, v_quats, v_scales, v_motion, v_omega, v_trbf_center, v_trbf_scale, v_opacities, v_colors, outputs_prefilled != 0};
     const dim3 grid(gs_div_up(N, GS_BLOCK));
-    if (d.quant)
-        hipLaunchKernelGGL(projection_dyn_bwd_kernel<true>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N, means, quats, scales, opacities,
-                           viewmats, Ks, image_width, image_height, eps2d, camera_model, radii, rows, grad_rows, v_depths, antialiased, d, out);
-    else
-        hipLaunchKernelGGL(projection_dyn_bwd_kernel<false>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, C, N, means, quats, scales, opacities,
-                           viewmats, Ks, image_width, image_height, eps2d, camera_model, radii, rows, grad_rows, v_depths, antialiased, d, out);
+    launch_flagged(d.quant != 0u, projection_dyn_bwd_kernel<true>, projection_dyn_bwd_kernel<false>, grid, stream, C, N, means, quats, scales,
+                   opacities, viewmats, Ks, image_width, image_height, eps2d, camera_model, radii, rows, grad_rows, v_depths, antialiased, d, out);
     GS_CHECK_LAUNCH();
     return 0;
 }

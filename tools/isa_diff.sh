@@ -22,15 +22,21 @@ def kernels(path):
             # the generic wave kernels before they lost their pixels-per-lane / colour-in-LDS / checkpoint axes
             cur = re.sub(r'raster_wave_fwd_kernelILi1E(Li\d+E)Lb0ELb0EEEv10RasterArgsjjPfi', r'raster_wave_fwd_kernelI\1EEv10RasterArgsjj', cur)
             cur = re.sub(r'raster_wave_bwd_kernelILi1E(Li\d+ELi\d+ELb[01]E)', r'raster_wave_bwd_kernelI\1', cur)
+            # projection_bwd_kernel before its per-pair inputs became a template policy: ONE instance <NEED_VIEW, SHDEG> served the
+            # array and the row form, so both new instances <NEED_VIEW, SHDEG, ArrayPairs | RowPairs> are compared with it
+            m = re.match(r'(.*projection_bwd_kernelILb[01]ELin?\d+E)(?:NS_\d+(ArrayPairs|RowPairs)E)?EEv', cur)
+            if m:
+                cur = m.group(1) + (' [' + m.group(2) + ']' if m.group(2) else '')
             out[cur] = []
         elif cur is not None and ln.strip():
             out[cur].append(re.sub(r'<[^>]*>', '<L>', ln.strip()))
     return out
 A, B = kernels('/tmp/isa_a.txt'), kernels('/tmp/isa_b.txt')
-for k in sorted(set(A) | set(B)):
+base = lambda k: k.split(' [')[0]  # a new instance tagged ' [policy]' is compared with the old one without the tag
+for k in sorted((set(A) - {base(k) for k in B}) | set(B)):
     if frag and frag not in k:
         continue
-    a, b = A.get(k), B.get(k)
+    a, b = A.get(k, A.get(base(k))), B.get(k)
     if a is None or b is None:
         print(('ONLY-OLD ' if b is None else 'ONLY-NEW ') + k[:150]); continue
     print(('SAME     ' if a == b else f'DIFF {len(a)}->{len(b)} ') + k[:150])
