@@ -1,12 +1,17 @@
-"""Factorized-prior bits estimator behind the quantize hooks.
+"""Bits estimators behind the quantize hooks.
 
 ``Entropy_factorized_optimized_refactor`` keeps the reference's constructor, parameter names
 (``_matrices``, ``_bias``, ``_factor`` ParameterLists, same shapes and initialisation) and
 ``forward(x, Q) -> bits [N, C]`` contract (gsplat/compression_simulation/entropy_model.py:84-254),
 so state dicts and optimizers are interchangeable; the ~30-kernel torch graph is replaced by one
 fused HIP kernel each way (csrc/entropy.hip, ``gs_entropy_factorized_fwd/bwd``).  There is no torch
-fallback: CPU tensors raise.  The hash-grid Gaussian model (``Entropy_gaussian``) needs the
-reference's CUDA-only ``_gridencoder`` extension and is not provided.
+fallback: CPU tensors raise.
+
+``Entropy_gaussian`` is the position-conditioned model (reference entropy_model.py:313-345): the hash-grid
+regressor of gaussian_distribution_model.py predicts a mean and a scale per channel, and the bits are
+``-log2`` of that Gaussian's mass over one quantization bin -- encoder launch, the regressor's two torch
+GEMMs, one bits launch (csrc/hashgrid.hip, ``gs_gaussian_bits_fwd/bwd``) that reads the regressor's
+``[N, 2C]`` output in place.
 """
 from __future__ import annotations
 
@@ -16,6 +21,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _backend as B
+from .gaussian_distribution_model import hash_based_estimator
 
 
 _REPLICAS = 32  # copies of the parameter-gradient buffer the workgroups spread their atomics over
@@ -23,6 +29,18 @@ _REPLICAS = 32  # copies of the parameter-gradient buffer the workgroups spread 
 
 def _stream(t: Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _half_q(x: Tensor, Q, channel: int) -> Tensor:
+    """Q (number, or tensor of 1 or ``channel`` elements) -> [channel] device floats Q / 2, what the bits kernels read."""
+    if isinstance(Q, Tensor):
+        q = Q.detach().to(device=x.device, dtype=torch.float32).reshape(-1)
+        if q.numel() == 1:
+            q = q.expand(channel)
+        elif q.numel() != channel:
+            raise ValueError(f"Q must have 1 or {channel} elements, got {q.numel()}")
+        return (0.5 * q).contiguous()
+    return torch.full((channel,), 0.5 * float(Q), dtype=torch.float32, device=x.device)
 
 
 class _FactorizedBits(torch.autograd.Function):
@@ -142,16 +160,7 @@ class Entropy_factorized_optimized_refactor(nn.Module):
         return torch.cat(parts, dim=1).contiguous()
 
     def _half_q(self, x: Tensor, Q) -> Tensor:
-        if Q is None:
-            Q = self.Q
-        if isinstance(Q, Tensor):
-            q = Q.detach().to(device=x.device, dtype=torch.float32).reshape(-1)
-            if q.numel() == 1:
-                q = q.expand(self.channel)
-            elif q.numel() != self.channel:
-                raise ValueError(f"Q must have 1 or {self.channel} elements, got {q.numel()}")
-            return (0.5 * q).contiguous()
-        return torch.full((self.channel,), 0.5 * float(Q), dtype=torch.float32, device=x.device)
+        return _half_q(x, self.Q if Q is None else Q, self.channel)
 
     def forward(self, x: Tensor, Q=None, **kwargs) -> Tensor:
         assert x.dim() == 2 and x.shape[1] == self.channel, f"x must be [N, {self.channel}], got {tuple(x.shape)}"
@@ -163,3 +172,63 @@ class Entropy_factorized_optimized_refactor(nn.Module):
     def get_likelihood(self, x: Tensor, Q=None, **kwargs) -> Tensor:
         """The bounded likelihood (reference entropy_model.py:256-305) = 2^-bits."""
         return torch.exp2(-self.forward(x, Q))
+
+
+class _GaussianBits(torch.autograd.Function):
+    """bits [N, C] of x [N, C] under N(net[:, :C], max(net[:, C:], 1e-9)) over one bin of width 2 half_q."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, net: Tensor, half_q: Tensor, bound: float) -> Tensor:
+        if not (x.is_cuda and net.is_cuda):
+            raise RuntimeError("Gaussian bits estimator: the HIP path needs device tensors (no CPU fallback)")
+        x, net = x.contiguous(), net.contiguous()
+        bits = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            B.call("gs_gaussian_bits_fwd", x.shape[0], x.shape[1], B.ptr(x), B.ptr(net), B.ptr(half_q), float(bound),
+                   B.ptr(bits), _stream(x))
+        ctx.save_for_backward(x, net, half_q)
+        ctx.bound = float(bound)
+        return bits
+
+    @staticmethod
+    def backward(ctx, v_bits: Tensor):
+        x, net, half_q = ctx.saved_tensors
+        v_bits = v_bits.contiguous()
+        v_x, v_net = torch.empty_like(x), torch.empty_like(net)
+        with torch.cuda.device(x.device):
+            B.call("gs_gaussian_bits_bwd", x.shape[0], x.shape[1], B.ptr(x), B.ptr(net), B.ptr(half_q), ctx.bound,
+                   B.ptr(v_bits), B.ptr(v_x), B.ptr(v_net), _stream(x))
+        return v_x, v_net, None, None
+
+
+class Entropy_gaussian(nn.Module):
+    """bits[n, c] = -log2 of the mass of N(mean[n, c], scale[n, c]) over [x - Q/2, x + Q/2], mean and scale regressed from the
+    splat's position through a multi-resolution hash grid (reference entropy_model.py:313-345; same constructor, attribute
+    names and state-dict keys)."""
+
+    def __init__(self, channel=3, Q=1, likelihood_bound=1e-6):
+        super().__init__()
+        if not 1 <= int(channel) <= 32:
+            raise NotImplementedError("channel must be in 1..32")
+        self.Q = Q
+        self.likelihood_bound = float(likelihood_bound)
+        self.likelihood_lower_bound = LowerBound(likelihood_bound)
+        self.mean = 0
+        self.scale = 1
+        self.param_regressor = hash_based_estimator(channel)
+
+    def forward(self, x: Tensor, Q=None, pos: Tensor = None) -> Tensor:
+        assert pos is not None
+        assert x.size()[0] == pos.size()[0]
+        channel = self.param_regressor.channel
+        assert x.dim() == 2 and x.shape[1] == channel, f"x must be [N, {channel}], got {tuple(x.shape)}"
+        if not (x.is_cuda and pos.is_cuda):
+            raise RuntimeError("Gaussian bits estimator: the HIP path needs device tensors (no CPU fallback)")
+        if x.dtype != torch.float32:
+            x = x.float()
+        net = self.param_regressor.regress(pos.float())
+        return _GaussianBits.apply(x, net, _half_q(x, self.Q if Q is None else Q, channel), self.likelihood_bound)
+
+    def get_means_and_scales(self, pos: Tensor):
+        means, scales = self.param_regressor(pos)
+        return means, torch.clamp(scales, min=1e-9)

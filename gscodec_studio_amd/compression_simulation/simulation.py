@@ -5,8 +5,9 @@ Mirrors ``CompressionSimulation`` (reference simulation.py:14-348) and
 and bit widths, and the ``simulate_compression(splats, step) -> (new_splats, esti_bits)``
 contract.  ``entropy_model_enable=True`` with the factorized prior attaches the fused bits
 estimator (entropy_model.py, reference wiring simulation.py:87-149, 247-316, 576-608); the
-hash-grid Gaussian model needs the reference's CUDA-only ``_gridencoder`` and raises
-NotImplementedError.  ``ada_mask_opt=True`` attaches the learnable shN mask (ada_mask.py; reference
+hash-grid Gaussian model (``entropy_model_type="gaussian_model"`` in the reference) is wired up by
+``HashGridCompressionSimulation``, and ``CompressionSimulation`` itself keeps raising
+NotImplementedError for it.  ``ada_mask_opt=True`` attaches the learnable shN mask (ada_mask.py; reference
 simulation.py:38-41, 151-168, 319-324, 611-620) or, with ``ada_mask_strategy="gradient"``, the
 gradient threshold (simulation.py:327-348).  Every attribute the reference's trainers read
 (``shN_ada_mask_opt``, ``shN_ada_mask_step``, ``shN_ada_mask_strategy``, ``shN_qat``, ``shN_ada_mask``,
@@ -24,7 +25,7 @@ from typing_extensions import Literal
 
 from .ada_mask import AnnealingMask
 from .ada_mask import shN_gradient_threshold as _shN_gradient_threshold
-from .entropy_model import Entropy_factorized_optimized_refactor
+from .entropy_model import Entropy_factorized_optimized_refactor, Entropy_gaussian
 from .ops import QUANT_MULTI_MAX, fake_quantize_noise_multi, fake_quantize_round_multi, fake_quantize_ste, multi_selfcheck
 
 
@@ -38,30 +39,38 @@ class _SimulationBase:
     entropy_model_option: Dict[str, bool] = {}
     entropy_models: Dict[str, Optional[torch.nn.Module]] = {}
 
+    _ENTROPY_MODEL_TYPE = "factorized_model"  # the one model type a class wires up (HashGridCompressionSimulation: "gaussian_model")
+
     def _setup_entropy(self, enable: bool, model_type: str, specs: Dict[str, Optional[dict]]) -> None:
-        """Factorized-prior models + their Adam optimizers (reference simulation.py:87-149, 576-608).
+        """Entropy models + their Adam optimizers and schedulers (reference simulation.py:87-149, 576-608).
         ``specs``: attribute -> constructor kwargs (None: no model)."""
         self.entropy_model_enable = bool(enable)
         if not enable:
             return
-        if model_type != "factorized_model":
+        if model_type != self._ENTROPY_MODEL_TYPE:
             raise NotImplementedError(
-                f"entropy_model_type={model_type!r}: only the factorized prior is built (the hash-grid Gaussian "
-                "model depends on the reference's CUDA-only _gridencoder extension)")
+                f"entropy_model_type={model_type!r}: {type(self).__name__} wires up {self._ENTROPY_MODEL_TYPE!r} only (the "
+                "hash-grid Gaussian model, 'gaussian_model', comes with HashGridCompressionSimulation)")
         if self.entropy_steps is None:
             raise ValueError("entropy_model_enable=True needs entropy_steps")
         for name in list(self.entropy_model_option):  # turn off if entropy step < 0 (simulation.py:70-73)
             if self.entropy_steps.get(name, -1) < 0:
                 self.entropy_model_option[name] = False
-        self.entropy_models = {k: (Entropy_factorized_optimized_refactor(**kw).to(self.device) if kw is not None else None)
+        self.entropy_models = {k: (self._entropy_model(**kw).to(self.device) if kw is not None else None)
                                for k, kw in specs.items()}
         positive = [k for k, v in self.entropy_steps.items() if v > 0]
         self.entropy_min_step = self.entropy_steps[min(positive, key=lambda k: self.entropy_steps[k])] if positive else 0
         self.entropy_model_optimizers, self.entropy_model_schedulers = {}, {}
         for k, m in self.entropy_models.items():
-            self.entropy_model_optimizers[k] = None if m is None else torch.optim.Adam(
-                [{"params": p, "lr": 1e-4, "name": n} for n, p in m.named_parameters()])
-            self.entropy_model_schedulers[k] = None
+            opt, sch = (None, None) if m is None else self._entropy_optimizer(k, m)
+            self.entropy_model_optimizers[k], self.entropy_model_schedulers[k] = opt, sch
+
+    def _entropy_model(self, **kw) -> torch.nn.Module:
+        return Entropy_factorized_optimized_refactor(**kw)
+
+    def _entropy_optimizer(self, name: str, model: torch.nn.Module):
+        """-> (optimizer, scheduler) of one attribute's model; the factorized prior has no scheduler (simulation.py:119-141)."""
+        return torch.optim.Adam([{"params": p, "lr": 1e-4, "name": n} for n, p in model.named_parameters()]), None
 
     def _setup_ada_mask(self, ada_mask_opt: bool, ada_mask_step: int, strategy: Optional[str], kwargs: dict) -> None:
         """reference simulation.py:38-41, 151-168 (static) / 548-550, 611-620 (dynamic; always "learnable" there)."""
@@ -108,11 +117,14 @@ class _SimulationBase:
         value = out["output_value"]
         if estimate:
             x = value if as_channels is None else as_channels(value)
-            bits_est = self.entropy_models[name](x, out["q_step"])
+            bits_est = self._estimate_bits(name, x, out["q_step"])
             if act is not None:
                 value = torch.exp(value) if act == "exp" else torch.sigmoid(value)
             return value, bits_est
         return value, None
+
+    def _estimate_bits(self, name: str, x: Tensor, q_step) -> Tensor:
+        return self.entropy_models[name](x, q_step)
 
     def simulate_compression(self, splats: Dict[str, Tensor], step: int, activate: bool = False):
         """Returns (new_splats, esti_bits_dict); un-simulated attributes come back as ``p + 0.``
@@ -235,6 +247,68 @@ class CompressionSimulation(_SimulationBase):
     def shN_gradient_threshold(self, param: torch.nn.Parameter, step: int) -> None:
         """reference simulation.py:327-348 (the "gradient" strategy; edits ``param.grad`` in place)."""
         _shN_gradient_threshold(param.data, param.grad)
+
+
+class HashGridCompressionSimulation(CompressionSimulation):
+    """``CompressionSimulation`` with the position-conditioned Gaussian entropy model: the reference's
+    ``CompressionSimulation(entropy_model_type="gaussian_model")`` (simulation.py:99-149, 185-231).  scales, quats and sh0 get an
+    ``Entropy_gaussian`` with its two-group Adam and an exponential schedule; past ``entropy_min_step`` every call samples 5 % of
+    the splats inside the bounding box once and estimates the bits of the hooked attributes on that sample, conditioned on the
+    sampled means (which receive a gradient).  ``_estiblish_bbox(means)`` must have been called before (the reference's trainer
+    does so at simple_trainer.py:902-904); without it the reference fails with an AttributeError, here with a RuntimeError."""
+
+    _ENTROPY_MODEL_TYPE = "gaussian_model"
+
+    def __init__(self, entropy_model_enable: bool = False, entropy_steps: Optional[Dict[str, int]] = None, device=None,
+                 ada_mask_opt: bool = False, ada_mask_step: int = 10_000, ada_mask_strategy: Optional[str] = "learnable",
+                 **kwargs) -> None:
+        self.bbox_lower_bound = self.bbox_upper_bound = None
+        self._sample = None  # (mask [N] bool, means[mask]) of the call in flight
+        super().__init__(entropy_model_enable, "gaussian_model", entropy_steps, device, ada_mask_opt, ada_mask_step,
+                         ada_mask_strategy, **kwargs)
+
+    def _entropy_model(self, channel: int, **_) -> torch.nn.Module:
+        return Entropy_gaussian(channel=channel)
+
+    def _entropy_optimizer(self, name: str, model: torch.nn.Module):
+        opt = torch.optim.Adam([
+            {"params": model.param_regressor.hash_grid.parameters(), "lr": 5e-3, "name": "hash_grid"},
+            {"params": model.param_regressor.mlp_regressor.parameters(), "lr": 5e-3, "name": "mlp_regressor"}])
+        sch = torch.optim.lr_scheduler.ExponentialLR(opt, gamma=0.01 ** (1.0 / (30000 - self.entropy_steps.get(name, 0))))
+        return opt, sch
+
+    def _estiblish_bbox(self, pos: Tensor, k: float = 1.5) -> None:
+        """Per-axis 0.01 / 0.99 quantiles of the means (the reference's spelling; ``k`` is unused there too)."""
+        self.bbox_lower_bound, self.bbox_upper_bound = torch.quantile(pos, torch.tensor([0.01, 0.99], device=pos.device), dim=0)
+
+    def _get_pts_inside_bbox(self, pos: Tensor) -> Tensor:
+        return torch.all((pos >= self.bbox_lower_bound) & (pos <= self.bbox_upper_bound), dim=1)
+
+    def _random_sample_pts(self, mask: Tensor, ratio: float = 0.05) -> Tensor:
+        """The reference's torch calls in its order, so a seeded generator draws the same sample."""
+        random_values = torch.rand_like(mask.float())
+        random_values[~mask] = 0
+        threshold = torch.quantile(random_values[mask], 1 - ratio)
+        return random_values >= threshold
+
+    def _simulate(self, splats: Dict[str, Tensor], step: int):
+        self._sample = None
+        if self.entropy_model_enable and step > self.entropy_min_step:
+            if self.bbox_lower_bound is None:
+                raise RuntimeError("HashGridCompressionSimulation: no bounding box; call _estiblish_bbox(means) before the "
+                                   "first step past entropy_min_step")
+            mask = self._random_sample_pts(self._get_pts_inside_bbox(splats["means"]))
+            self._sample = (mask, splats["means"][mask])
+        try:
+            return super()._simulate(splats, step)
+        finally:
+            self._sample = None
+
+    def _estimate_bits(self, name: str, x: Tensor, q_step) -> Tensor:
+        if self._sample is None:  # (an entropy step of 0 is below entropy_min_step, the smallest POSITIVE one: the reference asserts)
+            raise RuntimeError(f"HashGridCompressionSimulation: {name} is past its entropy step but not past entropy_min_step")
+        mask, pos = self._sample
+        return self.entropy_models[name](x[mask], q_step, pos=pos)
 
 
 class STGCompressionSimulation(_SimulationBase):

@@ -50,7 +50,8 @@ extern "C" {
  * gs_stg_decode_partial_rows), and the appearance module's (gs_appearance_fwd / _bwd, gs_appearance_partial_rows,
  * gs_appearance_partial_cols), and the K-means entries (gs_kmeans_padded_width, gs_kmeans_default_slices, gs_kmeans_assign,
  * gs_kmeans_update), and the nearest-neighbour entries (gs_knn_cells, gs_knn_finish_grid, gs_knn_search), and the
- * PLY entries (gs_ply_unpack, gs_ply_pack, gs_ply_max_stride, gs_ply_max_columns, gs_ply_block_rows). */
+ * PLY entries (gs_ply_unpack, gs_ply_pack, gs_ply_max_stride, gs_ply_max_columns, gs_ply_block_rows), and the hash-grid Gaussian entropy model's (gs_hashgrid_encode_fwd / _bwd,
+ * gs_gaussian_bits_fwd / _bwd). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -752,6 +753,53 @@ int32_t gs_entropy_factorized_bwd(
     uint64_t n_rows, uint32_t channels, uint32_t hidden_layers, uint32_t hidden_width,
     const float *x, const float *half_q, const float *params, float likelihood_bound,
     const float *v_bits, float *v_x, float *v_params, uint32_t replicas, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Hash-grid Gaussian entropy model (the reference trainer's `--entropy_model_type gaussian_model`).
+ * gs_hashgrid_encode_*: replaces the reference's CUDA-only `_gridencoder` extension (third_party/gridencoder/src/
+ * gridencoder.cu kernel_grid / kernel_grid_backward / kernel_input_backward, driven by
+ * gsplat/compression_simulation/gaussian_distribution_model.py:56-346), float32 only, for 1..4 grids in ONE launch:
+ * grid g has its own raw table params[g] [rows[g], n_features], num_dim[g] in {2, 3}, an axis selector axes[g]
+ * (which columns of pos are its coordinates: 0 = xyz, 1 = xy, 2 = xz, 3 = yz) and n_levels[g] levels whose resolutions / offsets
+ * (n_levels[g] / n_levels[g] + 1 entries) follow each other in the two concatenated lists.  params, v_params, rows,
+ * num_dim, axes, n_levels, resolutions and offsets are HOST arrays (params / v_params: host arrays of device pointers);
+ * pos [n, pos_dim] (pos_dim 3, or 2 for a lone xy grid), out / v_out [n, sum(n_levels) * n_features] row-major in the
+ * order of the grids and their levels (the reference's [L, N, F] buffer and its permute do not exist), v_pos [n, pos_dim].
+ * Per (point, level), with R the resolution and T = offsets[l+1] - offsets[l]: a coordinate outside [0, 1] or NaN gives 0
+ * outputs and no gradient (the reference lets NaN through); p = u * float(R - 2) + 0.5f in two float32 roundings,
+ * g = floor(p), f = p - g; corner i has c[d] = g[d] or min(g[d] + 1, R - 1) (bit d of i) and weight prod(bit ? f : 1 - f); a
+ * corner with any c[d] in {0, R - 1} takes no part; row = (dense index while the stride fits T, else xor of
+ * c[d] * {1, 2654435761, 805459861}) % T, so every access is inside the level's slice; out = sum w / wn * E[row] with wn the
+ * participating weights' sum (1e-9 if 0).  ste_binary != 0: E = (p >= 0) - (p < 0) of the raw parameter (STE_binary, 0
+ * for NaN), and the table gradient passes where -1 <= p <= 1; ste_binary == 0: E = p.
+ * bwd: v_params[g] is ACCUMULATED with float atomics (zero-fill first); v_pos is OVERWRITTEN with the reference's dy_dx
+ * formula (finite differences of the corner values, a border corner counting as 0, wn not entering) summed over all grids
+ * and levels by one owner per point -- no atomics, bit-identical from run to run.  v_params (or single entries of it) and
+ * v_pos may be NULL: that gradient is skipped.  n_features in {1, 2, 4}, at most 32 levels in total, R in 3..2^24, offsets
+ * ascending from >= 0 with offsets[last] <= rows, tables / out / v_out aligned to n_features floats; anything else:
+ * status 1 and nothing is written.  n == 0 launches nothing.
+ * gs_gaussian_bits_*: Entropy_gaussian.forward's likelihood (entropy_model.py:327-338) in one elementwise launch each
+ * way.  x, bits, v_bits, v_x [n_rows, channels]; net, v_net [n_rows, 2 channels] = the regressor's output (means in columns
+ * 0..C-1, raw scales in C..2C-1, read in place); half_q [channels] device floats (= Q/2).  s = max(scale, 1e-9),
+ * like = |Phi((x + hq - m) / s) - Phi((x - hq - m) / s)| (erfc differences on the side where both are small: the tails keep
+ * their relative accuracy), bits = -log2(max(bound, like)).  bwd OVERWRITES v_x and v_net: LowerBound rule (passes where
+ * like >= bound or the likelihood's incoming gradient is negative), sign of the abs, clamp gate (scale >= 1e-9).
+ * channels in 1..32; anything else, or a null pointer: status 1. */
+int32_t gs_hashgrid_encode_fwd(
+    uint64_t n, uint32_t pos_dim, uint32_t n_grids, uint32_t n_features, uint32_t ste_binary, const float *pos,
+    const float *const *params, const uint64_t *rows, const uint32_t *num_dim, const uint32_t *axes,
+    const uint32_t *n_levels, const int32_t *resolutions, const int32_t *offsets, float *out, gs_stream_t stream);
+int32_t gs_hashgrid_encode_bwd(
+    uint64_t n, uint32_t pos_dim, uint32_t n_grids, uint32_t n_features, uint32_t ste_binary, const float *pos,
+    const float *const *params, const uint64_t *rows, const uint32_t *num_dim, const uint32_t *axes,
+    const uint32_t *n_levels, const int32_t *resolutions, const int32_t *offsets, const float *v_out,
+    float *const *v_params, float *v_pos, gs_stream_t stream);
+int32_t gs_gaussian_bits_fwd(
+    uint64_t n_rows, uint32_t channels, const float *x, const float *net, const float *half_q, float likelihood_bound,
+    float *bits, gs_stream_t stream);
+int32_t gs_gaussian_bits_bwd(
+    uint64_t n_rows, uint32_t channels, const float *x, const float *net, const float *half_q, float likelihood_bound,
+    const float *v_bits, float *v_x, float *v_net, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Unfused public ops (reference: quat_scale_to_covar_preci_{fwd,bwd}.cu,
