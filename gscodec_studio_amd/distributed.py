@@ -741,8 +741,16 @@ class SparseGradPlan:
     def __init__(self, N, world, rank, block, masks, union, send_idx, urank, uidx, pinned, event):
         self.N, self.world, self.rank, self.block = N, world, rank, block
         self.masks, self.union = masks, union  # uint8 [world, world * block], bool [world * block]
-        # int32: my visible splats in ascending order (-1 padded) [world * block]; position of every splat of MY block inside
-        # the block's union [block]; the global indices of my block's union rows, ascending (-1 padded) [block]
+        # int32, all GLOBAL and of length n_pad = world * block, the same on every rank but for send_idx:
+        #   send_idx  my visible splats in ascending order; entries behind my row count (sum(rows[rank])) are undefined
+        #             (the torch route pads with -1, gs_dp_plan leaves them unwritten)
+        #   uidx      the splats of the union of ALL ranks' masks in ascending order, so owner o's union rows are the slice
+        #             [uoff, uoff + urows[o]) with uoff = sum(urows[:o]); entries behind sum(urows) are undefined (-1 / unwritten)
+        #   urank     urank[n] = position of splat n in uidx; an owner's accumulator row is urank[n] - uoff.  Defined on union
+        #             splats ONLY: off the union the torch route holds cumsum(union) - 1 (the rank of the last union splat in
+        #             front, -1 in front of the first), gs_dp_plan writes nothing -- nothing may read it there (wire rows carry
+        #             indices of visible splats only)
+        # masks is uint8 [world, n_pad]; union is bool [n_pad] on the torch route and None on the native one.
         self.send_idx, self.urank, self.uidx = send_idx, urank, uidx
         self._pinned, self._event = pinned, event
         self._counts = None

@@ -290,3 +290,44 @@ def _sparse_grad_reduce(rank, world):
 
 def test_sparse_splat_grad_reduction_world2():
     _run("_sparse_grad_reduce")
+
+
+# --------------------------------------------------------------------------- the numpy restatements of exchange_reference.py
+def _exchange_restatements(rank, world):
+    """The torch formulations of distributed.py (the CPU / gloo route of plan_sparse_grad_exchange and _reduce_received_rows)
+    against tests/exchange_reference.py (run by tests/test_exchange_cpu.py at world 2 and 3): the restatements the HIP kernels
+    are compared with bit for bit (tests/test_gpu_exchange.py) state what the library's own plain formulation computes."""
+    import numpy as np
+
+    import exchange_reference as XR
+    from gscodec_studio_amd import distributed as D
+
+    for variant in XR.PLAN_VARIANTS:
+        N = 2999
+        block = -(-N // world)
+        m = XR.plan_masks(world, block, variant)
+        XR.check_plan_masks(m, world, block, variant)
+        m[:, N:] = 0                                                  # (padding: seen by nobody)
+        radii = torch.stack([torch.from_numpy(m[rank, :N].astype(np.int32)) * 3,           # camera 0 sees the mask,
+                             -torch.from_numpy((m[(rank + 1) % world, :N] != 0).astype(np.int32))])  # camera 1 nothing (0 / -1)
+        assert np.array_equal(XR.visibility(radii.numpy(), world * block), m[rank])
+        plan = D.plan_sparse_grad_exchange(radii, world)
+        assert plan.block == block and np.array_equal(plan.masks.numpy(), m)
+        ref = XR.plan(plan.masks.numpy(), block)
+        rows, urows = plan.counts()
+        assert np.array_equal(np.asarray(rows + [urows]).reshape(-1), ref.counts)
+        mine, U = int(ref.rows[rank].sum()), int(ref.urows.sum())
+        assert np.array_equal(plan.send_idx[:mine].numpy(), ref.send_idx[rank])
+        assert np.array_equal(plan.uidx[:U].numpy(), ref.uidx)
+        assert np.array_equal(plan.urank.numpy()[ref.union], ref.urank[ref.union])
+    for width, umax in ((59, 5), (65, 300), (1, 1)):
+        owner = rank
+        p, wire, starts, uoff, uidx_mine = XR.reduce_inputs(world, width, umax, owner)
+        XR.check_reduce_inputs(world, owner, p, wire, starts, uoff, uidx_mine, umax)
+        for scale in (1.0, 1.0 / world):
+            want = XR.reduce_rows(wire, starts, p.urank, uoff, uidx_mine, umax, scale)
+            got = D._reduce_received_rows(torch.from_numpy(wire), [int(c) for c in np.diff(starts)], torch.from_numpy(p.urank), uoff,
+                                          torch.from_numpy(uidx_mine), umax, scale)
+            assert np.array_equal(got[:, 0].contiguous().view(torch.int32).numpy(), want[:, 0].copy().view(np.int32))
+            # (index_add_ fixes no order of the additions: close, not equal)
+            assert torch.allclose(got[:, 1:], torch.from_numpy(want[:, 1:]), atol=1e-6)
