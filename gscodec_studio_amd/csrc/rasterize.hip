@@ -193,8 +193,8 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_fwd_kernel(RasterArgs a, 
 template <int CDIM, bool CKPT>
 __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_tile_fwd_kernel(RasterArgs a, float *__restrict__ ckpt, int32_t seg, int32_t solo_min,
                                                               uint32_t *__restrict__ cost_head, uint32_t *__restrict__ cost_body,
-                                                              uint32_t *__restrict__ body_tile, uint32_t *__restrict__ class_count,
-                                                              ZeroFill zf, uint32_t ch_off, uint32_t cnt) {
+                                                              uint32_t *__restrict__ body_tile, int32_t *__restrict__ tile_last,
+                                                              uint32_t *__restrict__ class_count, ZeroFill zf, uint32_t ch_off, uint32_t cnt) {
     constexpr bool WIDE = CDIM > 4;
     constexpr int NCW = WIDE ? (CDIM - 2 + 3) / 4 : 0; // float4s of colours 2.. behind R0, R1
     constexpr int REC = WIDE ? 2 + NCW : 3;
@@ -540,14 +540,22 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
         if (NBUF == 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // nobody restages while a wave still walks this batch
     }
 
+    // The quadrant's last contributor: the maximum the backward takes over the same 64 last_ids (q_bin_max, -1 outside the image).
+    // tile_last[tile][wave], stored like the costs; seg_items_build_kernel drops the segments behind the maximum of the four.
+    const int32_t wave_last = __builtin_amdgcn_readfirstlane(wave_max_i32(inside ? cur : -1));
     if (CKPT && n > 0) {
-        // boundaries after the last composited record (or after an early exit) carry the final state
+        // boundaries after the last composited record (or after an early exit) carry the final state.  The backward restores a
+        // quadrant from checkpoint k only in a segment k - 1 that holds one of the quadrant's contributors (q_live), so the planes
+        // of the boundaries further back are not written: nobody reads this wave's quarter of them.  Their costs still are (the
+        // build kernel's staleness check of body_tile depends on every boundary being reported in every call).
         while (ck.next_b < tg.range_end) {
-            store_ckpt();
+            if (ck.next_b - seg <= wave_last) store_ckpt();
+            else store_cost();
             ck.advance(seg);
         }
         store_cost(); // the tile's last segment
     }
+    if (CKPT && cost_owner && lane == 0) tile_last[tg.lin * 4u + w] = wave_last;
     if (inside) store_pixel<CDIM>(a, p.pix, CH, ch0, nch, cost_owner, T, out, cur, bg);
     zero_fill_slice();
 }
@@ -616,9 +624,9 @@ template <int CDIM>
 void launch_tile_fwd(const RasterArgs &a, const RasterScratch &v, int32_t solo_min, ZeroFill zf, hipStream_t st, uint32_t ch_off, uint32_t cnt) {
     dim3 grid(a.C * a.tile_width * a.tile_height);
     if (v.ckpt != nullptr)
-        hipLaunchKernelGGL((raster_tile_fwd_kernel<CDIM, true>), grid, dim3(256), 0, st, a, v.ckpt, v.seg, solo_min, v.cost_head, v.cost_body, v.body_tile, v.class_count, zf, ch_off, cnt);
+        hipLaunchKernelGGL((raster_tile_fwd_kernel<CDIM, true>), grid, dim3(256), 0, st, a, v.ckpt, v.seg, solo_min, v.cost_head, v.cost_body, v.body_tile, v.tile_last, v.class_count, zf, ch_off, cnt);
     else
-        hipLaunchKernelGGL((raster_tile_fwd_kernel<CDIM, false>), grid, dim3(256), 0, st, a, v.ckpt, v.seg, solo_min, v.cost_head, v.cost_body, v.body_tile, v.class_count, zf, ch_off, cnt);
+        hipLaunchKernelGGL((raster_tile_fwd_kernel<CDIM, false>), grid, dim3(256), 0, st, a, v.ckpt, v.seg, solo_min, v.cost_head, v.cost_body, v.body_tile, v.tile_last, v.class_count, zf, ch_off, cnt);
 }
 
 // ---------------------------------------------------------------------------
@@ -1040,21 +1048,34 @@ void launch_bwd_seg(const RasterArgs &a, const RasterGradArgs &ga, int use_va, c
 // kernel, inside gs_rasterize_fwd: the backward itself is ONE launch, and a repeated backward (retain_graph) reuses it.
 //   unit u < n_tiles_all           : the first segment of tile u
 //   unit u = n_tiles_all + k       : segment k of the tile that owns list boundary k * seg (body_tile[k], verified)
+// A unit whose segment lies behind its tile's last contributor (tile_last, reported by the forward) is no item: 27 % of the
+// units of BASELINE config 2, whose waves used to load their pixel state and leave (profiles/r25_dead_segments.txt).
+// item = (tile, k, end, -): the walk covers list entries [max(range_start, k * seg), end).
 __global__ void __launch_bounds__(GS_BLOCK) seg_items_build_kernel(uint32_t n_tiles_all, uint32_t n_isects, const int32_t *__restrict__ offsets,
                                                                    const uint8_t *__restrict__ masks, int32_t seg, uint32_t n_bounds,
                                                                    const uint32_t *__restrict__ cost_head, const uint32_t *__restrict__ cost_body,
-                                                                   const uint32_t *__restrict__ body_tile, uint32_t *__restrict__ class_count,
-                                                                   uint2 *__restrict__ items, uint32_t max_items) {
+                                                                   const uint32_t *__restrict__ body_tile, const int32_t *__restrict__ tile_last,
+                                                                   uint32_t *__restrict__ class_count, uint4 *__restrict__ items, uint32_t max_items) {
     __shared__ uint32_t s_cnt[COST_CLASSES], s_base[COST_CLASSES];
     if (threadIdx.x < COST_CLASSES) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t u = blockIdx.x * GS_BLOCK + threadIdx.x;
     uint32_t tile = 0, cls = 0, local = 0;
-    int32_t k = 0;
+    int32_t k = 0, end = 0;
     bool valid = false;
     auto range = [&](uint32_t t, int32_t &rs, int32_t &re) {
         rs = offsets[t];
         re = (t + 1 == n_tiles_all) ? (int32_t)n_isects : offsets[t + 1];
+    };
+    // Segment k of tile t (list [rs, re), segment start `start`) is an item only if the tile's last contributor (the maximum of
+    // its four waves' tile_last = of its 256 last_ids) lies at or behind the segment's start: otherwise the backward's own test
+    // q_bin_max[i] >= range_start fails for all four quadrants.  The item ends at the segment's end or right behind that last
+    // contributor, whichever comes first.
+    auto live = [&](uint32_t t, int32_t start, int32_t re) {
+        const int4 l = reinterpret_cast<const int4 *>(tile_last)[t];
+        const int32_t last = max(max(l.x, l.y), max(l.z, l.w));
+        end = (int32_t)min(min((int64_t)re, ((int64_t)k + 1) * seg), (int64_t)last + 1);
+        return last >= start;
     };
     if (u < n_tiles_all) {
         int32_t rs, re;
@@ -1062,6 +1083,7 @@ __global__ void __launch_bounds__(GS_BLOCK) seg_items_build_kernel(uint32_t n_ti
         valid = re > rs && (masks == nullptr || masks[u]);
         tile = u;
         k = rs / seg;
+        valid = valid && live(u, rs, re);
         if (valid) {
             const uint4 c = reinterpret_cast<const uint4 *>(cost_head)[u];
             cls = cost_class(c.x + c.y + c.z + c.w, seg);
@@ -1074,6 +1096,7 @@ __global__ void __launch_bounds__(GS_BLOCK) seg_items_build_kernel(uint32_t n_ti
             range(t, rs, re);
             valid = (int64_t)rs < (int64_t)k * seg && (int64_t)k * seg < (int64_t)re && (masks == nullptr || masks[t]);
             tile = t;
+            valid = valid && live(t, k * seg, re);
             if (valid) {
                 const uint4 c = reinterpret_cast<const uint4 *>(cost_body)[k];
                 cls = cost_class(c.x + c.y + c.z + c.w, seg);
@@ -1087,7 +1110,7 @@ __global__ void __launch_bounds__(GS_BLOCK) seg_items_build_kernel(uint32_t n_ti
         s_base[threadIdx.x] = c ? atomicAdd(&class_count[threadIdx.x], c) : 0u;
     }
     __syncthreads();
-    if (valid) items[(size_t)cls * max_items + s_base[cls] + local] = make_uint2(tile, (uint32_t)k);
+    if (valid) items[(size_t)cls * max_items + s_base[cls] + local] = make_uint4(tile, (uint32_t)k, (uint32_t)end, 0u);
 }
 
 
@@ -1160,7 +1183,7 @@ RasterRoute raster_route_bwd(uint32_t channels, const gs_raster_plan *plan, cons
 // The scratch of plan `p` as typed pointers (scratch == NULL: all NULL; the sizes hold either way)
 RasterScratch scratch_view(const gs_raster_plan &p, void *scratch) {
     const bool ckpt = plan_has_ckpt(p), tile = raster_route_fwd(p.channels, &p) != RasterRoute::WAVE_GENERIC;
-    size_t o = 256; // [0, 256): the class counters + padding; then the regions in this order, each padded to 256 bytes
+    size_t o = 256; // [0, 256): the class counters + padding; then the regions in this order, each padded to 256 bytes (tile_last: 16-byte loads)
     auto take = [&](bool on, size_t bytes) -> void * {
         void *r = (on && scratch != nullptr) ? (char *)scratch + o : nullptr;
         if (on) o += (bytes + 255) & ~(size_t)255;
@@ -1171,11 +1194,12 @@ RasterScratch scratch_view(const gs_raster_plan &p, void *scratch) {
     v.n_bounds = (ckpt ? p.n_isects / (uint32_t)p.seg : 0u) + 2u;
     v.max_items = p.n_tiles_all + v.n_bounds;
     v.class_count = (ckpt && scratch != nullptr) ? (uint32_t *)scratch : nullptr;
-    v.items = (uint2 *)take(ckpt, (size_t)COST_CLASSES * v.max_items * sizeof(uint2));
+    v.items = (uint4 *)take(ckpt, (size_t)COST_CLASSES * v.max_items * sizeof(uint4));
     v.cost_head = (uint32_t *)take(true, (size_t)p.n_tiles_all * 4 * sizeof(uint32_t)); // (a region of every layout)
     if (!ckpt) v.cost_head = nullptr;
     v.cost_body = (uint32_t *)take(ckpt, (size_t)v.n_bounds * 4 * sizeof(uint32_t));
     v.body_tile = (uint32_t *)take(ckpt, (size_t)v.n_bounds * sizeof(uint32_t));
+    v.tile_last = (int32_t *)take(ckpt, (size_t)p.n_tiles_all * 4 * sizeof(int32_t));
     v.ckpt = (float *)take(ckpt, (size_t)v.n_bounds * (p.channels + 1) * 256 * sizeof(float));
     v.tile_order = (uint32_t *)take(tile, (size_t)p.n_tiles_all * sizeof(uint32_t)); // heaviest lists first (tile_order_kernel)
     if (p.reserved[0] == 0u || p.n_tiles_all == 0u) v.tile_order = nullptr;
@@ -1277,7 +1301,7 @@ int32_t raster_dispatch_fwd(const RasterArgs &a_in, const gs_raster_plan *plan, 
     }
     if (v.ckpt != nullptr) // the backward's work list, ordered by the costs just counted
         hipLaunchKernelGGL(seg_items_build_kernel, dim3(gs_div_up(v.max_items, GS_BLOCK)), dim3(GS_BLOCK), 0, st, n_tiles_all, a.n_isects,
-                           a.tile_offsets, a.masks, v.seg, v.n_bounds, v.cost_head, v.cost_body, v.body_tile, v.class_count, v.items, v.max_items);
+                           a.tile_offsets, a.masks, v.seg, v.n_bounds, v.cost_head, v.cost_body, v.body_tile, v.tile_last, v.class_count, v.items, v.max_items);
     return 0;
 }
 

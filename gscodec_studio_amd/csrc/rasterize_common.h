@@ -102,8 +102,9 @@ enum class RasterRoute { TILE_NARROW, TILE_WIDE, WAVE_GENERIC };
 // no use for (no scratch, no segments, more channels than the tile kernels cover) is NULL.
 struct RasterScratch {
     uint32_t *class_count;                      // [COST_CLASSES] work items per cost class
-    uint2 *items;                               // [COST_CLASSES][max_items] (tile, k), the segmented backward's work list
+    uint4 *items;                               // [COST_CLASSES][max_items] (tile, k, end, -), the segmented backward's work list
     uint32_t *cost_head, *cost_body, *body_tile; // [tile][4], [boundary][4] costs counted by the forward; [boundary] owner tile
+    int32_t *tile_last;                         // [tile][4] the last contributor of each quadrant wave (maximum of its last_ids)
     float *ckpt;                                // [boundary][channels + 1][256] forward checkpoints
     uint32_t *tile_order;                       // [tile] the forward's tile order (NULL: unordered)
     uint32_t max_items, n_bounds;               // length of an item region; list boundaries k * seg, k < n_bounds

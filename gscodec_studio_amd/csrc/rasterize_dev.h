@@ -342,7 +342,7 @@ GS_DEV void store_pixel(const RasterArgs &a, size_t pix, uint32_t channels, uint
 
 // the segmented backward's work list (built by seg_items_build_kernel inside gs_rasterize_fwd) and the forward's checkpoints
 struct SegArgs {
-    const uint2 *items;          // [COST_CLASSES][max_items] (tile, k), one region per cost class
+    const uint4 *items;          // [COST_CLASSES][max_items] (tile, k, end, -), one region per cost class
     const uint32_t *class_count; // [COST_CLASSES] items per class
     uint32_t max_items;          // region length
     const float *ckpt;           // [k][CDIM+1][256]

@@ -30,6 +30,9 @@ struct ChanWindow {
 // Block index -> item: the classes in order of decreasing cost (the grid is an upper bound on the total).  False: nothing to do
 // (behind the last item, or a masked tile).  tg comes back with its range clamped to the segment; from_ckpt: the segment ends
 // in front of the tile's list end, i.e. the state at its far end is the forward's checkpoint seg_k + 1.
+// The item carries its own end (it.z): the segment's, or, in the tile's last live segment, the entry behind the tile's last
+// contributor -- everything behind that fails `my_idx <= q_bin_max[i]` in every quadrant (seg_stage), so the walk starts
+// there, the state at the far end being the same as before (from_ckpt is taken from the unclamped segment).
 GS_DEV bool seg_item(const RasterArgs &a, const SegArgs &sg, TileGeom &tg, int32_t &seg_k, bool &from_ckpt) {
     uint32_t n_work = 0;
 #pragma unroll 8
@@ -42,14 +45,13 @@ GS_DEV bool seg_item(const RasterArgs &a, const SegArgs &sg, TileGeom &tg, int32
         if (r < nc) break;
         r -= nc;
     }
-    const uint2 it = sg.items[(size_t)cls * sg.max_items + r];
+    const uint4 it = sg.items[(size_t)cls * sg.max_items + r];
     seg_k = (int32_t)it.y;
     tg = tile_geom(a, it.x);
     if (a.masks != nullptr && !a.masks[tg.lin]) return false;
-    const int32_t tile_end = tg.range_end;
+    from_ckpt = (seg_k + 1) * sg.seg < tg.range_end;
     tg.range_start = max(tg.range_start, seg_k * sg.seg);
-    tg.range_end = min(tg.range_end, (seg_k + 1) * sg.seg);
-    from_ckpt = tg.range_end < tile_end;
+    tg.range_end = (int32_t)it.z;
     return true;
 }
 
@@ -81,7 +83,8 @@ struct SegPixels {
 
 // The state at the far end of segment seg_k of tile tg: the final render, or (from_ckpt) the forward's checkpoint seg_k + 1
 // (T, accumulated colour): B = v_out . (colour_final - colour_ckpt).  q_live == 0 afterwards: nothing was composited in this
-// segment for any pixel.
+// segment for any pixel.  (The forward writes a quadrant's quarter of checkpoint seg_k + 1 only if the quadrant has a contributor
+// at or behind the segment's start: a quadrant without its q_live bit may hold stale T / Wq here, which nothing reads.)
 template <int CDIM, class Chan>
 GS_DEV void seg_pixels_init(const RasterArgs &a, const RasterGradArgs &ga, int use_v_alpha, const SegArgs &sg, const TileGeom &tg,
                             int32_t seg_k, bool from_ckpt, const Chan &ch, uint32_t lane, SegPixels<CDIM> &p) {
