@@ -30,10 +30,15 @@
   directory, with the scales and the quats rANS-coded on the GPU by ``ans`` (csrc/ans.hip: histogram, lane-per-stream encode,
   pack, decode).  The reference takes its coder from the ``constriction`` package; the bitstream here is this project's own,
   defined by the numpy coder ``ans_reference`` that the kernels match byte for byte.
+* ``gauss_ans``: the hash-grid Gaussian route of the same class (``_compress_gaussian_ans``, chosen through the registry): every
+  symbol coded against the Gaussian that the trained ``Entropy_gaussian`` predicts at the splat's position (csrc/gauss_ans.hip:
+  the regressor's MLP in one stated float32 order, lane-per-stream encode and decode at 16-bit resolution), with the reference's
+  model files and meta keys around a bitstream defined by the numpy coder ``gauss_ans_reference``.
 """
 from .decode import decode_to_dynamic_inputs, decode_to_rasterizer_inputs, kmeans_decode, kmeans_encode, morton_order, reorder_splats, sort_splats
 from .png_compression import PngCompression, png_read, png_write
 from .ans import ans_decode, ans_encode, normalize_frequencies, symbol_histogram
+from .gauss_ans import gauss_ans_decode, gauss_ans_encode, gaussian_params
 from .entropy_coding_compression import EntropyCodingCompression
 from .stg_compression import STGPngCompression
 from .grid_sort import grid_sort_order, sort_splats_grid
@@ -51,4 +56,4 @@ __all__ = ["quantize_grid", "dequantize_grid", "compress_to_arrays", "decompress
            "inverse_log_transform", "decode_to_rasterizer_inputs", "kmeans_decode", "kmeans_encode", "morton_order",
            "sort_splats", "reorder_splats", "PngCompression", "png_read", "png_write", "EntropyCodingCompression", "ans_encode",
            "ans_decode", "normalize_frequencies", "symbol_histogram", "grid_sort_order", "sort_splats_grid", "STGPngCompression",
-           "decode_to_dynamic_inputs", "KMeans", "kmeans_fit"]
+           "decode_to_dynamic_inputs", "KMeans", "kmeans_fit", "gaussian_params", "gauss_ans_encode", "gauss_ans_decode"]

@@ -4,17 +4,25 @@
     meta.json                      one entry per attribute: shape, dtype, mins, maxs (plus what K-means adds)
     means_l.png, means_u.png       low / high byte of the 16-bit grid of the log-transformed means
     opacities.png, sh0.png         plain 8-bit grids
-    scales.bin, quats.bin          the rANS-coded 8-bit symbols, one categorical model per channel
-    scales_prob.npy, quats_prob.npy   the float32 [C, 256] symbol probabilities the coder's tables are derived from
+    scales.bin, quats.bin          the rANS-coded 8-bit symbols
+    scales_prob.npy, quats_prob.npy   factorized route: the float32 [C, 256] symbol probabilities the coder's tables are derived from
+    <name>_entropy_model_encoding_{xyz,xy,xz,yz}.bin, <name>_entropy_model_mlp.ckpt
+                                   hash-grid Gaussian route: the model that predicts a Gaussian per splat and channel from the
+                                   splat's position -- the signs of the four hash tables, one bit each, and the regressor's MLP
     shN.npz, mask.bin              masked K-means codebook, as PngCompression writes it
     <other>.npz                    anything else, under the key "arr"
 
-Every file but the two ``.bin`` is what the reference writes and is read by either implementation.  The ``.bin`` payload is
-this project's own bitstream (``ans_reference`` defines it, csrc/ans.hip codes it on the GPU): the reference takes its coder
-from the ``constriction`` package, whose stream cannot be reproduced without it.  ``decompress`` says so when it meets one.
+Every file but ``<name>.bin`` is what the reference writes and is read by either implementation.  The ``.bin`` payload of BOTH
+routes is this project's own bitstream (``ans_reference`` / ``gauss_ans_reference`` define them, csrc/ans.hip and
+csrc/gauss_ans.hip code them on the GPU): the reference takes its coder from the ``constriction`` package, whose stream cannot be
+reproduced without it.  ``decompress`` says so when it meets one.
 
 Like the reference's ``_compress_factorized_ans`` (328-395) the factorized coder does not read the entropy model it is handed: it
-codes against the empirical histogram of the symbols.  The hash-grid Gaussian codec (``_compress_gaussian_ans``) is not built.
+codes against the empirical histogram of the symbols.  The hash-grid Gaussian route (``_compress_gaussian_ans``, 448-654; chosen
+through ``attribute_codec_registry``) spends the trained ``Entropy_gaussian``: every symbol is coded against the Gaussian the model
+predicts at the splat's DECODED position -- ``compress`` reads the means back from the PNG files it has just written, so that both
+sides hand the model the same float32 positions bit for bit -- and the model itself is evaluated by ``gs_gauss_ans_params`` in one
+stated float32 order, so that both sides also get the same integers out of it.
 
 Constant channels: where ``maxs == mins`` the reference divides 0 by 0; here such a channel gets symbol 0 everywhere and decodes
 to ``mins``.
@@ -30,13 +38,14 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from . import gauss_ans_reference as GR
 from .ans import ans_decode, ans_encode, probabilities, symbol_histogram
+from .gauss_ans import check_entropy_model, gauss_ans_decode, gauss_ans_encode, gaussian_params
 from .grid_codec import dequantize_grid, inverse_log_transform, quantize_grid
 from .png_compression import (_meta_of, compress_masked_kmeans, decompress_masked_kmeans, png_read, png_write,
                               prepare_splats)
 
-_GAUSSIAN = ("the hash-grid Gaussian codec is not built: only the factorized prior is (the hash-grid Gaussian "
-             "model depends on the reference's CUDA-only _gridencoder extension)")
+_ENCODINGS = ("encoding_xyz", "encoding_xy", "encoding_xz", "encoding_yz")
 
 
 def _compress_png_16bit(compress_dir: str, param_name: str, params: Tensor, n_sidelen: int, **kwargs) -> Dict[str, Any]:
@@ -84,12 +93,77 @@ def _decompress_factorized_ans(compress_dir: str, param_name: str, meta: Dict[st
     return dequantize_grid([symbols], meta, device=device)
 
 
-def _compress_gaussian_ans(*args, **kwargs):
-    raise NotImplementedError(f"_compress_gaussian_ans: {_GAUSSIAN}")
+def save_gaussian_entropy_model(param_name: str, entropy_model: torch.nn.Module, compress_dir: str) -> Dict[str, Any]:
+    """467-489: the hash tables as ``STE_binary`` leaves them, one bit per entry, LSB first (``to_bin_stream``'s bytes, without
+    its Python loop), and ``mlp_regressor.state_dict()``; returns the ``encoding_*_shape`` entries of the meta."""
+    check_entropy_model(entropy_model)
+    pr = entropy_model.param_regressor
+    meta: Dict[str, Any] = {}
+    for enc_name in _ENCODINGS:
+        params = getattr(pr.hash_grid, enc_name).params.detach()
+        if bool(torch.isnan(params).any()):
+            raise ValueError(f"{enc_name} of the entropy model of {param_name} holds a NaN: its sign is 0, which the one-bit file cannot hold")
+        meta[f"{enc_name}_shape"] = list(params.shape)
+        GR.pack_signs(np.where(params.cpu().numpy().reshape(-1) >= 0, 1, -1)).tofile(
+            os.path.join(compress_dir, f"{param_name}_entropy_model_{enc_name}.bin"))
+    torch.save({k: v.detach().cpu() for k, v in pr.mlp_regressor.state_dict().items()},
+               os.path.join(compress_dir, f"{param_name}_entropy_model_mlp.ckpt"))
+    return meta
 
 
-def _decompress_gaussian_ans(*args, **kwargs):
-    raise NotImplementedError(f"_decompress_gaussian_ans: {_GAUSSIAN}")
+def load_gaussian_entropy_model(compress_dir: str, param_name: str, meta: Dict[str, Any], device="cuda") -> torch.nn.Module:
+    """602-620: a fresh ``Entropy_gaussian`` with the stored signs as its tables and the stored MLP (``strict=True``)."""
+    from ..compression_simulation.entropy_model import Entropy_gaussian
+
+    entropy_model = Entropy_gaussian(channel=meta["shape"][-1])
+    pr = entropy_model.param_regressor
+    state = torch.load(os.path.join(compress_dir, f"{param_name}_entropy_model_mlp.ckpt"), map_location="cpu", weights_only=True)
+    pr.mlp_regressor.load_state_dict(state, strict=True)
+    for enc_name in _ENCODINGS:
+        shape = [int(v) for v in meta[f"{enc_name}_shape"]]
+        enc = getattr(pr.hash_grid, enc_name)
+        if shape != list(enc.params.shape):
+            raise ValueError(f"{param_name}: {enc_name}_shape {shape} in meta.json, the model's table is {list(enc.params.shape)}")
+        data = np.fromfile(os.path.join(compress_dir, f"{param_name}_entropy_model_{enc_name}.bin"), dtype=np.uint8)
+        enc.params.data = torch.from_numpy(GR.unpack_signs(data, int(np.prod(shape))).reshape(shape))
+    return entropy_model.to(device)
+
+
+def _compress_gaussian_ans(compress_dir: str, param_name: str, params: Tensor, n_sidelen: int, entropy_model=None,
+                           decoded_means: Optional[Tensor] = None, stream_len: int = 1024, **kwargs) -> Dict[str, Any]:
+    """491-568: the model's files, then the same 8-bit min-max symbols as the factorized route, each coded against the Gaussian
+    the model predicts at the splat's decoded position (``gauss_ans``).  Meta: ``encoding_*_shape``, shape, dtype, mins, maxs."""
+    if entropy_model is None:
+        raise NotImplementedError(
+            f"_compress_gaussian_ans: the hash-grid Gaussian codec codes {param_name} against its trained Entropy_gaussian, and "
+            f"entropy_models holds no model for {param_name}: pass the simulation's entropy_models, or keep the factorized route")
+    if decoded_means is None:
+        raise ValueError(f"_compress_gaussian_ans: {param_name} needs the decoded means (compress() hands them over)")
+    meta = save_gaussian_entropy_model(param_name, entropy_model, compress_dir)
+    (plane,), q_meta = quantize_grid(params, n_sidelen, bits=8)
+    symbols = plane.reshape(params.shape[0], -1)
+    mu_q, k = gaussian_params(entropy_model, decoded_means.to(symbols.device), q_meta["mins"], q_meta["maxs"])
+    gauss_ans_encode(symbols, mu_q, k, stream_len=stream_len).tofile(os.path.join(compress_dir, f"{param_name}.bin"))
+    meta.update(q_meta)
+    return meta
+
+
+def _decompress_gaussian_ans(compress_dir: str, param_name: str, meta: Dict[str, Any], decoded_means: Optional[Tensor] = None,
+                             device="cuda") -> Tensor:
+    """593-654: rebuild the model from its files, evaluate it at the decoded means, decode, dequantize."""
+    if not all(f"{e}_shape" in meta for e in _ENCODINGS):
+        raise NotImplementedError(
+            f"_decompress_gaussian_ans: the meta of {param_name} has no encoding_*_shape keys: this directory was not written by the "
+            f"hash-grid Gaussian codec (no entropy model files for {param_name}); decode it with the route that wrote it")
+    if decoded_means is None:
+        raise ValueError(f"_decompress_gaussian_ans: {param_name} needs the decoded means (decompress() hands them over)")
+    path = os.path.join(compress_dir, f"{param_name}.bin")
+    entropy_model = load_gaussian_entropy_model(compress_dir, param_name, meta, device)
+    mu_q, k = gaussian_params(entropy_model, decoded_means.to(device), meta["mins"], meta["maxs"])
+    symbols = gauss_ans_decode(np.fromfile(path, dtype=np.uint8), mu_q, k, device=device, what=path)
+    if symbols.shape[0] != meta["shape"][0] or symbols.shape[1] != len(meta["mins"]):
+        raise ValueError(f"{path}: {tuple(symbols.shape)} symbols, meta.json describes {meta['shape']}")
+    return dequantize_grid([symbols], meta, device=device)
 
 
 def _compress_masked_kmeans(compress_dir: str, param_name: str, params: Tensor, n_sidelen: int, n_clusters: int = 32768,
@@ -160,8 +234,9 @@ class EntropyCodingCompression:
 
     @torch.no_grad()
     def compress(self, compress_dir: str, splats: Dict[str, Tensor], entropy_models=None) -> None:
-        """``entropy_models`` must be given, as in the reference (121-122); the factorized codec does not read them.  The
-        reference's decode-the-means-again step (157-159) feeds only the Gaussian codec and is left out."""
+        """``entropy_models`` must be given, as in the reference (121-122); the factorized codec does not read them.  An
+        attribute routed to ``_compress_gaussian_ans`` gets its model and the DECODED means (157-159: read back from the files
+        just written), so ``means`` must precede it in ``splats``."""
         if entropy_models is None:
             raise ValueError("EntropyCodingCompression should require entropy_models")
         os.makedirs(compress_dir, exist_ok=True)
@@ -171,8 +246,14 @@ class EntropyCodingCompression:
             if value.numel() == 0:
                 meta[name] = _meta_of(value)
             else:
-                meta[name] = self._get_compress_fn(name)(compress_dir, name, value, n_sidelen=side, n_clusters=self.n_clusters,
-                                                         verbose=self.verbose, kmeans_method=self.kmeans_method)
+                fn, extra = self._get_compress_fn(name), {}
+                if fn is _compress_gaussian_ans and name in entropy_models and entropy_models[name] is not None:
+                    if "means" not in meta:
+                        raise ValueError(f"{name} is coded against the decoded means: 'means' must precede it in the splats")
+                    extra = {"entropy_model": entropy_models[name],
+                             "decoded_means": self.get_decompressed_means(compress_dir, meta["means"], value.device)}
+                meta[name] = fn(compress_dir, name, value, n_sidelen=side, n_clusters=self.n_clusters, verbose=self.verbose,
+                                kmeans_method=self.kmeans_method, **extra)
         with open(os.path.join(compress_dir, "meta.json"), "w") as f:
             json.dump(meta, f)
 
@@ -184,7 +265,15 @@ class EntropyCodingCompression:
         for name, m in meta.items():
             if not np.all(m["shape"]):
                 splats[name] = torch.zeros(m["shape"], dtype=getattr(torch, m["dtype"]), device=device)
+            elif self._get_decompress_fn(name) is _decompress_gaussian_ans:
+                if "means" not in splats:
+                    raise ValueError(f"{name} is coded against the decoded means: 'means' must precede it in meta.json")
+                splats[name] = _decompress_gaussian_ans(compress_dir, name, m, inverse_log_transform(splats["means"]), device=device)
             else:
                 splats[name] = self._get_decompress_fn(name)(compress_dir, name, m, device=device)
         splats["means"] = inverse_log_transform(splats["means"])
         return splats
+
+    def get_decompressed_means(self, compress_dir: str, meta_means: Dict[str, Any], device="cuda") -> Tensor:
+        """193-201: the means as ``decompress`` will see them, from the files of ``compress_dir``."""
+        return inverse_log_transform(self._get_decompress_fn("means")(compress_dir, "means", meta_means, device=device))

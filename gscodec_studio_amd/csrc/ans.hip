@@ -206,6 +206,21 @@ extern "C" int32_t gs_ans_pack(uint64_t n_streams_total, uint32_t S, uint32_t P,
     return 0;
 }
 
+// the same copy for a caller that sizes its slots itself (gauss_ans.hip: P = 16, its own worst case)
+extern "C" int32_t gs_ans_pack_slots(uint64_t n_streams_total, uint32_t slot_bytes, const uint8_t *scratch, const uint32_t *lengths,
+                                     const uint32_t *states, const int64_t *offsets, uint8_t *payload, uint64_t payload_bytes,
+                                     gs_stream_t stream) {
+    if (n_streams_total == 0) return 0;
+    GS_CHECK_ARG(scratch && lengths && states && offsets && payload, "null pointer");
+    GS_CHECK_ARG(slot_bytes >= 1, "slot_bytes must be positive");
+    constexpr uint32_t per_block = GS_BLOCK / GS_WAVE;
+    GS_CHECK_ARG(gs_div_up(n_streams_total, per_block) < (1ull << 31), "too many streams");
+    hipLaunchKernelGGL(ans_pack_kernel, dim3(gs_div_up(n_streams_total, per_block)), dim3(GS_BLOCK), 0, (hipStream_t)stream,
+                       n_streams_total, slot_bytes, scratch, lengths, states, offsets, payload, payload_bytes);
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int32_t gs_ans_decode(uint64_t N, uint32_t C, uint32_t S, uint32_t P, const uint8_t *payload, uint64_t payload_bytes,
                                  const int64_t *offsets, const uint32_t *freq, const uint32_t *cum, uint8_t *symbols,
                                  gs_stream_t stream) {

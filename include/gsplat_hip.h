@@ -51,7 +51,8 @@ extern "C" {
  * gs_appearance_partial_cols), and the K-means entries (gs_kmeans_padded_width, gs_kmeans_default_slices, gs_kmeans_assign,
  * gs_kmeans_update), and the nearest-neighbour entries (gs_knn_cells, gs_knn_finish_grid, gs_knn_search), and the
  * PLY entries (gs_ply_unpack, gs_ply_pack, gs_ply_max_stride, gs_ply_max_columns, gs_ply_block_rows), and the hash-grid Gaussian entropy model's (gs_hashgrid_encode_fwd / _bwd,
- * gs_gaussian_bits_fwd / _bwd). */
+ * gs_gaussian_bits_fwd / _bwd), and the Gaussian entropy coder's (gs_ans_pack_slots, gs_gauss_ans_slot_bytes,
+ * gs_gauss_ans_encode_bytes, gs_gauss_ans_params, gs_gauss_ans_encode, gs_gauss_ans_decode). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -960,6 +961,44 @@ int32_t gs_ans_pack(uint64_t n_streams_total, uint32_t S, uint32_t P, const uint
                     const uint32_t *states, const int64_t *offsets, uint8_t *payload, uint64_t payload_bytes, gs_stream_t stream);
 int32_t gs_ans_decode(uint64_t N, uint32_t C, uint32_t S, uint32_t P, const uint8_t *payload, uint64_t payload_bytes,
                       const int64_t *offsets, const uint32_t *freq, const uint32_t *cum, uint8_t *symbols, gs_stream_t stream);
+/* gs_ans_pack for a caller that sizes its slots itself: slot_bytes instead of (S, P). */
+int32_t gs_ans_pack_slots(uint64_t n_streams_total, uint32_t slot_bytes, const uint8_t *scratch, const uint32_t *lengths,
+                          const uint32_t *states, const int64_t *offsets, uint8_t *payload, uint64_t payload_bytes, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Hash-grid Gaussian route of the entropy coder (gauss_ans.hip): the same state machine, stream layout and slots as above at
+ * P = 16, but EVERY SYMBOL HAS ITS OWN FREQUENCIES, given by mu_q (the mean on a grid of 8 steps per symbol, 0..2040) and k (a scale
+ * level, 0..63: sigma_k = 2^((k - 22) / 5) symbol widths) through one table G uint16 [64, 4073]:
+ *   cum(0) = 0, cum(256) = 2^16, cum(s) = G[k][clamp(8 s - 4 - mu_q, -2036, 2036) + 2036] + s for s = 1..255, f(s) = cum(s + 1) - cum(s)
+ * (every f >= 1: any model codes any symbol).  The format's definition is gscodec_studio_amd/compression/gauss_ans_reference.py,
+ * which also builds G and the 63 level thresholds; the kernels' output is byte-identical to it.
+ *
+ * gs_gauss_ans_params: one lane per splat; features float [N, 48] (gs_hashgrid_encode_fwd's output, read in place, 16-byte
+ *   aligned) through Linear(48, 5C) [w1 [5C, 48], b1], ReLU (h > 0 ? h : 0), Linear(5C, 2C) [w2 [2C, 5C], b2] in float32 with the
+ *   accumulator starting at the bias, inputs ascending, every product and sum rounded on its own; miu = out[c], sigma = out[C + c]
+ *   (1e-9 where below); mu_norm = (miu - mins) / (maxs - mins) * 255, sigma_norm = sigma / (maxs - mins) * 255; mu_q = 0 where not
+ *   mu_norm > 0, 2040 where mu_norm >= 255, else rint(8 mu_norm); k = the number of thresholds [63] <= sigma_norm.  Writes mu_q
+ *   int16 [C, N] and k uint8 [C, N] (channel-major, what the coder reads); miu / sigma (float [N, C], may be NULL) receive the
+ *   float values.  Inference only.  1 <= C <= 8.
+ * gs_gauss_ans_encode: as gs_ans_encode, on channel_major symbols uint8 [C, N] (gs_ans_histogram's copy); slots of
+ *   gs_gauss_ans_slot_bytes(S) = 2 S + S / 512 + 8 bytes (the worst case at P = 16 plus 8) in scratch (>= gs_gauss_ans_encode_bytes);
+ *   gs_ans_pack_slots copies them.  *status (device uint32, zero-filled by the caller): bit 0 = a mu_q or k out of range was met
+ *   (clamped), bit 1 = a slot was too small (no write leaves the slot).  table: G on the device, 2-byte aligned.
+ * gs_gauss_ans_decode: payload + offsets (int64 [C n_streams + 1], device) -> symbols uint8 [N, C].  Reads are bounded to the
+ *   stream's byte range clamped to [0, payload_bytes], a byte beyond it is 0; mu_q, k and the table index are clamped; the symbol
+ *   is found by an 8-step binary search and at most two bytes are read per symbol: a damaged file decodes to wrong symbols.
+ * C <= 16 for the two coder entries. */
+uint32_t gs_gauss_ans_slot_bytes(uint32_t S);
+uint64_t gs_gauss_ans_encode_bytes(uint64_t N, uint32_t C, uint32_t S);
+int32_t gs_gauss_ans_params(uint64_t N, uint32_t C, const float *features, const float *w1, const float *b1, const float *w2,
+                            const float *b2, const float *mins, const float *maxs, const float *thresholds, int16_t *mu_q,
+                            uint8_t *k, float *miu, float *sigma, gs_stream_t stream);
+int32_t gs_gauss_ans_encode(uint64_t N, uint32_t C, uint32_t S, const uint8_t *channel_major, const int16_t *mu_q, const uint8_t *k,
+                            const uint16_t *table, uint8_t *scratch, uint64_t scratch_bytes, uint32_t *lengths, uint32_t *states,
+                            uint32_t *status, gs_stream_t stream);
+int32_t gs_gauss_ans_decode(uint64_t N, uint32_t C, uint32_t S, const uint8_t *payload, uint64_t payload_bytes,
+                            const int64_t *offsets, const int16_t *mu_q, const uint8_t *k, const uint16_t *table, uint8_t *symbols,
+                            gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Grid sort (grid_sort.hip): the order of the splats on the S x S image grid of the PNG codecs that makes every attribute image

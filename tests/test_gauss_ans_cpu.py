@@ -1,0 +1,225 @@
+"""The Gaussian ANS bitstream without a GPU: the numpy coder that defines the format
+(gscodec_studio_amd/compression/gauss_ans_reference.py), its tables, the container's validation (host checks; nothing is launched),
+the size of the payload against the exact cross-entropy and against the factorized route, and the one-bit table files against
+arrays recorded from the reference."""
+import math
+import os
+import struct
+
+import numpy as np
+import pytest
+
+from gauss_ans_cases import model_case
+from gscodec_studio_amd.compression import ans_reference as A
+from gscodec_studio_amd.compression import gauss_ans_reference as R
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gauss_ans.npz")
+HEAD = struct.calcsize("<8sIIIIQIII")
+
+
+def test_tables():
+    g, tau = R.gaussian_table(), R.level_thresholds()
+    assert g.shape == (64, 4073) and g.dtype == np.uint16 and tau.shape == (63,) and tau.dtype == np.float32
+    assert np.all(np.diff(g.astype(np.int64), axis=1) >= 0) and g.max() <= 65536 - 256
+    assert np.all(g[:, 2036] == (65536 - 256) // 2) and np.all(np.diff(tau) > 0)
+    for k, t in ((0, -3), (22, 8), (63, 2036), (40, -2036)):
+        want = (65536 - 256) * 0.5 * (1 + math.erf(t / (8 * 2.0 ** ((k - 22) / 5)) / math.sqrt(2)))
+        assert g[k, t + 2036] == np.rint(want)
+    sig = R.level_sigmas()
+    assert np.allclose(tau.astype(np.float64) ** 2, sig[:-1] * sig[1:], rtol=1e-6)  # geometric midpoints
+    # every (mu_q, k) gives 256 frequencies >= 1 that sum to 2^16
+    mu_q, k = np.meshgrid(np.array([0, 1, 4, 1019, 1020, 2039, 2040]), np.arange(64), indexing="ij")
+    f = R.frequencies(mu_q, k)
+    assert f.shape == (7, 64, 256) and f.min() >= 1 and np.all(f.sum(-1) == 1 << 16)
+    assert R.slot_bytes(1024) == 2 * 1024 + 2 + 8 and R.slot_bytes(1) == 10
+
+
+def test_quantize_params():
+    tau = R.level_thresholds()
+    mu = np.array([np.nan, -np.inf, -1.0, 0.0, 1e-30, 0.0625, 0.1875, 100.3, 254.99, 255.0, 300.0, np.inf], np.float32)
+    mu_q, _ = R.quantize_params(mu, np.ones_like(mu))
+    assert mu_q.dtype == np.int16 and mu_q.tolist() == [0, 0, 0, 0, 0, 0, 2, 802, 2040, 2040, 2040, 2040]  # rint: half to even
+    sg = np.array([np.nan, 0.0, 1e-9, tau[0], np.nextafter(tau[0], np.float32(0)), 1.0, tau[62], 1e30, np.inf], np.float32)
+    _, k = R.quantize_params(np.zeros_like(sg), sg)
+    assert k.dtype == np.uint8 and k.tolist() == [0, 0, 0, 1, 0, 22, 63, 63, 63]
+    # the level whose sigma is nearest in the log domain
+    s = np.exp(np.random.default_rng(0).uniform(np.log(0.03), np.log(400), 2000)).astype(np.float32)
+    _, k = R.quantize_params(np.zeros_like(s), s)
+    assert np.array_equal(k, np.clip(np.rint(22 + 5 * np.log2(s.astype(np.float64))), 0, 63))
+
+
+def test_regress_params_order():
+    """The stated float32 order, spelled out with scalar arithmetic for a few rows."""
+    rng = np.random.default_rng(5)
+    c, n = 3, 6
+    x = rng.choice(np.array([-1, -0.5, 0, 0.25, 1], np.float32), (n, 48))
+    w1, b1 = rng.normal(0, 0.3, (15, 48)).astype(np.float32), rng.normal(0, 0.3, 15).astype(np.float32)
+    w2, b2 = rng.normal(0, 0.3, (6, 15)).astype(np.float32), rng.normal(0, 0.3, 6).astype(np.float32)
+    b2[3:] += np.float32(0.5)
+    mins, maxs = np.array([-1, -2, 0], np.float32), np.array([1, 2, 0.5], np.float32)
+    mu_q, k, miu, sigma = R.regress_params(x, w1, b1, w2, b2, mins, maxs, return_float=True)
+    f = np.float32
+    for r in range(n):
+        h = []
+        for j in range(15):
+            acc = b1[j]
+            for i in range(48):
+                acc = f(acc + f(x[r, i] * w1[j, i]))
+            h.append(acc if acc > 0 else f(0))
+        o = []
+        for m in range(6):
+            acc = b2[m]
+            for j in range(15):
+                acc = f(acc + f(h[j] * w2[m, j]))
+            o.append(acc)
+        for ch in range(c):
+            sg = f(1e-9) if o[c + ch] < f(1e-9) else o[c + ch]
+            assert miu[r, ch] == o[ch] and sigma[r, ch] == sg
+            d = f(maxs[ch] - mins[ch])
+            want = R.quantize_params(f(f(f(o[ch] - mins[ch]) / d) * f(255)), f(f(sg / d) * f(255)))
+            assert (mu_q[r, ch], k[r, ch]) == (want[0], want[1])
+    with pytest.raises(ValueError):
+        R.regress_params(x[:, :47], w1, b1, w2, b2, mins, maxs)
+
+
+@pytest.mark.parametrize("s_len", [1, 5, 1024])
+@pytest.mark.parametrize("c", [1, 3, 4])
+@pytest.mark.parametrize("n", [1, 7, 1023, 1024, 1025, 3000])
+def test_numpy_coder_round_trip(n, c, s_len):
+    sym, mu_q, k = model_case(n, c, 1000 * n + 10 * c + s_len)
+    blob = R.encode(sym, mu_q, k, stream_len=s_len)
+    channels, stream_len, count, offsets, payload = R.parse_container(blob)
+    assert (channels, stream_len, count) == (c, s_len, n) and offsets.size == c * (-(-n // s_len)) + 1
+    assert blob[:8].tobytes() == b"GSGANSv1" and offsets[-1] == payload.size
+    assert np.all(np.diff(offsets) - 4 <= R.slot_bytes(s_len) - 8)  # the derived worst case, without the slack
+    assert np.array_equal(R.decode(blob, mu_q, k), sym)
+    assert np.array_equal(R.decode(blob.tobytes(), mu_q, k), sym)
+
+
+def test_wrong_model_decodes_exactly_and_is_large():
+    """Correctness never depends on the model: a model that puts the mean at the other end of the range, at the narrowest level,
+    gives every symbol frequency 1 -- 16 bits each -- and still decodes exactly."""
+    n = 2048
+    sym = np.random.default_rng(1).integers(0, 40, (n, 2)).astype(np.uint8)
+    good_mu = (sym.astype(np.int16) * 8)
+    wrong_mu, k0 = np.full((n, 2), R.MU_Q_MAX, np.int16), np.zeros((n, 2), np.uint8)
+    good = R.encode(sym, good_mu, np.full((n, 2), 10, np.uint8))
+    wrong = R.encode(sym, wrong_mu, k0)
+    assert np.array_equal(R.decode(wrong, wrong_mu, k0), sym) and np.array_equal(R.decode(good, good_mu, np.full((n, 2), 10, np.uint8)), sym)
+    per_stream = np.diff(R.parse_container(wrong)[3]) - 4
+    assert np.all(per_stream >= 2 * 1024 - 1) and np.all(per_stream <= R.slot_bytes(1024) - 8)
+    assert wrong.size > 10 * good.size
+    # decoding against a model other than the encoder's gives other symbols, not an error
+    other = R.decode(good, wrong_mu, k0)
+    assert other.shape == sym.shape and not np.array_equal(other, sym)
+
+
+def test_container_validation():
+    sym, mu_q, k = model_case(3 * 64 + 1, 2, 9)
+    blob = R.encode(sym, mu_q, k, stream_len=64)
+    n_off = 2 * 4 + 1
+
+    def with_offsets(fn):
+        b = blob.copy()
+        off = b[HEAD:HEAD + 4 * n_off].view("<u4").copy()
+        fn(off)
+        b[HEAD:HEAD + 4 * n_off] = off.view(np.uint8)
+        return b
+
+    def with_byte(at, value):
+        b = blob.copy()
+        b[at] = value
+        return b
+
+    wrong_magic = with_byte(0, 0)
+    foreign = np.random.default_rng(0).integers(0, 2**32, 500, dtype=np.uint32)  # what a `constriction` stream looks like: words
+    factorized = A.encode(sym, np.full((2, 256), 1 / 256, np.float32), stream_len=64)  # the other route's container
+    for bad in (wrong_magic, foreign, foreign.tobytes(), factorized, b"", blob[:4]):
+        with pytest.raises(ValueError, match="not interchangeable"):
+            R.decode(bad, mu_q, k)
+    with pytest.raises(ValueError, match="not interchangeable"):  # and the factorized reader refuses this one
+        A.parse_container(blob)
+    crc = with_byte(40, blob[40] ^ 1)  # the tables' CRC32: the last header field
+    with pytest.raises(ValueError, match="CRC32"):
+        R.decode(crc, mu_q, k)
+    decreasing = with_offsets(lambda off: off.__setitem__(3, off[2] - 1))
+    too_short = with_offsets(lambda off: off.__setitem__(3, off[2] + 3))
+    past_end = with_offsets(lambda off: off.__setitem__(n_off - 1, off[n_off - 1] + 1))
+    not_from_zero = with_offsets(lambda off: off.__setitem__(0, 1))
+    for bad in (crc, decreasing, too_short, past_end, not_from_zero, blob[:-5], blob[:HEAD + 7], blob[:HEAD - 1], with_byte(8, 2),
+                with_byte(12, 14), with_byte(32, 32), with_byte(36, 4), with_byte(16, 0)):
+        with pytest.raises(ValueError):
+            R.parse_container(bad)
+        with pytest.raises(ValueError):
+            R.decode(bad, mu_q, k)
+    # the model: shape, dtype, range -- on both sides
+    for bad_mu, bad_k in ((mu_q[:-1], k[:-1]), (mu_q.astype(np.float32), k), (np.where(mu_q == 0, -1, mu_q), k),
+                          (np.where(mu_q == 0, 2041, mu_q), k), (mu_q, np.where(k == 5, 64, k))):
+        with pytest.raises(ValueError):
+            R.decode(blob, bad_mu, bad_k)
+        with pytest.raises(ValueError):
+            R.encode(sym, bad_mu, bad_k, stream_len=64)
+    assert np.array_equal(R.decode(blob, mu_q, k), sym)
+
+
+def test_damaged_payload_decodes_to_something():
+    """Flipped payload bytes give wrong symbols, not an error: reads stay inside each stream and are 0 beyond it."""
+    sym, mu_q, k = model_case(300, 1, 4)
+    blob = R.encode(sym, mu_q, k, stream_len=64)
+    bad = blob.copy()
+    bad[-40:] = 255 - bad[-40:]
+    out = R.decode(bad, mu_q, k)
+    assert out.shape == sym.shape and out.dtype == np.uint8 and np.array_equal(out[:192], sym[:192])
+
+
+def _phi(z):
+    return 0.5 * (1.0 + np.vectorize(math.erf)(z / math.sqrt(2.0)))
+
+
+def test_size_against_cross_entropy_and_factorized_route():
+    """204,800 symbols from clipped, rounded Gaussians (sigma log-uniform in [0.5, 32], means uniform in [-5, 260]), S = 1024:
+    the payload's bits per symbol exceed the exact float64 cross-entropy -- the mean of -log2 of the probability the clipped,
+    rounded Gaussian itself gives the drawn symbol -- by at most 0.15 bit:
+        0.0625  the 4-byte state and the 4-byte offset of a stream, per 1024 symbols
+        0.011   the division's floor, log2(1 + 2^-7)
+        0.045   the model at the most: 0.0039 frequency floor, about 0.010 scale levels, the mean grid
+        the rest is margin.
+    And the same symbols through the factorized route (one histogram per channel, ans_reference) come out larger: the point of
+    the position-conditioned model."""
+    rng = np.random.default_rng(2025)
+    n, c = 51200, 4
+    sigma = np.exp(rng.uniform(np.log(0.5), np.log(32.0), (n, c)))
+    mean = rng.uniform(-5.0, 260.0, (n, c))
+    sym = np.clip(np.rint(mean + sigma * rng.standard_normal((n, c))), 0, 255).astype(np.uint8)
+    s = sym.astype(np.float64)
+    upper = np.where(sym == 255, 1.0, _phi((s + 0.5 - mean) / sigma))
+    lower = np.where(sym == 0, 0.0, _phi((s - 0.5 - mean) / sigma))
+    cross_entropy = float(np.mean(-np.log2(upper - lower)))
+    mu_q, k = R.quantize_params(mean.astype(np.float32), sigma.astype(np.float32))
+    blob = R.encode(sym, mu_q, k, stream_len=1024)
+    assert np.array_equal(R.decode(blob, mu_q, k), sym)
+    offsets, payload = R.parse_container(blob)[3:]
+    file_bits = 8.0 * (payload.size + 4 * (offsets.size - 1)) / sym.size  # payload (with the states) + the offset table
+    f = R.frequencies(mu_q, k)
+    model_bits = float(np.mean(-np.log2(np.take_along_axis(f, sym[..., None].astype(np.int64), -1) / 65536.0)))
+    hist = np.stack([np.bincount(sym[:, j], minlength=256) for j in range(c)]).astype(np.float64)
+    prob = (hist / n).astype(np.float32)
+    factorized = A.encode(sym, prob, stream_len=1024)
+    print(f"cross-entropy {cross_entropy:.4f} bit/symbol, integer model {model_bits:.4f}, Gaussian payload + offsets {file_bits:.4f} "
+          f"({blob.size} bytes), factorized route {8.0 * factorized.size / sym.size:.4f} ({factorized.size} bytes + the table)")
+    assert model_bits - cross_entropy <= 0.045
+    assert file_bits - cross_entropy <= 0.15
+    assert factorized.size > blob.size
+
+
+def test_sign_files_match_the_reference():
+    g = np.load(GOLDEN)
+    for n in (8, 13, 1000):
+        signs, data = g[f"signs.{n}"], g[f"bytes.{n}"]
+        packed = R.pack_signs(signs)
+        assert packed.dtype == np.uint8 and np.array_equal(packed, data)
+        back = R.unpack_signs(data, n)
+        assert back.dtype == np.float32 and np.array_equal(back, g[f"back.{n}"]) and np.array_equal(back, signs)
+        assert np.array_equal(R.unpack_signs(data.tobytes(), n), signs)
+        if n > 8:
+            assert np.array_equal(R.unpack_signs(data[:-1], n), g[f"back_short.{n}"])
