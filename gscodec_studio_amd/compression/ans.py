@@ -17,21 +17,10 @@ from torch import Tensor
 
 from .. import _backend as B
 from . import ans_reference as R
+from ._ans_streams import _stream, check_symbols, decode_buffers, encode_streams
 from .ans_reference import normalize_frequencies
 
 MAX_CHANNELS = 16  # of one call: the histogram kernel keeps C x 256 counters in LDS
-
-
-def _stream(t: Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _check_symbols(symbols: Tensor) -> Tensor:
-    if not symbols.is_cuda:
-        raise RuntimeError("the ANS coder runs on the GPU: the symbols must be a device tensor (no CPU fallback)")
-    if symbols.dtype != torch.uint8 or symbols.dim() != 2 or not 1 <= symbols.shape[0] < 1 << 31 or not 1 <= symbols.shape[1] <= MAX_CHANNELS:
-        raise ValueError(f"symbols must be a non-empty uint8 [N, C] tensor with C <= {MAX_CHANNELS}, got {symbols.dtype} {tuple(symbols.shape)}")
-    return symbols.contiguous()
 
 
 def _histogram(symbols: Tensor, channel_major: bool) -> Tuple[Tensor, Optional[Tensor]]:
@@ -46,7 +35,7 @@ def _histogram(symbols: Tensor, channel_major: bool) -> Tuple[Tensor, Optional[T
 @torch.no_grad()
 def symbol_histogram(symbols: Tensor) -> Tensor:
     """Occurrences of every byte value per channel: uint8 [N, C] device tensor -> int32 [C, 256]."""
-    return _histogram(_check_symbols(symbols), channel_major=False)[0]
+    return _histogram(check_symbols(symbols, MAX_CHANNELS, "ANS coder"), channel_major=False)[0]
 
 
 def probabilities(counts: Tensor) -> np.ndarray:
@@ -59,36 +48,24 @@ def probabilities(counts: Tensor) -> np.ndarray:
 def ans_encode(symbols: Tensor, prob: np.ndarray, stream_len: int = R.DEFAULT_STREAM_LEN, bits: int = R.DEFAULT_BITS) -> np.ndarray:
     """Encode device symbols uint8 [N, C] against the float32 table ``prob`` [C, 256] -> the container as a numpy uint8 array,
     byte-identical to ``ans_reference.encode``.  A symbol whose probability is 0 raises ValueError."""
-    symbols = _check_symbols(symbols)
+    symbols = check_symbols(symbols, MAX_CHANNELS, "ANS coder", stream_len)
     n, c = symbols.shape
-    dev = symbols.device
-    if not 1 <= stream_len <= 1 << 24:
-        raise ValueError(f"stream_len = {stream_len}")
     freq = normalize_frequencies(prob, bits)
     if freq.shape[0] != c:
         raise ValueError(f"{c} channels of symbols, {freq.shape[0]} rows of probabilities")
     counts, cm = _histogram(symbols, channel_major=True)
     if np.any((counts.cpu().numpy() != 0) & (freq == 0)):
         raise ValueError("a symbol occurs whose probability is 0")
-    n_total = c * (-(-n // stream_len))
-    d_freq = torch.from_numpy(freq.view(np.int32)).to(dev)
-    d_cum = torch.from_numpy(R.cumulative(freq).view(np.int32)).to(dev)
-    scratch = torch.empty(int(B.query("gs_ans_encode_bytes", n, c, stream_len, bits)), dtype=torch.uint8, device=dev)
-    lengths = torch.empty(n_total, dtype=torch.int32, device=dev)
-    states = torch.empty(n_total, dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
+    d_freq = torch.from_numpy(freq.view(np.int32)).to(symbols.device)
+    d_cum = torch.from_numpy(R.cumulative(freq).view(np.int32)).to(symbols.device)
+
+    def launch(scratch, lengths, states, status, stream):
         B.call("gs_ans_encode", n, c, stream_len, bits, B.ptr(cm), B.ptr(d_freq), B.ptr(d_cum), B.ptr(scratch), scratch.numel(),
-               B.ptr(lengths), B.ptr(states), B.ptr(status), _stream(symbols))
-        offsets = torch.zeros(n_total + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(lengths.long() + 4, dim=0, out=offsets[1:])
-        total, bad = int(offsets[-1]), int(status)  # the one read-back: the payload's size
-        if bad:
-            raise RuntimeError(f"gs_ans_encode reported status {bad} (1: symbol without frequency, 2: slot too small)")
-        payload = torch.empty(total, dtype=torch.uint8, device=dev)
-        B.call("gs_ans_pack", n_total, stream_len, bits, B.ptr(scratch), B.ptr(lengths), B.ptr(states), B.ptr(offsets), B.ptr(payload),
-               total, _stream(symbols))
-    return R.build_container(bits, c, stream_len, n, offsets.cpu().numpy(), payload.cpu().numpy())
+               B.ptr(lengths), B.ptr(states), B.ptr(status), stream)
+
+    offsets, payload = encode_streams(symbols, stream_len, int(B.query("gs_ans_slot_bytes", stream_len, bits)), launch,
+                                      "gs_ans_encode", "1: symbol without frequency, 2: slot too small")
+    return R.build_container(bits, c, stream_len, n, offsets, payload)
 
 
 @torch.no_grad()
@@ -103,13 +80,9 @@ def ans_decode(blob, prob: np.ndarray, device="cuda", what: str = "the buffer") 
     freq = normalize_frequencies(prob, bits)
     if freq.shape[0] != c:
         raise ValueError(f"{what}: the container has {c} channels, the probability table {freq.shape[0]}")
-    if c > MAX_CHANNELS or n >= 1 << 31 or stream_len > 1 << 24:
-        raise ValueError(f"{what}: C = {c}, N = {n}, S = {stream_len} is outside what the kernels take")
+    d_off, d_payload, out = decode_buffers(n, c, stream_len, MAX_CHANNELS, offsets, payload, dev, what)
     d_freq = torch.from_numpy(freq.view(np.int32)).to(dev)
     d_cum = torch.from_numpy(R.cumulative(freq).view(np.int32)).to(dev)
-    d_off = torch.from_numpy(offsets).to(dev)
-    d_payload = torch.from_numpy(np.array(payload, copy=True)).to(dev)
-    out = torch.empty((n, c), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         B.call("gs_ans_decode", n, c, stream_len, bits, B.ptr(d_payload), d_payload.numel(), B.ptr(d_off), B.ptr(d_freq), B.ptr(d_cum),
                B.ptr(out), _stream(out))

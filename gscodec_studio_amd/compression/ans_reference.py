@@ -20,6 +20,9 @@ Container, little-endian::
     payload                            per stream: u32 final state, then the renormalisation bytes in the order the decoder
                                        consumes them (the reverse of the order the encoder emitted them in)
 
+Everything about one stream -- ``_streams`` / ``_pad``, the encode and the decode loop, the container behind its header -- takes the
+model as a callable and serves ``gauss_ans_reference`` as well; only header, magic and model differ between the two formats.
+
 No torch, no native library: importable anywhere."""
 from __future__ import annotations
 
@@ -77,20 +80,43 @@ def slot_bytes(stream_len: int, bits: int) -> int:
     return (stream_len * bits + 7) // 8 + 8
 
 
-def build_container(bits: int, n_channels: int, stream_len: int, n: int, offsets: np.ndarray, payload: np.ndarray) -> np.ndarray:
-    """Header + offset table + payload -> the file's bytes (uint8 array)."""
+def _container(head: bytes, offsets: np.ndarray, payload: np.ndarray) -> np.ndarray:
+    """What both containers are behind their own header: the u32 offset table, then the payload."""
     if int(offsets[-1]) >= 1 << 32:
         raise ValueError("ANS payload of 4 GiB or more: the container's offsets are 32-bit")
-    head = _HEADER.pack(MAGIC, VERSION, bits, n_channels, stream_len, n)
     return np.concatenate([np.frombuffer(head, np.uint8), np.asarray(offsets).astype("<u4").view(np.uint8),
                            np.asarray(payload, np.uint8)])
+
+
+def _as_bytes(blob) -> np.ndarray:
+    return np.frombuffer(bytes(blob), np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob).view(np.uint8).ravel()
+
+
+def _split_container(buf: np.ndarray, head_size: int, n_total: int, what: str) -> Tuple[np.ndarray, np.ndarray]:
+    """The part of a container behind its (validated) header -> (offsets int64 [n_total + 1], payload uint8); ValueError for
+    offsets that decrease, point outside the file or leave a stream fewer than its 4 state bytes."""
+    table_end = head_size + 4 * (n_total + 1)
+    if buf.size < table_end:
+        raise ValueError(f"{what}: truncated ANS offset table ({n_total + 1} entries expected)")
+    offsets = buf[head_size:table_end].view("<u4").astype(np.int64)
+    payload = buf[table_end:]
+    if offsets[0] != 0 or np.any(np.diff(offsets) < 4):
+        raise ValueError(f"{what}: ANS stream offsets must start at 0 and leave every stream at least its 4 state bytes")
+    if offsets[-1] > payload.size:
+        raise ValueError(f"{what}: ANS stream offsets point past the end of the file ({int(offsets[-1])} > {payload.size} payload bytes)")
+    return offsets, payload
+
+
+def build_container(bits: int, n_channels: int, stream_len: int, n: int, offsets: np.ndarray, payload: np.ndarray) -> np.ndarray:
+    """Header + offset table + payload -> the file's bytes (uint8 array)."""
+    return _container(_HEADER.pack(MAGIC, VERSION, bits, n_channels, stream_len, n), offsets, payload)
 
 
 def parse_container(blob, what: str = "the buffer") -> Tuple[int, int, int, int, np.ndarray, np.ndarray]:
     """Validate a container and split it: (P, C, S, N, offsets int64 [C * n_streams + 1], payload uint8).  Raises ValueError for
     anything a decoder must not be started on: a foreign or short file, an unknown version, offsets that decrease, point outside
     the file or leave a stream fewer than its 4 state bytes."""
-    buf = np.frombuffer(bytes(blob), np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob).view(np.uint8).ravel()
+    buf = _as_bytes(blob)
     if buf.size < len(MAGIC) or buf[:len(MAGIC)].tobytes() != MAGIC:
         raise ValueError(NOT_OURS.format(what=what))
     if buf.size < _HEADER.size:
@@ -100,78 +126,61 @@ def parse_container(blob, what: str = "the buffer") -> Tuple[int, int, int, int,
         raise ValueError(f"{what}: ANS container version {version}, this reader knows version {VERSION}")
     if not MIN_BITS <= bits <= MAX_BITS or n_channels < 1 or stream_len < 1 or n < 1:
         raise ValueError(f"{what}: bad ANS header (P = {bits}, C = {n_channels}, S = {stream_len}, N = {n})")
-    n_total = n_channels * (-(-n // stream_len))
-    table_end = _HEADER.size + 4 * (n_total + 1)
-    if buf.size < table_end:
-        raise ValueError(f"{what}: truncated ANS offset table ({n_total + 1} entries expected)")
-    offsets = buf[_HEADER.size:table_end].view("<u4").astype(np.int64)
-    payload = buf[table_end:]
-    if offsets[0] != 0 or np.any(np.diff(offsets) < 4):
-        raise ValueError(f"{what}: ANS stream offsets must start at 0 and leave every stream at least its 4 state bytes")
-    if offsets[-1] > payload.size:
-        raise ValueError(f"{what}: ANS stream offsets point past the end of the file ({int(offsets[-1])} > {payload.size} payload bytes)")
-    return bits, n_channels, stream_len, n, offsets, payload
+    return (bits, n_channels, stream_len, n) + _split_container(buf, _HEADER.size, n_channels * (-(-n // stream_len)), what)
 
 
-def _streams(n: int, n_channels: int, stream_len: int):
+def _streams(n: int, n_channels: int, stream_len: int) -> Tuple[np.ndarray, np.ndarray]:
+    """One row per stream, channel after channel: (its length, its channel), both [C * n_streams]."""
     n_streams = -(-n // stream_len)
     lens = np.tile(np.minimum(stream_len, n - np.arange(n_streams, dtype=np.int64) * stream_len), n_channels)
-    return n_streams, lens, np.repeat(np.arange(n_channels), n_streams)
+    return lens, np.repeat(np.arange(n_channels), n_streams)
 
 
-def encode(symbols: np.ndarray, prob: np.ndarray, stream_len: int = DEFAULT_STREAM_LEN, bits: int = DEFAULT_BITS) -> np.ndarray:
-    """symbols uint8 [N, C], prob float32 [C, 256] -> container bytes.  All streams advance together, one symbol per step."""
-    sym = np.asarray(symbols)
-    if sym.dtype != np.uint8 or sym.ndim != 2 or sym.shape[0] < 1 or stream_len < 1:
-        raise ValueError("symbols must be a non-empty uint8 [N, C] array and stream_len positive")
-    n, n_channels = sym.shape
-    freq = normalize_frequencies(prob, bits)
-    if freq.shape[0] != n_channels:
-        raise ValueError(f"{n_channels} channels of symbols, {freq.shape[0]} rows of probabilities")
-    if np.any(freq[np.arange(n_channels)[None, :], sym] == 0):
-        raise ValueError("a symbol occurs whose probability is 0")
-    cum = cumulative(freq)
-    n_streams, lens, ch = _streams(n, n_channels, stream_len)
-    padded = np.zeros((n_channels, n_streams * stream_len), np.uint8)
-    padded[:, :n] = sym.T
-    padded = padded.reshape(n_channels * n_streams, stream_len)
-    rows = np.arange(n_channels * n_streams)
-    slot = slot_bytes(stream_len, bits)
+def _pad(a: np.ndarray, stream_len: int) -> np.ndarray:
+    """[N, C] -> [C * n_streams, S]: the rows of ``_streams``, zero-padded behind N."""
+    n, c = a.shape
+    p = np.zeros((c, -(-n // stream_len) * stream_len), a.dtype)
+    p[:, :n] = a.T
+    return p.reshape(-1, stream_len)
+
+
+def _encode_streams(n: int, n_channels: int, stream_len: int, bits: int, slot: int, model) -> Tuple[np.ndarray, np.ndarray]:
+    """THE ENCODER of both routes.  All streams (rows) advance together, last symbol first; ``model(j)`` gives the frequency and
+    the cumulative frequency of symbol j of every row at resolution 2^bits (what it gives for a row that has no symbol j is not
+    used).  Each row fills a private slot of ``slot`` bytes from the back.  -> (offsets int64 [rows + 1], payload uint8)."""
+    lens = _streams(n, n_channels, stream_len)[0]
+    rows = np.arange(lens.size)
     buf = np.zeros((rows.size, slot), np.uint8)
     pos = np.full(rows.size, slot, np.int64)
     x = np.full(rows.size, STATE_LOW, np.uint64)
     for j in range(stream_len - 1, -1, -1):
         act = j < lens
-        s = padded[:, j]
-        f = np.where(act, freq[ch, s], 1).astype(np.uint64)
+        f, cum = model(j)
+        f = np.where(act, f, 1).astype(np.uint64)
         while True:
             m = act & (x >= (f << np.uint64(31 - bits)))
             if not m.any():
                 break
+            if np.any(pos[m] == 0):
+                raise RuntimeError("slot full: a stream outgrew its worst-case bound")  # unreachable (the slot_bytes derivations)
             pos[m] -= 1
             buf[rows[m], pos[m]] = (x[m] & np.uint64(0xFF)).astype(np.uint8)
             x[m] >>= np.uint64(8)
-        x = np.where(act, ((x // f) << np.uint64(bits)) + x % f + cum[ch, s], x)
-    sizes = 4 + (slot - pos)
-    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        x = np.where(act, ((x // f) << np.uint64(bits)) + x % f + np.asarray(cum).astype(np.uint64), x)
+    offsets = np.concatenate([[0], np.cumsum(4 + (slot - pos))]).astype(np.int64)
     payload = np.empty(int(offsets[-1]), np.uint8)
     states = x.astype("<u4").view(np.uint8).reshape(-1, 4)
     for i in rows:
         payload[offsets[i]:offsets[i] + 4] = states[i]
         payload[offsets[i] + 4:offsets[i + 1]] = buf[i, pos[i]:]
-    return build_container(bits, n_channels, stream_len, n, offsets, payload)
+    return offsets, payload
 
 
-def decode(blob, prob: np.ndarray) -> np.ndarray:
-    """container bytes, prob float32 [C, 256] -> symbols uint8 [N, C].  Reads are bounded to each stream's byte range; a byte
-    beyond it is 0 (a damaged stream gives wrong symbols, nothing else)."""
-    bits, n_channels, stream_len, n, offsets, payload = parse_container(blob)
-    freq = normalize_frequencies(prob, bits)
-    if freq.shape[0] != n_channels:
-        raise ValueError(f"the container has {n_channels} channels, the probability table {freq.shape[0]}")
-    cum = cumulative(freq)
-    symbol_of = np.stack([np.repeat(np.arange(256, dtype=np.uint8), row) for row in freq])  # [C, 2^P]
-    n_streams, lens, ch = _streams(n, n_channels, stream_len)
+def _decode_streams(offsets: np.ndarray, payload: np.ndarray, n: int, n_channels: int, stream_len: int, bits: int, lookup) -> np.ndarray:
+    """THE DECODER of both routes -> symbols uint8 [N, C].  ``lookup(j, slot)`` names, for symbol j of every row, the symbol
+    whose [cum, cum + f) holds ``slot`` (int64), with f and cum.  Reads are bounded to each stream's byte range; a byte beyond it
+    is 0 (a damaged stream gives wrong symbols, nothing else)."""
+    lens = _streams(n, n_channels, stream_len)[0]
     data = np.concatenate([payload, np.zeros(1, np.uint8)])  # index payload.size = the substituted 0
     rd, end = offsets[:-1].copy(), offsets[1:]
 
@@ -184,14 +193,51 @@ def decode(blob, prob: np.ndarray) -> np.ndarray:
     x = np.zeros(rd.size, np.uint64)
     for b in range(4):
         x |= next_byte(everyone) << np.uint64(8 * b)
-    out = np.zeros((n_channels * n_streams, stream_len), np.uint8)
+    out = np.zeros((rd.size, stream_len), np.uint8)
     for j in range(stream_len):
         act = j < lens
-        slot = x & np.uint64((1 << bits) - 1)
-        s = symbol_of[ch, slot.astype(np.int64)]
+        slot = (x & np.uint64((1 << bits) - 1)).astype(np.int64)
+        s, f, cum = lookup(j, slot)
         out[act, j] = s[act]
-        x = np.where(act, (freq[ch, s].astype(np.uint64) * (x >> np.uint64(bits)) + slot - cum[ch, s]) & np.uint64(0xFFFFFFFF), x)
+        x = np.where(act, (np.asarray(f).astype(np.uint64) * (x >> np.uint64(bits)) + (slot - cum).astype(np.uint64))
+                     & np.uint64(0xFFFFFFFF), x)
         for _ in range(2):  # a valid stream needs at most two bytes per symbol
             m = act & (x < STATE_LOW)
             x = np.where(m, (x << np.uint64(8)) | next_byte(m), x)
-    return np.ascontiguousarray(out.reshape(n_channels, n_streams * stream_len)[:, :n].T)
+    return np.ascontiguousarray(out.reshape(n_channels, -1)[:, :n].T)
+
+
+def encode(symbols: np.ndarray, prob: np.ndarray, stream_len: int = DEFAULT_STREAM_LEN, bits: int = DEFAULT_BITS) -> np.ndarray:
+    """symbols uint8 [N, C], prob float32 [C, 256] -> container bytes."""
+    sym = np.asarray(symbols)
+    if sym.dtype != np.uint8 or sym.ndim != 2 or sym.shape[0] < 1 or stream_len < 1:
+        raise ValueError("symbols must be a non-empty uint8 [N, C] array and stream_len positive")
+    n, n_channels = sym.shape
+    freq = normalize_frequencies(prob, bits)
+    if freq.shape[0] != n_channels:
+        raise ValueError(f"{n_channels} channels of symbols, {freq.shape[0]} rows of probabilities")
+    if np.any(freq[np.arange(n_channels)[None, :], sym] == 0):
+        raise ValueError("a symbol occurs whose probability is 0")
+    cum = cumulative(freq)
+    ch, padded = _streams(n, n_channels, stream_len)[1], _pad(sym, stream_len)
+    offsets, payload = _encode_streams(n, n_channels, stream_len, bits, slot_bytes(stream_len, bits),
+                                       lambda j: (freq[ch, padded[:, j]], cum[ch, padded[:, j]]))
+    return build_container(bits, n_channels, stream_len, n, offsets, payload)
+
+
+def decode(blob, prob: np.ndarray) -> np.ndarray:
+    """container bytes, prob float32 [C, 256] -> symbols uint8 [N, C].  Reads are bounded to each stream's byte range; a byte
+    beyond it is 0 (a damaged stream gives wrong symbols, nothing else)."""
+    bits, n_channels, stream_len, n, offsets, payload = parse_container(blob)
+    freq = normalize_frequencies(prob, bits)
+    if freq.shape[0] != n_channels:
+        raise ValueError(f"the container has {n_channels} channels, the probability table {freq.shape[0]}")
+    cum = cumulative(freq)
+    symbol_of = np.stack([np.repeat(np.arange(256, dtype=np.uint8), row) for row in freq])  # [C, 2^P]
+    ch = _streams(n, n_channels, stream_len)[1]
+
+    def lookup(j, slot):
+        s = symbol_of[ch, slot]
+        return s, freq[ch, s], cum[ch, s]
+
+    return _decode_streams(offsets, payload, n, n_channels, stream_len, bits, lookup)

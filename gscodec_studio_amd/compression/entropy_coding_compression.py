@@ -83,14 +83,18 @@ def _compress_factorized_ans(compress_dir: str, param_name: str, params: Tensor,
     return meta
 
 
+def _dequantize_symbols(path: str, symbols: Tensor, meta: Dict[str, Any], device) -> Tensor:
+    """What either ANS route does with its decoded symbols: they must be what the meta describes."""
+    if symbols.shape[0] != meta["shape"][0] or symbols.shape[1] != len(meta["mins"]):
+        raise ValueError(f"{path}: {tuple(symbols.shape)} symbols, meta.json describes {meta['shape']}")
+    return dequantize_grid([symbols], meta, device=device)
+
+
 def _decompress_factorized_ans(compress_dir: str, param_name: str, meta: Dict[str, Any], device="cuda") -> Tensor:
     """398-446: symbols / 255 in float64, times the float32 ``maxs - mins``, plus ``mins``, cast: ``gs_grid_dequantize``."""
     path = os.path.join(compress_dir, f"{param_name}.bin")
     prob = np.load(os.path.join(compress_dir, f"{param_name}_prob.npy")).astype(np.float32)
-    symbols = ans_decode(np.fromfile(path, dtype=np.uint8), prob, device=device, what=path)
-    if symbols.shape[0] != meta["shape"][0] or symbols.shape[1] != len(meta["mins"]):
-        raise ValueError(f"{path}: {tuple(symbols.shape)} symbols, meta.json describes {meta['shape']}")
-    return dequantize_grid([symbols], meta, device=device)
+    return _dequantize_symbols(path, ans_decode(np.fromfile(path, dtype=np.uint8), prob, device=device, what=path), meta, device)
 
 
 def save_gaussian_entropy_model(param_name: str, entropy_model: torch.nn.Module, compress_dir: str) -> Dict[str, Any]:
@@ -160,10 +164,7 @@ def _decompress_gaussian_ans(compress_dir: str, param_name: str, meta: Dict[str,
     path = os.path.join(compress_dir, f"{param_name}.bin")
     entropy_model = load_gaussian_entropy_model(compress_dir, param_name, meta, device)
     mu_q, k = gaussian_params(entropy_model, decoded_means.to(device), meta["mins"], meta["maxs"])
-    symbols = gauss_ans_decode(np.fromfile(path, dtype=np.uint8), mu_q, k, device=device, what=path)
-    if symbols.shape[0] != meta["shape"][0] or symbols.shape[1] != len(meta["mins"]):
-        raise ValueError(f"{path}: {tuple(symbols.shape)} symbols, meta.json describes {meta['shape']}")
-    return dequantize_grid([symbols], meta, device=device)
+    return _dequantize_symbols(path, gauss_ans_decode(np.fromfile(path, dtype=np.uint8), mu_q, k, device=device, what=path), meta, device)
 
 
 def _compress_masked_kmeans(compress_dir: str, param_name: str, params: Tensor, n_sidelen: int, n_clusters: int = 32768,

@@ -21,15 +21,12 @@ from torch import Tensor
 
 from .. import _backend as B
 from . import gauss_ans_reference as R
+from ._ans_streams import _stream, check_symbols, decode_buffers, encode_streams
 
 MAX_CHANNELS = 8  # of the params kernel: the regressor's weights live in LDS, its accumulators in registers
 MAX_CODER_CHANNELS = 16
 
 _DEVICE_TABLES: Dict[torch.device, Tuple[Tensor, Tensor]] = {}
-
-
-def _stream(t: Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _tables(dev: torch.device) -> Tuple[Tensor, Tensor]:
@@ -130,38 +127,19 @@ def _check_model(mu_q: Tensor, k: Tensor, n: int, c: int, dev: torch.device) -> 
 def gauss_ans_encode(symbols: Tensor, mu_q: Tensor, k: Tensor, stream_len: int = R.DEFAULT_STREAM_LEN) -> np.ndarray:
     """Encode device symbols uint8 [N, C] against the per-symbol model (mu_q int16, k uint8, both [N, C]) -> the container as a
     numpy uint8 array, byte-identical to ``gauss_ans_reference.encode``."""
-    if not symbols.is_cuda:
-        raise RuntimeError("the Gaussian ANS codec runs on the GPU: the symbols must be a device tensor (no CPU fallback)")
-    if symbols.dtype != torch.uint8 or symbols.dim() != 2 or not 1 <= symbols.shape[0] < 1 << 31 or not 1 <= symbols.shape[1] <= MAX_CODER_CHANNELS:
-        raise ValueError(f"symbols must be a non-empty uint8 [N, C] tensor with C <= {MAX_CODER_CHANNELS}, got {symbols.dtype} {tuple(symbols.shape)}")
-    if not 1 <= stream_len <= 1 << 24:
-        raise ValueError(f"stream_len = {stream_len}")
-    symbols = symbols.contiguous()
+    symbols = check_symbols(symbols, MAX_CODER_CHANNELS, "Gaussian ANS codec", stream_len)
     n, c = symbols.shape
-    dev = symbols.device
-    mu_cm, k_cm = _check_model(mu_q, k, n, c, dev)
-    table = _tables(dev)[0]
-    n_total = c * (-(-n // stream_len))
-    slot = int(B.query("gs_gauss_ans_slot_bytes", stream_len))
-    counts = torch.zeros((c, 256), dtype=torch.int32, device=dev)
-    cm = torch.empty((c, n), dtype=torch.uint8, device=dev)
-    scratch = torch.empty(int(B.query("gs_gauss_ans_encode_bytes", n, c, stream_len)), dtype=torch.uint8, device=dev)
-    lengths = torch.empty(n_total, dtype=torch.int32, device=dev)
-    states = torch.empty(n_total, dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        B.call("gs_ans_histogram", n, c, B.ptr(symbols), B.ptr(counts), B.ptr(cm), _stream(symbols))  # for its channel-major copy
+    mu_cm, k_cm = _check_model(mu_q, k, n, c, symbols.device)
+    table = _tables(symbols.device)[0]
+    cm = symbols.t().contiguous()  # channel-major, what the kernel streams through
+
+    def launch(scratch, lengths, states, status, stream):
         B.call("gs_gauss_ans_encode", n, c, stream_len, B.ptr(cm), B.ptr(mu_cm), B.ptr(k_cm), B.ptr(table), B.ptr(scratch),
-               scratch.numel(), B.ptr(lengths), B.ptr(states), B.ptr(status), _stream(symbols))
-        offsets = torch.zeros(n_total + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(lengths.long() + 4, dim=0, out=offsets[1:])
-        total, bad = int(offsets[-1]), int(status)  # the one read-back: the payload's size
-        if bad:
-            raise RuntimeError(f"gs_gauss_ans_encode reported status {bad} (1: model out of range, 2: slot too small)")
-        payload = torch.empty(total, dtype=torch.uint8, device=dev)
-        B.call("gs_ans_pack_slots", n_total, slot, B.ptr(scratch), B.ptr(lengths), B.ptr(states), B.ptr(offsets), B.ptr(payload),
-               total, _stream(symbols))
-    return R.build_container(c, stream_len, n, offsets.cpu().numpy(), payload.cpu().numpy())
+               scratch.numel(), B.ptr(lengths), B.ptr(states), B.ptr(status), stream)
+
+    offsets, payload = encode_streams(symbols, stream_len, int(B.query("gs_gauss_ans_slot_bytes", stream_len)), launch,
+                                      "gs_gauss_ans_encode", "1: model out of range, 2: slot too small")
+    return R.build_container(c, stream_len, n, offsets, payload)
 
 
 @torch.no_grad()
@@ -174,15 +152,11 @@ def gauss_ans_decode(blob, mu_q: Tensor, k: Tensor, device="cuda", what: str = "
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("the Gaussian ANS codec runs on the GPU (no CPU fallback); gauss_ans_reference.decode is the numpy form")
-    if c > MAX_CODER_CHANNELS or n >= 1 << 31 or stream_len > 1 << 24:
-        raise ValueError(f"{what}: C = {c}, N = {n}, S = {stream_len} is outside what the kernels take")
     if isinstance(mu_q, Tensor) and mu_q.is_cuda:
         dev = mu_q.device
+    d_off, d_payload, out = decode_buffers(n, c, stream_len, MAX_CODER_CHANNELS, offsets, payload, dev, what)
     mu_cm, k_cm = _check_model(mu_q, k, n, c, dev)
     table = _tables(dev)[0]
-    d_off = torch.from_numpy(offsets).to(dev)
-    d_payload = torch.from_numpy(np.array(payload, copy=True)).to(dev)
-    out = torch.empty((n, c), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         B.call("gs_gauss_ans_decode", n, c, stream_len, B.ptr(d_payload), d_payload.numel(), B.ptr(d_off), B.ptr(mu_cm), B.ptr(k_cm),
                B.ptr(table), B.ptr(out), _stream(out))

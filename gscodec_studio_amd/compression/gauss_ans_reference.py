@@ -2,7 +2,7 @@
 THIS MODULE IS THE DEFINITION OF THE FORMAT: the HIP coder (csrc/gauss_ans.hip behind ``gauss_ans.py``) must produce the same
 bytes, and does -- everything after ``regress_params`` is integer arithmetic, and ``regress_params`` states its float32 order.
 
-The state machine is ``ans_reference``'s: a 32-bit state in [L, 2^31), L = 2^23, byte-wise renormalisation, channel c of the N
+The streams are ``ans_reference``'s, whose encode and decode loops and container tail run here too: a 32-bit state in [L, 2^31), L = 2^23, byte-wise renormalisation, channel c of the N
 symbols cut into ``ceil(N / S)`` streams of S consecutive symbols, each stream encoded LAST SYMBOL FIRST from x = L and stored as
 its final state followed by the bytes in the order the decoder consumes them.  What differs is the model: the probability
 resolution is M = 2^P with P = 16, and EVERY SYMBOL HAS ITS OWN FREQUENCIES, given by two small integers --
@@ -52,9 +52,11 @@ from typing import Tuple
 
 import numpy as np
 
+from . import ans_reference as S  # the stream layer: one state machine, one layout, one container tail
+
 MAGIC = b"GSGANSv1"
 VERSION = 1
-STATE_LOW = 1 << 23  # L
+STATE_LOW = S.STATE_LOW  # L
 BITS = 16  # P
 DEFAULT_STREAM_LEN = 1024  # S
 N_LEVELS = 64  # K
@@ -186,11 +188,8 @@ def frequencies(mu_q, k) -> np.ndarray:
 
 def build_container(n_channels: int, stream_len: int, n: int, offsets: np.ndarray, payload: np.ndarray) -> np.ndarray:
     """Header + offset table + payload -> the file's bytes (uint8 array)."""
-    if int(offsets[-1]) >= 1 << 32:
-        raise ValueError("ANS payload of 4 GiB or more: the container's offsets are 32-bit")
     head = _HEADER.pack(MAGIC, VERSION, BITS, n_channels, stream_len, n, N_LEVELS, MEAN_STEPS, table_crc())
-    return np.concatenate([np.frombuffer(head, np.uint8), np.asarray(offsets).astype("<u4").view(np.uint8),
-                           np.asarray(payload, np.uint8)])
+    return S._container(head, offsets, payload)
 
 
 def parse_container(blob, what: str = "the buffer") -> Tuple[int, int, int, np.ndarray, np.ndarray]:
@@ -198,7 +197,7 @@ def parse_container(blob, what: str = "the buffer") -> Tuple[int, int, int, np.n
     anything a decoder must not be started on: a foreign or short file, an unknown version, P / K / F other than 16 / 64 / 8, a
     table CRC that is not this host's, offsets that decrease, point outside the file or leave a stream fewer than its 4 state
     bytes."""
-    buf = np.frombuffer(bytes(blob), np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob).view(np.uint8).ravel()
+    buf = S._as_bytes(blob)
     if buf.size < len(MAGIC) or buf[:len(MAGIC)].tobytes() != MAGIC:
         raise ValueError(NOT_OURS.format(what=what))
     if buf.size < _HEADER.size:
@@ -212,17 +211,7 @@ def parse_container(blob, what: str = "the buffer") -> Tuple[int, int, int, np.n
     if crc != table_crc():
         raise ValueError(f"{what}: the file was written against frequency tables with CRC32 {crc:08x}, this host builds "
                          f"{table_crc():08x} (its erf or pow rounds differently): decoding would give noise")
-    n_total = n_channels * (-(-n // stream_len))
-    table_end = _HEADER.size + 4 * (n_total + 1)
-    if buf.size < table_end:
-        raise ValueError(f"{what}: truncated ANS offset table ({n_total + 1} entries expected)")
-    offsets = buf[_HEADER.size:table_end].view("<u4").astype(np.int64)
-    payload = buf[table_end:]
-    if offsets[0] != 0 or np.any(np.diff(offsets) < 4):
-        raise ValueError(f"{what}: ANS stream offsets must start at 0 and leave every stream at least its 4 state bytes")
-    if offsets[-1] > payload.size:
-        raise ValueError(f"{what}: ANS stream offsets point past the end of the file ({int(offsets[-1])} > {payload.size} payload bytes)")
-    return n_channels, stream_len, n, offsets, payload
+    return (n_channels, stream_len, n) + S._split_container(buf, _HEADER.size, n_channels * (-(-n // stream_len)), what)
 
 
 def check_model(mu_q, k, n: int, n_channels: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -237,56 +226,20 @@ def check_model(mu_q, k, n: int, n_channels: int) -> Tuple[np.ndarray, np.ndarra
     return mu_q.astype(np.int64), k.astype(np.int64)
 
 
-def _streams(n: int, n_channels: int, stream_len: int):
-    n_streams = -(-n // stream_len)
-    lens = np.tile(np.minimum(stream_len, n - np.arange(n_streams, dtype=np.int64) * stream_len), n_channels)
-    return n_streams, lens
-
-
-def _pad(a: np.ndarray, n_streams: int, stream_len: int) -> np.ndarray:
-    """[N, C] -> [C * n_streams, S], zero-padded behind N."""
-    n, c = a.shape
-    p = np.zeros((c, n_streams * stream_len), a.dtype)
-    p[:, :n] = a.T
-    return p.reshape(c * n_streams, stream_len)
-
-
 def encode(symbols: np.ndarray, mu_q, k, stream_len: int = DEFAULT_STREAM_LEN) -> np.ndarray:
-    """symbols uint8 [N, C], mu_q / k integer [N, C] -> container bytes.  All streams advance together, one symbol per step."""
+    """symbols uint8 [N, C], mu_q / k integer [N, C] -> container bytes."""
     sym = np.asarray(symbols)
     if sym.dtype != np.uint8 or sym.ndim != 2 or sym.shape[0] < 1 or sym.shape[1] < 1 or stream_len < 1:
         raise ValueError("symbols must be a non-empty uint8 [N, C] array and stream_len positive")
     n, n_channels = sym.shape
     mu_q, k = check_model(mu_q, k, n, n_channels)
-    n_streams, lens = _streams(n, n_channels, stream_len)
-    p_sym, p_mu, p_k = (_pad(a, n_streams, stream_len) for a in (sym.astype(np.int64), mu_q, k))
-    rows = np.arange(n_channels * n_streams)
-    slot = slot_bytes(stream_len)
-    buf = np.zeros((rows.size, slot), np.uint8)
-    pos = np.full(rows.size, slot, np.int64)
-    x = np.full(rows.size, STATE_LOW, np.uint64)
-    for j in range(stream_len - 1, -1, -1):
-        act = j < lens
-        s = p_sym[:, j]
-        lo = cum_at(p_mu[:, j], p_k[:, j], s)
-        f = np.where(act, cum_at(p_mu[:, j], p_k[:, j], s + 1) - lo, 1).astype(np.uint64)
-        while True:
-            m = act & (x >= (f << np.uint64(31 - BITS)))
-            if not m.any():
-                break
-            if np.any(pos[m] == 0):
-                raise RuntimeError("slot full: a stream outgrew its worst-case bound")  # unreachable (module docstring)
-            pos[m] -= 1
-            buf[rows[m], pos[m]] = (x[m] & np.uint64(0xFF)).astype(np.uint8)
-            x[m] >>= np.uint64(8)
-        x = np.where(act, ((x // f) << np.uint64(BITS)) + x % f + lo.astype(np.uint64), x)
-    sizes = 4 + (slot - pos)
-    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    payload = np.empty(int(offsets[-1]), np.uint8)
-    states = x.astype("<u4").view(np.uint8).reshape(-1, 4)
-    for i in rows:
-        payload[offsets[i]:offsets[i] + 4] = states[i]
-        payload[offsets[i] + 4:offsets[i + 1]] = buf[i, pos[i]:]
+    p_sym, p_mu, p_k = (S._pad(a, stream_len) for a in (sym.astype(np.int64), mu_q, k))
+
+    def model(j):
+        lo = cum_at(p_mu[:, j], p_k[:, j], p_sym[:, j])
+        return cum_at(p_mu[:, j], p_k[:, j], p_sym[:, j] + 1) - lo, lo
+
+    offsets, payload = S._encode_streams(n, n_channels, stream_len, BITS, slot_bytes(stream_len), model)
     return build_container(n_channels, stream_len, n, offsets, payload)
 
 
@@ -295,37 +248,18 @@ def decode(blob, mu_q, k) -> np.ndarray:
     beyond it is 0 (a damaged stream gives wrong symbols, nothing else)."""
     n_channels, stream_len, n, offsets, payload = parse_container(blob)
     mu_q, k = check_model(mu_q, k, n, n_channels)
-    n_streams, lens = _streams(n, n_channels, stream_len)
-    p_mu, p_k = _pad(mu_q, n_streams, stream_len), _pad(k, n_streams, stream_len)
-    data = np.concatenate([payload, np.zeros(1, np.uint8)])  # index payload.size = the substituted 0
-    rd, end = offsets[:-1].copy(), offsets[1:]
+    p_mu, p_k = S._pad(mu_q, stream_len), S._pad(k, stream_len)
 
-    def next_byte(mask):
-        got = data[np.where(mask & (rd < end), rd, payload.size)].astype(np.uint64)
-        rd[mask] += 1
-        return got
-
-    everyone = np.ones(rd.size, bool)
-    x = np.zeros(rd.size, np.uint64)
-    for b in range(4):
-        x |= next_byte(everyone) << np.uint64(8 * b)
-    out = np.zeros((n_channels * n_streams, stream_len), np.uint8)
-    for j in range(stream_len):
-        act = j < lens
-        slot = (x & np.uint64((1 << BITS) - 1)).astype(np.int64)
-        s = np.zeros(rd.size, np.int64)
+    def lookup(j, slot):
+        s = np.zeros(slot.size, np.int64)
         step = 128
         while step >= 1:  # the last s with cum(s) <= slot: 8 steps, always
             s = np.where(cum_at(p_mu[:, j], p_k[:, j], s + step) <= slot, s + step, s)
             step >>= 1
-        out[act, j] = s[act].astype(np.uint8)
         lo = cum_at(p_mu[:, j], p_k[:, j], s)
-        f = (cum_at(p_mu[:, j], p_k[:, j], s + 1) - lo).astype(np.uint64)
-        x = np.where(act, (f * (x >> np.uint64(BITS)) + (slot - lo).astype(np.uint64)) & np.uint64(0xFFFFFFFF), x)
-        for _ in range(2):  # a valid stream needs at most two bytes per symbol
-            m = act & (x < STATE_LOW)
-            x = np.where(m, (x << np.uint64(8)) | next_byte(m), x)
-    return np.ascontiguousarray(out.reshape(n_channels, n_streams * stream_len)[:, :n].T)
+        return s, cum_at(p_mu[:, j], p_k[:, j], s + 1) - lo, lo
+
+    return S._decode_streams(offsets, payload, n, n_channels, stream_len, BITS, lookup)
 
 
 def pack_signs(signed: np.ndarray) -> np.ndarray:

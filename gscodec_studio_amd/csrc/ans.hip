@@ -5,27 +5,17 @@
 // own, and so is the bitstream: its definition is the numpy coder gscodec_studio_amd/compression/ans_reference.py, and every
 // kernel below is integer arithmetic whose output is byte-identical to it.
 //
-//   state x: 32 bits, kept in [2^23, 2^31) between symbols; probability resolution M = 2^P (8 <= P <= 14)
-//   encode s (frequency f, cumulative c):  while x >= f << (31 - P): emit x & 255, x >>= 8;   x = (x / f << P) + x % f + c
-//   decode:  slot = x & (M - 1), s = symbol_of[slot];  x = f (x >> P) + slot - c;  while x < 2^23: x = x << 8 | next byte
-//
-// Channel c of N symbols is cut into ceil(N / S) streams of S symbols and ONE LANE OWNS ONE STREAM: it walks its symbols
-// backwards (so that the decoder reads forwards), writes its bytes from the end of a private worst-case slot towards the front,
-// and records the length and the final state; a pack kernel then copies the slots to their offsets in the dense payload.  A lane
-// emits at most ceil(S P / 8) + 1 bytes: a symbol costs log2(M / f) + log2(1 + 2^-9) bits at the most (the floor in x / f loses
-// less than one part in 2^9 of a state >= 2^23 / 2^14), which is below P for every f >= 2 and exactly P for f = 1, and the state
-// itself grows by less than 8 bits over the stream.
-// Lane-per-stream with byte accesses is not the fastest shape for a GPU coder; it is the simplest one whose output order is fixed
-// by the format (a wave-interleaved layout would be a different format).
-#include "gs_common.h"
+// One stream -- state machine, geometry, slot writer, bounded reader -- is ans_stream_dev.h.  Here is the model: integer
+// frequencies uint32 [C, 256] that sum to M = 2^P per channel (8 <= P <= 14) and their prefix sums, one LDS word per symbol, and for
+// the decoder the table slot -> symbol (2^P bytes of LDS).  A lane emits at most ceil(S P / 8) + 1 bytes: a symbol costs
+// log2(M / f) + log2(1 + 2^-9) bits at the most (the floor in x / f loses less than one part in 2^9 of a state >= 2^23 / 2^14), which
+// is below P for every f >= 2 and exactly P for f = 1, and the state itself grows by less than 8 bits over the stream.
+#include "ans_stream_dev.h"
 
 namespace {
 
-constexpr uint32_t ANS_L = 1u << 23;
-constexpr uint32_t ANS_MIN_P = 8, ANS_MAX_P = 14;
-constexpr uint32_t ANS_MAX_C = 16;
+constexpr uint32_t ANS_MIN_P = 8, ANS_MAX_P = 14, ANS_MAX_C = 16, ANS_STATUS_ZERO_FREQ = 1u;
 constexpr int ANS_ENC_BLOCK = GS_WAVE; // the encoder's tables are 1 KB: one wave per workgroup spreads the streams over the CUs
-constexpr uint32_t ANS_STATUS_ZERO_FREQ = 1u, ANS_STATUS_SLOT_FULL = 2u;
 
 __host__ __device__ inline uint32_t ans_slot_bytes(uint32_t S, uint32_t P) { return (uint32_t)(((uint64_t)S * P + 7) / 8) + 8u; }
 
@@ -62,31 +52,20 @@ __global__ void __launch_bounds__(ANS_ENC_BLOCK) ans_encode_kernel(uint64_t N, u
     __syncthreads();
     const uint32_t k = blockIdx.x * ANS_ENC_BLOCK + threadIdx.x;
     if (k >= n_streams) return;
-    const uint64_t begin = (uint64_t)k * S;
-    const uint32_t len = (uint32_t)(N - begin < (uint64_t)S ? N - begin : (uint64_t)S);
-    const uint8_t *src = cm + (uint64_t)c * N + begin;
-    const uint64_t sid = (uint64_t)c * n_streams + k;
-    uint8_t *dst = scratch + sid * slot;
+    const AnsStream st = ans_stream(N, S, k, c, n_streams);
+    const uint8_t *src = cm + (uint64_t)c * N + st.begin;
+    uint8_t *dst = scratch + st.sid * slot;
     uint32_t pos = slot, x = ANS_L, bad = 0u;
-    for (uint32_t i = len; i-- > 0u;) {
+    for (uint32_t i = st.len; i-- > 0u;) {
         const uint32_t fc = s_fc[src[i]];
         uint32_t f = fc >> 16;
         if (f == 0u) { // a symbol the table does not have (the host wrapper excludes it): keep the division defined, report
             bad |= ANS_STATUS_ZERO_FREQ;
             f = 1u;
         }
-        const uint32_t x_max = f << (31u - P);
-        while (x >= x_max) {
-            if (pos > 0u) dst[--pos] = (uint8_t)(x & 0xFFu);
-            else bad |= ANS_STATUS_SLOT_FULL;
-            x >>= 8;
-        }
-        const uint32_t q = x / f;
-        x = (q << P) + (x - q * f) + (fc & 0xFFFFu);
+        ans_put(x, f, fc & 0xFFFFu, P, dst, pos, bad);
     }
-    lengths[sid] = slot - pos;
-    states[sid] = x;
-    if (bad != 0u) atomicOr(status, bad);
+    ans_finish(st.sid, slot - pos, x, bad, lengths, states, status);
 }
 
 // one wave per stream: the little-endian final state, then the slot's bytes
@@ -129,32 +108,24 @@ __global__ void __launch_bounds__(GS_BLOCK) ans_decode_kernel(uint64_t N, uint32
     __syncthreads();
     const uint32_t k = blockIdx.x * GS_BLOCK + threadIdx.x;
     if (k >= n_streams) return;
-    const uint64_t begin = (uint64_t)k * S;
-    const uint32_t len = (uint32_t)(N - begin < (uint64_t)S ? N - begin : (uint64_t)S);
-    const uint64_t sid = (uint64_t)c * n_streams + k;
-    // the stream's byte range, clamped into the payload: whatever the offsets say, no read leaves [0, payload_bytes)
-    const int64_t o0 = offsets[sid], o1 = offsets[sid + 1];
-    const uint64_t lo_b = o0 < 0 ? 0ull : ((uint64_t)o0 < payload_bytes ? (uint64_t)o0 : payload_bytes);
-    const uint64_t hi_b = o1 < 0 ? lo_b : ((uint64_t)o1 < lo_b ? lo_b : ((uint64_t)o1 < payload_bytes ? (uint64_t)o1 : payload_bytes));
-    uint64_t rd = lo_b;
-    uint32_t x = 0u;
+    const AnsStream st = ans_stream(N, S, k, c, n_streams);
+    uint64_t rd, end;
+    ans_range(payload_bytes, offsets, st.sid, rd, end);
+    uint32_t x = 0u; // the 4 state bytes
 #pragma unroll
-    for (uint32_t b = 0u; b < 4u; ++b, ++rd) x |= (rd < hi_b ? (uint32_t)payload[rd] : 0u) << (8u * b);
-    uint8_t *dst = out + begin * C + c;
-    for (uint32_t i = 0u; i < len; ++i) {
+    for (uint32_t b = 0u; b < 4u; ++b, ++rd) x |= ans_byte(payload, rd, end) << (8u * b);
+    uint8_t *dst = out + st.begin * C + c;
+#pragma unroll 1 // every step waits for the state of the one before: a second copy of the body only costs registers
+    for (uint32_t i = 0u; i < st.len; ++i) {
         const uint32_t sl = x & (M - 1u);
         const uint32_t s = s_sym[sl];
         const uint32_t fc = s_fc[s];
-        x = (fc >> 16) * (x >> P) + sl - (fc & 0xFFFFu);
-        // a valid stream needs at most two bytes here (x >= 2^9 after the step); a damaged one must not spin
-        for (uint32_t r = 0u; r < 2u && x < ANS_L; ++r, ++rd) x = (x << 8) | (rd < hi_b ? (uint32_t)payload[rd] : 0u);
+        x = ans_advance(x, fc >> 16, fc & 0xFFFFu, sl, P, payload, rd, end);
         dst[(uint64_t)i * C] = (uint8_t)s;
     }
 }
 
-bool ans_shape_ok(uint64_t N, uint32_t C, uint32_t S, uint32_t P) {
-    return N >= 1 && N < (1ull << 32) && C >= 1 && C <= ANS_MAX_C && S >= 1 && S <= (1u << 24) && P >= ANS_MIN_P && P <= ANS_MAX_P;
-}
+bool ans_shape_ok(uint64_t N, uint32_t C, uint32_t S, uint32_t P) { return ans_shape_ok(N, C, S, P, ANS_MAX_C, ANS_MIN_P, ANS_MAX_P); }
 
 } // namespace
 
@@ -192,33 +163,28 @@ extern "C" int32_t gs_ans_encode(uint64_t N, uint32_t C, uint32_t S, uint32_t P,
     return 0;
 }
 
-extern "C" int32_t gs_ans_pack(uint64_t n_streams_total, uint32_t S, uint32_t P, const uint8_t *scratch, const uint32_t *lengths,
-                               const uint32_t *states, const int64_t *offsets, uint8_t *payload, uint64_t payload_bytes,
-                               gs_stream_t stream) {
-    if (n_streams_total == 0) return 0;
-    GS_CHECK_ARG(scratch && lengths && states && offsets && payload, "null pointer");
-    GS_CHECK_ARG(S >= 1 && S <= (1u << 24) && P >= ANS_MIN_P && P <= ANS_MAX_P, "need 1 <= S <= 2^24, 8 <= P <= 14");
-    constexpr uint32_t per_block = GS_BLOCK / GS_WAVE;
-    GS_CHECK_ARG(gs_div_up(n_streams_total, per_block) < (1ull << 31), "too many streams");
-    hipLaunchKernelGGL(ans_pack_kernel, dim3(gs_div_up(n_streams_total, per_block)), dim3(GS_BLOCK), 0, (hipStream_t)stream,
-                       n_streams_total, ans_slot_bytes(S, P), scratch, lengths, states, offsets, payload, payload_bytes);
-    GS_CHECK_LAUNCH();
-    return 0;
-}
-
-// the same copy for a caller that sizes its slots itself (gauss_ans.hip: P = 16, its own worst case)
+// the pack launch, for either model: the slot size is an argument; gs_ans_pack gives it as this file's (S, P)
 extern "C" int32_t gs_ans_pack_slots(uint64_t n_streams_total, uint32_t slot_bytes, const uint8_t *scratch, const uint32_t *lengths,
                                      const uint32_t *states, const int64_t *offsets, uint8_t *payload, uint64_t payload_bytes,
                                      gs_stream_t stream) {
     if (n_streams_total == 0) return 0;
     GS_CHECK_ARG(scratch && lengths && states && offsets && payload, "null pointer");
     GS_CHECK_ARG(slot_bytes >= 1, "slot_bytes must be positive");
-    constexpr uint32_t per_block = GS_BLOCK / GS_WAVE;
-    GS_CHECK_ARG(gs_div_up(n_streams_total, per_block) < (1ull << 31), "too many streams");
-    hipLaunchKernelGGL(ans_pack_kernel, dim3(gs_div_up(n_streams_total, per_block)), dim3(GS_BLOCK), 0, (hipStream_t)stream,
-                       n_streams_total, slot_bytes, scratch, lengths, states, offsets, payload, payload_bytes);
+    const uint32_t blocks = gs_div_up(n_streams_total, GS_BLOCK / GS_WAVE); // a wave per stream
+    GS_CHECK_ARG(blocks < (1ull << 31), "too many streams");
+    hipLaunchKernelGGL(ans_pack_kernel, dim3(blocks), dim3(GS_BLOCK), 0, (hipStream_t)stream, n_streams_total, slot_bytes, scratch,
+                       lengths, states, offsets, payload, payload_bytes);
     GS_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int32_t gs_ans_pack(uint64_t n_streams_total, uint32_t S, uint32_t P, const uint8_t *scratch, const uint32_t *lengths,
+                               const uint32_t *states, const int64_t *offsets, uint8_t *payload, uint64_t payload_bytes,
+                               gs_stream_t stream) {
+    if (n_streams_total == 0) return 0;
+    GS_CHECK_ARG(scratch && lengths && states && offsets && payload, "null pointer");
+    GS_CHECK_ARG(S >= 1 && S <= (1u << 24) && P >= ANS_MIN_P && P <= ANS_MAX_P, "need 1 <= S <= 2^24, 8 <= P <= 14");
+    return gs_ans_pack_slots(n_streams_total, ans_slot_bytes(S, P), scratch, lengths, states, offsets, payload, payload_bytes, stream);
 }
 
 extern "C" int32_t gs_ans_decode(uint64_t N, uint32_t C, uint32_t S, uint32_t P, const uint8_t *payload, uint64_t payload_bytes,

@@ -8,7 +8,6 @@
 //
 //   model of a symbol: mu_q (mean on a grid of 8 steps per symbol, 0..2040), k (scale level 0..63), one table G uint16 [64, 4073]
 //   cum(0) = 0, cum(256) = 2^16, cum(s) = G[k][8 s - 4 - mu_q + 2036] + s;  f(s) = cum(s + 1) - cum(s) >= 1 for every s
-//   state machine, stream layout and slots: as ans.hip, at P = 16
 //
 // gauss_ans_params_kernel: one lane per splat runs the regressor's MLP (Linear(48, 5C), ReLU, Linear(5C, 2C)) on the features the
 // hash-grid encoder wrote, in the one float32 order regress_params states (accumulator starts at the bias, inputs ascending, every
@@ -16,27 +15,20 @@
 // two normalisations and the quantisation to (mu_q, k).  The weights are wave-uniform LDS reads (broadcasts).  A splat's model thus
 // depends on its features, the stored weights and mins / maxs alone -- not on a GEMM library's algorithm choice, N or the launch shape.
 //
-// Encoder and decoder are one lane per stream, as in ans.hip; G (521 KB) is read from global memory and lives in L2.  A lane emits at
-// most 2 S + S / 512 bytes: a symbol costs log2(2^16 / f) + log2(1 + 2^-7) bits at the most (the floor in x / f loses less than one
-// part in 2^7 of a quotient >= 2^7) and the state ends where it began or above; the slot is 2 S + S / 512 + 8 bytes.  The decoder
-// finds the symbol by an 8-step binary search on cum: a fixed trip count, nothing to spin on in a damaged stream.
-#include "gs_common.h"
-
-#include <cmath>
+// Encoder and decoder are ans_stream_dev.h's streams at P = 16 under this model; G (521 KB) is read from global memory and lives
+// in L2.  A lane emits at most 2 S + S / 512 bytes (a symbol costs at most 16 + log2(1 + 2^-7) bits: gauss_ans_reference.py derives
+// it); the slot is that + 8.  The decoder's 8-step binary search on cum has a fixed trip count: nothing to spin on in a damaged stream.
+#include "ans_stream_dev.h"
 
 namespace {
 
-constexpr uint32_t GA_L = 1u << 23;
-constexpr uint32_t GA_P = 16;
-constexpr uint32_t GA_K = 64;
+constexpr uint32_t GA_P = 16, GA_K = 64, GA_WIDTH = 4073;
 constexpr int32_t GA_MU_MAX = 2040, GA_T_MAX = 2036;
-constexpr uint32_t GA_WIDTH = 4073;
 constexpr uint32_t GA_MAX_C = 8; // of the params kernel (weights in LDS, accumulators in registers)
 constexpr uint32_t GA_MAX_C_CODER = 16;
 constexpr uint32_t GA_IN = 48, GA_HID_PER_C = 5;
 constexpr float GA_SCALE_MIN = 1e-9f;
-constexpr int GA_ENC_BLOCK = GS_WAVE;
-constexpr uint32_t GA_STATUS_MODEL = 1u, GA_STATUS_SLOT_FULL = 2u;
+constexpr uint32_t GA_STATUS_MODEL = 1u;
 
 __host__ __device__ inline uint32_t ga_slot_bytes(uint32_t S) { return 2u * S + S / 512u + 8u; }
 
@@ -125,22 +117,20 @@ __global__ void __launch_bounds__(GS_BLOCK) gauss_ans_params_kernel(uint64_t N, 
     }
 }
 
-__global__ void __launch_bounds__(GA_ENC_BLOCK) gauss_ans_encode_kernel(uint64_t N, uint32_t S, uint32_t n_streams,
-                                                                        const uint8_t *__restrict__ cm, const int16_t *__restrict__ mu_q,
-                                                                        const uint8_t *__restrict__ k_lv, const uint16_t *__restrict__ G,
-                                                                        uint8_t *__restrict__ scratch, uint32_t slot,
-                                                                        uint32_t *__restrict__ lengths, uint32_t *__restrict__ states,
-                                                                        uint32_t *__restrict__ status) {
+__global__ void __launch_bounds__(GS_WAVE) gauss_ans_encode_kernel(uint64_t N, uint32_t S, uint32_t n_streams,
+                                                                   const uint8_t *__restrict__ cm, const int16_t *__restrict__ mu_q,
+                                                                   const uint8_t *__restrict__ k_lv, const uint16_t *__restrict__ G,
+                                                                   uint8_t *__restrict__ scratch, uint32_t slot,
+                                                                   uint32_t *__restrict__ lengths, uint32_t *__restrict__ states,
+                                                                   uint32_t *__restrict__ status) {
     const uint32_t c = blockIdx.y;
-    const uint32_t st = blockIdx.x * GA_ENC_BLOCK + threadIdx.x;
-    if (st >= n_streams) return;
-    const uint64_t begin = (uint64_t)st * S;
-    const uint32_t len = (uint32_t)(N - begin < (uint64_t)S ? N - begin : (uint64_t)S);
-    const uint64_t base = (uint64_t)c * N + begin;
-    const uint64_t sid = (uint64_t)c * n_streams + st;
-    uint8_t *dst = scratch + sid * slot;
-    uint32_t pos = slot, x = GA_L, bad = 0u;
-    for (uint32_t i = len; i-- > 0u;) {
+    const uint32_t k = blockIdx.x * GS_WAVE + threadIdx.x;
+    if (k >= n_streams) return;
+    const AnsStream st = ans_stream(N, S, k, c, n_streams);
+    const uint64_t base = (uint64_t)c * N + st.begin;
+    uint8_t *dst = scratch + st.sid * slot;
+    uint32_t pos = slot, x = ANS_L, bad = 0u;
+    for (uint32_t i = st.len; i-- > 0u;) {
         const uint32_t s = cm[base + i];
         int32_t mq = mu_q[base + i];
         uint32_t kk = k_lv[base + i];
@@ -150,19 +140,9 @@ __global__ void __launch_bounds__(GA_ENC_BLOCK) gauss_ans_encode_kernel(uint64_t
             kk = kk >= GA_K ? GA_K - 1u : kk;
         }
         const uint32_t lo = ga_cum(G, kk, mq, s);
-        const uint32_t f = ga_cum(G, kk, mq, s + 1u) - lo; // 1 <= f < 2^16
-        const uint32_t x_max = f << (31u - GA_P);
-        while (x >= x_max) {
-            if (pos > 0u) dst[--pos] = (uint8_t)(x & 0xFFu);
-            else bad |= GA_STATUS_SLOT_FULL;
-            x >>= 8;
-        }
-        const uint32_t q = x / f;
-        x = (q << GA_P) + (x - q * f) + lo;
+        ans_put(x, ga_cum(G, kk, mq, s + 1u) - lo, lo, GA_P, dst, pos, bad); // 1 <= f < 2^16
     }
-    lengths[sid] = slot - pos;
-    states[sid] = x;
-    if (bad != 0u) atomicOr(status, bad);
+    ans_finish(st.sid, slot - pos, x, bad, lengths, states, status);
 }
 
 __global__ void __launch_bounds__(GS_WAVE) gauss_ans_decode_kernel(uint64_t N, uint32_t C, uint32_t S, uint32_t n_streams,
@@ -171,22 +151,17 @@ __global__ void __launch_bounds__(GS_WAVE) gauss_ans_decode_kernel(uint64_t N, u
                                                                    const uint8_t *__restrict__ k_lv, const uint16_t *__restrict__ G,
                                                                    uint8_t *__restrict__ out) {
     const uint32_t c = blockIdx.y;
-    const uint32_t st = blockIdx.x * GS_WAVE + threadIdx.x;
-    if (st >= n_streams) return;
-    const uint64_t begin = (uint64_t)st * S;
-    const uint32_t len = (uint32_t)(N - begin < (uint64_t)S ? N - begin : (uint64_t)S);
-    const uint64_t base = (uint64_t)c * N + begin;
-    const uint64_t sid = (uint64_t)c * n_streams + st;
-    // the stream's byte range, clamped into the payload: whatever the offsets say, no read leaves [0, payload_bytes)
-    const int64_t o0 = offsets[sid], o1 = offsets[sid + 1];
-    const uint64_t lo_b = o0 < 0 ? 0ull : ((uint64_t)o0 < payload_bytes ? (uint64_t)o0 : payload_bytes);
-    const uint64_t hi_b = o1 < 0 ? lo_b : ((uint64_t)o1 < lo_b ? lo_b : ((uint64_t)o1 < payload_bytes ? (uint64_t)o1 : payload_bytes));
-    uint64_t rd = lo_b;
-    uint32_t x = 0u;
+    const uint32_t k = blockIdx.x * GS_WAVE + threadIdx.x;
+    if (k >= n_streams) return;
+    const AnsStream st = ans_stream(N, S, k, c, n_streams);
+    const uint64_t base = (uint64_t)c * N + st.begin;
+    uint64_t rd, end;
+    ans_range(payload_bytes, offsets, st.sid, rd, end);
+    uint32_t x = 0u; // the 4 state bytes
 #pragma unroll
-    for (uint32_t b = 0u; b < 4u; ++b, ++rd) x |= (rd < hi_b ? (uint32_t)payload[rd] : 0u) << (8u * b);
-    uint8_t *dst = out + begin * C + c;
-    for (uint32_t i = 0u; i < len; ++i) {
+    for (uint32_t b = 0u; b < 4u; ++b, ++rd) x |= ans_byte(payload, rd, end) << (8u * b);
+    uint8_t *dst = out + st.begin * C + c;
+    for (uint32_t i = 0u; i < st.len; ++i) {
         int32_t mq = mu_q[base + i];
         uint32_t kk = k_lv[base + i];
         mq = mq < 0 ? 0 : (mq > GA_MU_MAX ? GA_MU_MAX : mq);
@@ -197,17 +172,12 @@ __global__ void __launch_bounds__(GS_WAVE) gauss_ans_decode_kernel(uint64_t N, u
         for (uint32_t step = 128u; step >= 1u; step >>= 1)
             if (ga_cum_mid(G, kk, mq, s + step) <= sl) s += step;
         const uint32_t lo = ga_cum(G, kk, mq, s);
-        const uint32_t f = ga_cum(G, kk, mq, s + 1u) - lo;
-        x = f * (x >> GA_P) + sl - lo;
-        // a valid stream needs at most two bytes here (x >= 2^7 after the step); a damaged one must not spin
-        for (uint32_t r = 0u; r < 2u && x < GA_L; ++r, ++rd) x = (x << 8) | (rd < hi_b ? (uint32_t)payload[rd] : 0u);
+        x = ans_advance(x, ga_cum(G, kk, mq, s + 1u) - lo, lo, sl, GA_P, payload, rd, end);
         dst[(uint64_t)i * C] = (uint8_t)s;
     }
 }
 
-bool ga_shape_ok(uint64_t N, uint32_t C, uint32_t S) {
-    return N >= 1 && N < (1ull << 32) && C >= 1 && C <= GA_MAX_C_CODER && S >= 1 && S <= (1u << 24);
-}
+bool ga_shape_ok(uint64_t N, uint32_t C, uint32_t S) { return ans_shape_ok(N, C, S, GA_P, GA_MAX_C_CODER, GA_P, GA_P); }
 
 template <int C>
 void ga_params_launch(uint64_t N, const float *feat, const float *w1, const float *b1, const float *w2, const float *b2,
@@ -257,7 +227,7 @@ extern "C" int32_t gs_gauss_ans_encode(uint64_t N, uint32_t C, uint32_t S, const
     GS_CHECK_ARG(((uintptr_t)mu_q % 2u) == 0 && ((uintptr_t)table % 2u) == 0, "mu_q and table must be 2-byte aligned");
     GS_CHECK_ARG(scratch_bytes >= gs_gauss_ans_encode_bytes(N, C, S), "scratch smaller than gs_gauss_ans_encode_bytes");
     const uint32_t n_streams = (uint32_t)((N + S - 1) / S);
-    hipLaunchKernelGGL(gauss_ans_encode_kernel, dim3(gs_div_up(n_streams, GA_ENC_BLOCK), C), dim3(GA_ENC_BLOCK), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(gauss_ans_encode_kernel, dim3(gs_div_up(n_streams, GS_WAVE), C), dim3(GS_WAVE), 0, (hipStream_t)stream,
                        N, S, n_streams, channel_major, mu_q, k, table, scratch, ga_slot_bytes(S), lengths, states, status);
     GS_CHECK_LAUNCH();
     return 0;

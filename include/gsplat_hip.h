@@ -935,6 +935,8 @@ int32_t gs_png_unfilter(const uint8_t *data, uint32_t h, uint32_t stride, uint32
  *   state 32 bits, lower bound 2^23, renormalised one byte at a time; probability resolution 2^P, 8 <= P <= 14;
  *   channel c of the N symbols (8 bits each) is cut into n_streams = ceil(N / S) streams of S symbols, stream k = symbols
  *   [k S, min(N, (k + 1) S)); stream index sid = c * n_streams + k; a stream is encoded last symbol first, so it decodes forward.
+ * All of that -- state machine, stream geometry, the slot writer, the bounded reader -- is one stream layer (ans_stream_dev.h) that
+ * the Gaussian route below runs too; this section's model is a static table per channel.
  * freq / cum: uint32 [C, 256] integer frequencies (sum 2^P per channel) and their exclusive prefix sums, derived on the host.
  *
  * gs_ans_histogram: symbols uint8 [N, C] -> counts uint32 [C, 256] (ADDED to: the caller zero-fills), LDS histogram per
@@ -945,8 +947,9 @@ int32_t gs_png_unfilter(const uint8_t *data, uint32_t h, uint32_t stride, uint32
  *   = bytes written, states = final state; the bytes of stream sid are scratch[(sid + 1) slot - lengths[sid], (sid + 1) slot), in
  *   the order the decoder consumes them.  *status (device uint32, zero-filled by the caller) gets bit 0 set when a symbol with
  *   frequency 0 was met and bit 1 when a slot was too small (neither write leaves the slot).
- * gs_ans_pack: after an exclusive scan of (4 + lengths) into offsets (int64 [n + 1], device): payload[offsets[sid]...] = the
- *   little-endian final state, then the stream's bytes.  A stream that would not fit payload_bytes is skipped.
+ * gs_ans_pack_slots: after an exclusive scan of (4 + lengths) into offsets (int64 [n + 1], device): payload[offsets[sid]...] = the
+ *   little-endian final state, then the stream's bytes, out of slots of slot_bytes each -- the one pack launch, for either model.
+ *   A stream that would not fit payload_bytes is skipped.  gs_ans_pack: the same with slot_bytes = gs_ans_slot_bytes(S, P).
  * gs_ans_decode: payload + offsets (int64 [C n_streams + 1], device) -> symbols uint8 [N, C] (the layout gs_grid_dequantize
  *   reads).  Every read is bounded to the stream's byte range clamped to [0, payload_bytes]; beyond it the byte is 0: a damaged
  *   file decodes to wrong symbols, never to an out-of-range access.  P <= 14: the slot-to-symbol table (2^P bytes) lives in LDS. */
@@ -961,13 +964,12 @@ int32_t gs_ans_pack(uint64_t n_streams_total, uint32_t S, uint32_t P, const uint
                     const uint32_t *states, const int64_t *offsets, uint8_t *payload, uint64_t payload_bytes, gs_stream_t stream);
 int32_t gs_ans_decode(uint64_t N, uint32_t C, uint32_t S, uint32_t P, const uint8_t *payload, uint64_t payload_bytes,
                       const int64_t *offsets, const uint32_t *freq, const uint32_t *cum, uint8_t *symbols, gs_stream_t stream);
-/* gs_ans_pack for a caller that sizes its slots itself: slot_bytes instead of (S, P). */
 int32_t gs_ans_pack_slots(uint64_t n_streams_total, uint32_t slot_bytes, const uint8_t *scratch, const uint32_t *lengths,
                           const uint32_t *states, const int64_t *offsets, uint8_t *payload, uint64_t payload_bytes, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
- * Hash-grid Gaussian route of the entropy coder (gauss_ans.hip): the same state machine, stream layout and slots as above at
- * P = 16, but EVERY SYMBOL HAS ITS OWN FREQUENCIES, given by mu_q (the mean on a grid of 8 steps per symbol, 0..2040) and k (a scale
+ * Hash-grid Gaussian route of the entropy coder (gauss_ans.hip): the stream layer of the section above (ans_stream_dev.h) at
+ * P = 16, under another model: EVERY SYMBOL HAS ITS OWN FREQUENCIES, given by mu_q (the mean on a grid of 8 steps per symbol, 0..2040) and k (a scale
  * level, 0..63: sigma_k = 2^((k - 22) / 5) symbol widths) through one table G uint16 [64, 4073]:
  *   cum(0) = 0, cum(256) = 2^16, cum(s) = G[k][clamp(8 s - 4 - mu_q, -2036, 2036) + 2036] + s for s = 1..255, f(s) = cum(s + 1) - cum(s)
  * (every f >= 1: any model codes any symbol).  The format's definition is gscodec_studio_amd/compression/gauss_ans_reference.py,
@@ -980,7 +982,7 @@ int32_t gs_ans_pack_slots(uint64_t n_streams_total, uint32_t slot_bytes, const u
  *   mu_norm > 0, 2040 where mu_norm >= 255, else rint(8 mu_norm); k = the number of thresholds [63] <= sigma_norm.  Writes mu_q
  *   int16 [C, N] and k uint8 [C, N] (channel-major, what the coder reads); miu / sigma (float [N, C], may be NULL) receive the
  *   float values.  Inference only.  1 <= C <= 8.
- * gs_gauss_ans_encode: as gs_ans_encode, on channel_major symbols uint8 [C, N] (gs_ans_histogram's copy); slots of
+ * gs_gauss_ans_encode: as gs_ans_encode, on channel_major symbols uint8 [C, N] (the transposed symbols); slots of
  *   gs_gauss_ans_slot_bytes(S) = 2 S + S / 512 + 8 bytes (the worst case at P = 16 plus 8) in scratch (>= gs_gauss_ans_encode_bytes);
  *   gs_ans_pack_slots copies them.  *status (device uint32, zero-filled by the caller): bit 0 = a mu_q or k out of range was met
  *   (clamped), bit 1 = a slot was too small (no write leaves the slot).  table: G on the device, 2-byte aligned.

@@ -2,6 +2,7 @@
 (gscodec_studio_amd/compression/ans_reference.py), the container's validation (host checks; nothing is launched) and the size of
 the files against the empirical entropy."""
 import io
+import os
 import struct
 
 import numpy as np
@@ -137,6 +138,20 @@ def test_damaged_payload_decodes_to_something():
     bad[-40:] = 255 - bad[-40:]
     out = R.decode(bad, prob)
     assert out.shape == sym.shape and out.dtype == np.uint8 and np.array_equal(out[:192], sym[:192])
+
+
+def test_container_bytes_are_pinned():
+    """The whole file, byte for byte, for N around one and several streams of S = 5 at P = 8, 12 and 14: arrays recorded by
+    tests/golden/make_golden_ans_containers.py from the coder as it stood before the stream layer was shared."""
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ans_containers.npz"))
+    for n in (1, 4, 5, 6, 17):
+        sym, prob = g[f"f.{n}.sym"], g[f"f.{n}.prob"]
+        assert sym.shape == (n, 3) and sym.dtype == np.uint8 and prob.dtype == np.float32
+        for bits in (8, 12, 14):
+            blob = g[f"f.{n}.{bits}.blob"]
+            got = R.encode(sym, prob, stream_len=5, bits=bits)
+            assert got.dtype == np.uint8 and np.array_equal(got, blob), (n, bits)
+            assert np.array_equal(R.decode(blob, prob), sym), (n, bits)
 
 
 @pytest.mark.parametrize("kind", DISTRIBUTIONS)

@@ -172,6 +172,23 @@ def test_damaged_payload_decodes_to_something():
     assert out.shape == sym.shape and out.dtype == np.uint8 and np.array_equal(out[:192], sym[:192])
 
 
+def test_container_bytes_are_pinned():
+    """The whole file, byte for byte: N around one and several streams of S = 5, a model under which every symbol has frequency 1
+    (each full stream fills its worst case of 2 S + S // 512 bytes) and S = 1024 with N = 1025 -- arrays recorded by
+    tests/golden/make_golden_ans_containers.py from the coder as it stood before the stream layer was shared."""
+    g = np.load(os.path.join(os.path.dirname(GOLDEN), "ans_containers.npz"))
+    for name in ("1", "4", "5", "6", "17", "freq1", "long"):
+        sym, mu_q, k, blob = (g[f"g.{name}.{a}"] for a in ("sym", "mu_q", "k", "blob"))
+        s_len = int(g[f"g.{name}.stream_len"])
+        n = {"freq1": 17, "long": 1025}.get(name) or int(name)
+        assert sym.shape == (n, 2) and sym.dtype == np.uint8 and s_len == (1024 if name == "long" else 5)
+        got = R.encode(sym, mu_q, k, stream_len=s_len)
+        assert got.dtype == np.uint8 and np.array_equal(got, blob), name
+        assert np.array_equal(R.decode(blob, mu_q, k), sym), name
+    sizes = np.diff(R.parse_container(g["g.freq1.blob"])[3]) - 4
+    assert np.all(sizes[[0, 1, 2, 4, 5, 6]] == R.slot_bytes(5) - 8)  # the full streams: the bound is met
+
+
 def _phi(z):
     return 0.5 * (1.0 + np.vectorize(math.erf)(z / math.sqrt(2.0)))
 

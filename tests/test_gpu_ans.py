@@ -103,6 +103,61 @@ def test_damaged_payload_stays_in_bounds_and_matches_the_numpy_decoder():
     assert np.array_equal(out, R.decode(bad, prob)) and not np.array_equal(out, sym)
 
 
+def test_truncated_payload_stays_in_bounds():
+    """The kernel handed 2500 payload bytes fewer than the offsets describe clamps every stream's range to what it was given: the
+    same symbols as the numpy decoder on a payload whose missing tail reads as 0 (the reader is the Gaussian route's too)."""
+    from gscodec_studio_amd import _backend as B
+    from gscodec_studio_amd.compression import ans_reference as R
+
+    sym = draw("uniform", 70 * 64 + 9, 2)
+    prob = probabilities(sym)
+    blob = R.encode(sym, prob, stream_len=64)
+    bits, c, s_len, n, offsets, payload = R.parse_container(blob)
+    keep = payload.size - 2500  # some three dozen streams of about 67 bytes lie behind it
+    zeroed = blob.copy()
+    zeroed[-2500:] = 0
+    freq = R.normalize_frequencies(prob, bits)
+    d_payload, d_off = T(np.array(payload[:keep])), T(offsets)
+    d_freq, d_cum = T(freq.view(np.int32)), T(R.cumulative(freq).view(np.int32))
+    got = torch.full((n, c), 7, dtype=torch.uint8, device="cuda")
+    B.call("gs_ans_decode", n, c, s_len, bits, B.ptr(d_payload), keep, B.ptr(d_off), B.ptr(d_freq), B.ptr(d_cum), B.ptr(got),
+           torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(N(got), R.decode(zeroed, prob))
+
+
+def test_the_two_pack_entries_agree():
+    """One gs_ans_encode, packed through gs_ans_pack(S, P) and through gs_ans_pack_slots(gs_ans_slot_bytes(S, P)): the same
+    payload, and the numpy coder's."""
+    from gscodec_studio_amd import _backend as B
+    from gscodec_studio_amd.compression import ans_reference as R
+
+    n, c, S, P = 3 * 64 + 5, 2, 64, 14
+    sym = _mixed(n, c, seed=11)
+    prob = probabilities(sym)
+    want_offsets, want_payload = R.parse_container(R.encode(sym, prob, stream_len=S, bits=P))[4:]
+    freq = R.normalize_frequencies(prob, P)
+    n_total = c * (-(-n // S))
+    slot = int(B.query("gs_ans_slot_bytes", S, P))
+    assert slot == R.slot_bytes(S, P) and int(B.query("gs_ans_encode_bytes", n, c, S, P)) == n_total * slot
+    stream = torch.cuda.current_stream().cuda_stream
+    cm, d_freq, d_cum = T(np.ascontiguousarray(sym.T)), T(freq.view(np.int32)), T(R.cumulative(freq).view(np.int32))
+    scratch = torch.zeros(n_total * slot, dtype=torch.uint8, device="cuda")
+    lengths, states = (torch.zeros(n_total, dtype=torch.int32, device="cuda") for _ in range(2))
+    status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    B.call("gs_ans_encode", n, c, S, P, B.ptr(cm), B.ptr(d_freq), B.ptr(d_cum), B.ptr(scratch), scratch.numel(), B.ptr(lengths),
+           B.ptr(states), B.ptr(status), stream)
+    offsets = torch.zeros(n_total + 1, dtype=torch.int64, device="cuda")
+    torch.cumsum(lengths.long() + 4, dim=0, out=offsets[1:])
+    assert int(status) == 0 and np.array_equal(N(offsets), want_offsets)
+    total = int(offsets[-1])
+    by_sp, by_slot = (torch.full((total,), 0xA5, dtype=torch.uint8, device="cuda") for _ in range(2))
+    B.call("gs_ans_pack", n_total, S, P, B.ptr(scratch), B.ptr(lengths), B.ptr(states), B.ptr(offsets), B.ptr(by_sp), total, stream)
+    B.call("gs_ans_pack_slots", n_total, slot, B.ptr(scratch), B.ptr(lengths), B.ptr(states), B.ptr(offsets), B.ptr(by_slot), total, stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(N(by_sp), N(by_slot)) and np.array_equal(N(by_sp), want_payload)
+
+
 @pytest.mark.parametrize("kind", DISTRIBUTIONS)
 def test_size_bound_hip_coder(kind):
     """file bytes <= 1.01 x empirical entropy + 8 bytes per stream + 64, on 16384 symbols at S = 1024 (by byte identity the

@@ -168,7 +168,7 @@ def main():
 
             def read():
                 for k in vals:
-                    dequantize_grid([torch.from_numpy(png_read(os.path.join(d, f"{k}.png")))], {**meta[k], "quantization": 8})
+                    dequantize_grid([torch.from_numpy(png_read(os.path.join(d, f"{k}.png")))], {**meta[k], "quantization": 8}, device=dev)
 
             tw = host_ms(write, max(2, a.rounds // 2))
             tr = host_ms(read, max(2, a.rounds // 2))
