@@ -211,15 +211,26 @@ _LAYOUT_GUARDS = {
 }
 
 
+def _check_layout(L: ctypes.CDLL, cls: type, name: str, entry: str, guarded: Tuple[str, ...]) -> None:
+    want = (ctypes.c_uint64 * 64)()
+    m = int(getattr(L, entry)(want, 64))
+    mine = [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in guarded]
+    if m != len(mine) or list(want[:m]) != mine:
+        raise ImportError(f"gscodec_studio_amd: {name}: the class derived from the header does not match the library's "
+                          f"struct layout ({entry}: {list(want[:m])} vs {mine}); rebuild with `make -C gscodec_studio_amd/csrc`")
+
+
 def _check_layouts(L: ctypes.CDLL, structs: Dict[str, type]) -> None:
     for name, (entry, guarded) in _LAYOUT_GUARDS.items():
-        cls = structs[name]  # (for HEADER_PATH: the very class objects _step, _wrapper and ops hold)
-        want = (ctypes.c_uint64 * 64)()
-        m = int(getattr(L, entry)(want, 64))
-        mine = [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in guarded]
-        if m != len(mine) or list(want[:m]) != mine:
-            raise ImportError(f"gscodec_studio_amd: {name}: the class derived from the header does not match the library's "
-                              f"struct layout ({entry}: {list(want[:m])} vs {mine}); rebuild with `make -C gscodec_studio_amd/csrc`")
+        _check_layout(L, structs[name], name, entry, guarded)  # (for HEADER_PATH: the very class objects _step, _wrapper and ops hold)
+
+
+def guarded_struct(name: str, entry: str, guarded: Tuple[str, ...], path: str = HEADER_PATH) -> type:
+    """``struct(name)`` after the same check against the library's ``entry`` (sizeof, then the offsetof of ``guarded``): for a
+    descriptor whose module guards it itself, before its first table, instead of ``lib()`` at load (``_LAYOUT_GUARDS``)."""
+    cls = struct(name, path)
+    _check_layout(lib(), cls, name, entry, tuple(guarded))
+    return cls
 
 
 def check_layouts(path: str = HEADER_PATH) -> None:

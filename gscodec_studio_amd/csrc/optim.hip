@@ -1,4 +1,5 @@
-// optim.hip -- Adam and SelectiveAdam over several tensors in one launch (gs_adam_multi).
+// optim.hip -- Adam and SelectiveAdam over several tensors in one launch (gs_adam_multi), and SparseAdam over several tensors
+// that share one index list (gs_sparse_adam_multi, second half of the file).
 //
 // Dense mode: torch.optim.adam._single_tensor_adam (non-capturable) per element, in its order of operations:
 //   m = lerp(m, g, 1 - b1)            (ATen's two-branch lerp)
@@ -174,6 +175,89 @@ void div_magic(uint32_t dv, uint32_t &magic, uint32_t &sh1, uint32_t &sh2) {
     sh2 = l > 0 ? l - 1 : 0u;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// SparseAdam (gs_sparse_adam_multi): torch.optim._functional.sparse_adam per element of the rows that have a gradient, in its
+// order of operations (every line one float32 rounding):
+//   g  = the sum of the duplicates' values
+//   d1 = (g - m) * w1            d2 = (g * g - v) * w2
+//   m' = m + d1                  v' = v + d2
+//   p' = p + s * ((d1 + m) / (sqrt(d2 + v) + eps))
+// with w1 = 1 - beta1, w2 = 1 - beta2 and s = -(lr * sqrt(1 - beta2^step) / (1 - beta1^step)) computed by the host in double and
+// rounded to float.  Rows without an index are neither read nor written.
+//
+// Mapping: one lane per (sorted position k, column c), element e = k * row_width + c (k by the magic division above), so the
+// lanes of a row are contiguous in values, p, m and v alike.  sorted_ids ascends; a lane whose id equals its predecessor's is not
+// the head of its run and returns.  A head lane walks forward over its run and adds values[perm[j] * row_width + c] in the order
+// of j: the sort behind sorted_ids / perm is stable on (id, position), so a run is summed in ascending position in values,
+// starting from its first value -- THE defined order of the duplicates' sum (torch's own coalesce() uses another for three or
+// more).  A run of length r costs r serial loads per column; the trainers produce r <= the number of cameras, so there is no
+// second path for long runs.  Every (row, column) is written by exactly one lane: no atomics, results bit-identical from run to
+// run and independent of the grid.  Chunks (GS_BLOCK elements) of all the tensors form one index space that a device-sized grid
+// strides over, as above.  An id outside [0, rows) or a perm entry outside [0, nnz) is skipped, never used as an address.
+struct SparseAdamTensor {
+    float *p, *m, *v;
+    const float *g;            // values [nnz, row_width]
+    uint32_t row_width, n;     // n = nnz * row_width elements
+    uint32_t magic, sh1, sh2;  // e / row_width, as in AdamTensor
+    float w1, w2, s, eps;
+};
+
+struct SparseAdamMultiArgs {
+    uint32_t n;
+    uint32_t nnz;
+    uint64_t rows;
+    const int64_t *ids;   // [nnz] ascending
+    const int32_t *perm;  // [nnz] or null (identity)
+    uint32_t chunk_end[GS_ADAM_MULTI_MAX];
+    SparseAdamTensor t[GS_ADAM_MULTI_MAX];
+};
+
+GS_DEV void sparse_adam_one(float &p, float g, float &m, float &v, const SparseAdamTensor &d) {
+    GS_FP_STRICT
+    const float d1 = (g - m) * d.w1;
+    const float d2 = (g * g - v) * d.w2;
+    const float numer = d1 + m;
+    const float denom = sqrtf(d2 + v) + d.eps;
+    m = m + d1;
+    v = v + d2;
+    p = p + d.s * (numer / denom);
+}
+
+__global__ void __launch_bounds__(GS_BLOCK) sparse_adam_multi_kernel(SparseAdamMultiArgs a) {
+    const uint32_t total = a.chunk_end[a.n - 1];
+    uint32_t t = 0;
+    for (uint32_t ch = blockIdx.x; ch < total; ch += gridDim.x) {
+        while (ch >= a.chunk_end[t]) ++t;
+        const uint32_t c0 = t ? a.chunk_end[t - 1] : 0u;
+        const SparseAdamTensor &d = a.t[t];
+        const uint64_t e64 = (uint64_t)(ch - c0) * GS_BLOCK + threadIdx.x;
+        if (e64 >= d.n) continue;
+        const uint32_t e = (uint32_t)e64;
+        const uint32_t tq = __umulhi(e, d.magic);
+        const uint32_t k = (tq + ((e - tq) >> d.sh1)) >> d.sh2;
+        const uint32_t c = e - k * d.row_width;
+        const int64_t id = a.ids[k];
+        if (k > 0 && a.ids[k - 1] == id) continue;      // not the head of its run
+        if (id < 0 || (uint64_t)id >= a.rows) continue;  // never an address
+        float g = 0.f;
+        bool first = true;
+        for (uint32_t j = k; j < a.nnz && a.ids[j] == id; ++j) {
+            const uint32_t src = a.perm ? (uint32_t)a.perm[j] : j;
+            if (src >= a.nnz) continue;
+            const float x = d.g[(uint64_t)src * d.row_width + c];
+            g = first ? x : g + x;  // (starts from the first value: -0 stays -0)
+            first = false;
+        }
+        if (first) continue;
+        const uint64_t o = (uint64_t)id * d.row_width + c;
+        float p = d.p[o], m = d.m[o], v = d.v[o];
+        sparse_adam_one(p, g, m, v, d);
+        d.p[o] = p;
+        d.m[o] = m;
+        d.v[o] = v;
+    }
+}
+
 }  // namespace
 
 extern "C" uint32_t gs_adam_multi_max(void) { return GS_ADAM_MULTI_MAX; }
@@ -273,6 +357,80 @@ extern "C" int32_t gs_adam_multi(uint32_t n_tensors, const gs_adam_desc *descs, 
         chunks += c;
         a.chunk_end[a.n] = (uint32_t)(chunks < 0xffffffffull ? chunks : 0xffffffffull);
         ++a.n;
+    }
+    return 0;
+}
+
+extern "C" uint32_t gs_sparse_adam_desc_layout(uint64_t *out, uint32_t n) {
+    const uint64_t v[] = {sizeof(gs_sparse_adam_desc), offsetof(gs_sparse_adam_desc, param), offsetof(gs_sparse_adam_desc, exp_avg),
+                          offsetof(gs_sparse_adam_desc, exp_avg_sq), offsetof(gs_sparse_adam_desc, values),
+                          offsetof(gs_sparse_adam_desc, row_width), offsetof(gs_sparse_adam_desc, one_minus_beta1),
+                          offsetof(gs_sparse_adam_desc, one_minus_beta2), offsetof(gs_sparse_adam_desc, neg_step_size),
+                          offsetof(gs_sparse_adam_desc, eps)};
+    const uint32_t m = (uint32_t)(sizeof(v) / sizeof(v[0]));
+    for (uint32_t i = 0; out != nullptr && i < n && i < m; ++i) out[i] = v[i];
+    return m;
+}
+
+extern "C" int32_t gs_sparse_adam_multi(uint32_t n_tensors, const gs_sparse_adam_desc *descs, uint64_t nnz, const int64_t *sorted_ids,
+                                        const int32_t *perm, uint64_t rows, gs_stream_t stream) {
+    GS_CHECK_ARG(n_tensors == 0 || descs != nullptr, "null descriptor table");
+    GS_CHECK_ARG(nnz < (1ull << 31), "nnz must be < 2^31");
+    if (nnz == 0 || n_tensors == 0) return 0;
+    GS_CHECK_ARG(sorted_ids != nullptr, "null sorted_ids");
+    GS_CHECK_ARG((uintptr_t)sorted_ids % 8 == 0 && (uintptr_t)perm % 4 == 0, "sorted_ids must be 8-byte, perm 4-byte aligned");
+    // every descriptor is checked before anything is launched: a bad one leaves all the tensors untouched
+    for (uint32_t i = 0; i < n_tensors; ++i) {
+        const gs_sparse_adam_desc &d = descs[i];
+        if (!d.param || !d.exp_avg || !d.exp_avg_sq || !d.values) {
+            gs_set_error("gs_sparse_adam_multi: descriptor %u: null pointer", i);
+            return 1;
+        }
+        if (((uintptr_t)d.param | (uintptr_t)d.exp_avg | (uintptr_t)d.exp_avg_sq | (uintptr_t)d.values) % 4 != 0) {
+            gs_set_error("gs_sparse_adam_multi: descriptor %u: float arrays must be 4-byte aligned", i);
+            return 1;
+        }
+        if (d.row_width == 0 || d.row_width >= (1u << 31) || nnz * d.row_width > 0xffffffffull || rows > 0xffffffffull ||
+            rows * d.row_width > 0xffffffffull) {
+            gs_set_error("gs_sparse_adam_multi: descriptor %u: needs 1 <= row_width < 2^31, nnz * row_width < 2^32 and "
+                         "rows * row_width < 2^32", i);
+            return 1;
+        }
+    }
+    uint32_t cap = 0;
+    if (device_grid_cap(&cap)) {
+        gs_set_error("gs_sparse_adam_multi: cannot query the current device");
+        return 1;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    SparseAdamMultiArgs a;
+    a.nnz = (uint32_t)nnz;
+    a.rows = rows;
+    a.ids = sorted_ids;
+    a.perm = perm;
+    for (uint32_t i0 = 0; i0 < n_tensors; i0 += GS_ADAM_MULTI_MAX) {
+        a.n = n_tensors - i0 < GS_ADAM_MULTI_MAX ? n_tensors - i0 : GS_ADAM_MULTI_MAX;
+        uint32_t chunks = 0;  // (16 tensors of < 2^24 chunks each)
+        for (uint32_t i = 0; i < a.n; ++i) {
+            const gs_sparse_adam_desc &d = descs[i0 + i];
+            SparseAdamTensor &t = a.t[i];
+            t.p = d.param;
+            t.m = d.exp_avg;
+            t.v = d.exp_avg_sq;
+            t.g = d.values;
+            t.row_width = d.row_width;
+            t.n = (uint32_t)(nnz * d.row_width);
+            div_magic(d.row_width, t.magic, t.sh1, t.sh2);
+            t.w1 = d.one_minus_beta1;
+            t.w2 = d.one_minus_beta2;
+            t.s = d.neg_step_size;
+            t.eps = d.eps;
+            chunks += (uint32_t)(((uint64_t)t.n + GS_BLOCK - 1) / GS_BLOCK);
+            a.chunk_end[i] = chunks;
+        }
+        const uint32_t blocks = chunks < cap ? chunks : cap;
+        hipLaunchKernelGGL(sparse_adam_multi_kernel, dim3(blocks), dim3(GS_BLOCK), 0, st, a);
+        GS_CHECK_LAUNCH();
     }
     return 0;
 }

@@ -9,6 +9,10 @@
   loop as ONE ``gs_adam_multi`` call over every parameter of every optimizer (``Adam``, plain ``torch.optim.Adam`` with
   supported settings, ``SelectiveAdam``).
 * ``visibility_mask(meta, n)`` -- the trainer's ``visible_adam`` mask from ``rasterization()``'s meta.
+* ``SparseAdam`` -- a drop-in ``torch.optim.SparseAdam`` for the trainers' ``--sparse_grad`` mode, and ``sparsify_grads(params,
+  gaussian_ids, coalesced)``, the trainer's loop that builds the COO gradients (``optimizers/sparse.py``).  ``step_all`` takes
+  ``SparseAdam`` optimizers next to the dense ones: all their gradients over one index list cost one sort and one
+  ``gs_sparse_adam_multi`` launch.
 
 There is no fallback to torch's own Adam: a parameter the kernel cannot step raises.
 """
@@ -21,7 +25,7 @@ from torch import Tensor
 
 from .. import _wrapper as W
 
-__all__ = ["Adam", "SelectiveAdam", "step_all", "visibility_mask"]
+__all__ = ["Adam", "SelectiveAdam", "SparseAdam", "step_all", "sparsify_grads", "visibility_mask"]
 
 
 def _check_group(group: dict) -> None:
@@ -190,29 +194,40 @@ def step_all(optimizers: Union[Dict[str, torch.optim.Optimizer], Iterable[torch.
     """Step every optimizer in ONE ``gs_adam_multi`` call (per device), then ``zero_grad(set_to_none=True)`` each of them.
 
     ``optimizers``: a dict (the trainer's ``self.optimizers``) or an iterable of ``Adam``, ``torch.optim.Adam`` (supported
-    settings; its ``step`` state is advanced exactly as its own ``step()`` would) and ``SelectiveAdam`` (needs ``visibility``).
+    settings; its ``step`` state is advanced exactly as its own ``step()`` would), ``SelectiveAdam`` (needs ``visibility``) and
+    ``SparseAdam`` / ``torch.optim.SparseAdam`` (sparse gradients: planned together over all of them, one sort and one
+    ``gs_sparse_adam_multi`` call per index list).
     Parameters whose ``grad`` is None are skipped.  Every optimizer is checked before any state changes.  The optimizers' own
     ``step`` hooks do not run (their ``step`` is not called)."""
     opts = list(optimizers.values()) if isinstance(optimizers, dict) else list(optimizers)
-    kinds = []
+    kinds, sparse_opts = [], []
     for opt in opts:
-        if isinstance(opt, SelectiveAdam):
-            kinds.append(True)
+        if isinstance(opt, torch.optim.SparseAdam):
+            sparse_opts.append(opt)
+        elif isinstance(opt, SelectiveAdam):
+            kinds.append((opt, True))
         elif isinstance(opt, torch.optim.Adam):
-            kinds.append(False)
+            kinds.append((opt, False))
         else:
-            raise TypeError(f"step_all: {type(opt).__name__} is not an Adam / SelectiveAdam optimizer")
-    for opt, sel in zip(opts, kinds):
+            raise TypeError(f"step_all: {type(opt).__name__} is not an Adam / SelectiveAdam / SparseAdam optimizer")
+    for opt, sel in kinds:
         _validate(opt, sel, visibility)
+    for opt in sparse_opts:
+        _sparse.validate(opt)
     entries: List = []
     with torch.no_grad():
-        for opt, sel in zip(opts, kinds):
+        for opt, sel in kinds:
             _collect(opt, sel, visibility, entries)
         _launch(entries)
+        _sparse.step_sparse(sparse_opts)
     for opt in opts:
         opt._opt_called = True  # what the optimizer's own step() wrapper records (an LR scheduler checks it)
         if zero_grad:
             opt.zero_grad(set_to_none=True)
+
+
+from . import sparse as _sparse  # noqa: E402  (it uses _check_state / _param_name above)
+from .sparse import SparseAdam, sparsify_grads  # noqa: E402
 
 
 def visibility_mask(meta: dict, n: Optional[int] = None) -> Tensor:

@@ -52,7 +52,8 @@ extern "C" {
  * gs_kmeans_update), and the nearest-neighbour entries (gs_knn_cells, gs_knn_finish_grid, gs_knn_search), and the
  * PLY entries (gs_ply_unpack, gs_ply_pack, gs_ply_max_stride, gs_ply_max_columns, gs_ply_block_rows), and the hash-grid Gaussian entropy model's (gs_hashgrid_encode_fwd / _bwd,
  * gs_gaussian_bits_fwd / _bwd), and the Gaussian entropy coder's (gs_ans_pack_slots, gs_gauss_ans_slot_bytes,
- * gs_gauss_ans_encode_bytes, gs_gauss_ans_params, gs_gauss_ans_encode, gs_gauss_ans_decode). */
+ * gs_gauss_ans_encode_bytes, gs_gauss_ans_params, gs_gauss_ans_encode, gs_gauss_ans_decode), and the SparseAdam entries
+ * (gs_sparse_adam_desc, gs_sparse_adam_multi, gs_sparse_adam_desc_layout). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -1347,6 +1348,38 @@ uint32_t gs_adam_multi_max(void);
  * step_size, mode */
 uint32_t gs_adam_desc_layout(uint64_t *out, uint32_t n);
 int32_t gs_adam_multi(uint32_t n_tensors, const gs_adam_desc *descs, gs_stream_t stream);
+
+/* O2  SparseAdam over several tensors that share ONE index list, in one launch (torch.optim.SparseAdam per splat attribute in
+ * the trainers' --sparse_grad mode: COO gradients over the packed render's gaussian_ids).  descs: HOST array; more than
+ * GS_ADAM_MULTI_MAX descriptors are split over several launches on the same stream.  param, exp_avg, exp_avg_sq: fp32
+ * [rows, row_width], updated in place; values: fp32 [nnz, row_width], the gradient's value rows; all contiguous, 4-byte aligned.
+ * sorted_ids: int64 [nnz], ascending, every id in [0, rows) (an id outside is skipped, never used as an address).  perm: int32
+ * [nnz], perm[k] = the row of `values` that sorted_ids[k] came from, or NULL = identity (a coalesced or already sorted gradient).
+ * The rows whose id does not occur are neither read nor written.  Per element of the other rows,
+ * torch.optim._functional.sparse_adam in its order of operations, one float32 rounding each:
+ *   g = the sum of the duplicates' values;  d1 = (g - m) * one_minus_beta1;  d2 = (g * g - v) * one_minus_beta2;
+ *   m = m + d1;  v = v + d2;  p = p + neg_step_size * ((d1 + m_old) / (sqrt(d2 + v_old) + eps))
+ * The caller computes one_minus_beta1 = 1 - beta1, one_minus_beta2 = 1 - beta2 and neg_step_size =
+ * -(lr * sqrt(1 - beta2^step) / (1 - beta1^step)) in double and rounds them to float, as torch does; it also advances its step
+ * counter.  Duplicates: a run of equal ids is summed in the order of its positions in sorted_ids, starting from its first value;
+ * with perm from a stable sort on (id, position) -- gs_sort_pairs_u64_i32 over (ids, 0 .. nnz - 1) -- that is ascending position
+ * in `values`.  (torch's coalesce() sums three or more duplicates in another order; up to two, or exactly representable sums,
+ * agree bit for bit.)  A run of length r costs r serial loads per column: meant for r <= the number of cameras.
+ * nnz < 2^31, 1 <= row_width < 2^31, nnz * row_width < 2^32, rows * row_width < 2^32; all checked, with the null pointers and
+ * the alignment, before anything is launched.  nnz == 0: nothing is launched.  No atomics: every (row, column) is written by one
+ * lane, the results are bit-identical from run to run and do not depend on the grid. */
+typedef struct gs_sparse_adam_desc {
+    float *param;                /* [rows, row_width], updated in place */
+    float *exp_avg, *exp_avg_sq; /* [rows, row_width], updated in place */
+    const float *values;         /* [nnz, row_width] */
+    uint32_t row_width;
+    float one_minus_beta1, one_minus_beta2, neg_step_size, eps;
+} gs_sparse_adam_desc;
+/* layout guard (see gs_step_layout): sizeof, then offsetof param, exp_avg, exp_avg_sq, values, row_width, one_minus_beta1,
+ * one_minus_beta2, neg_step_size, eps */
+uint32_t gs_sparse_adam_desc_layout(uint64_t *out, uint32_t n);
+int32_t gs_sparse_adam_multi(uint32_t n_tensors, const gs_sparse_adam_desc *descs, uint64_t nnz, const int64_t *sorted_ids,
+                             const int32_t *perm, uint64_t rows, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * L1  The trainers' photometric loss: the 3DGS SSIM of the fused_ssim package (11-tap separable Gaussian window, sigma 1.5,
