@@ -124,7 +124,7 @@ def _finish(s, sp, stream, bufs, C, N, height, width, tile_height, tile_width, d
     n_isects, n_kept_host = sums.wait()
     s.n_kept_host = n_kept_host if W._PACKED_PAIRS else 0
     s.n_isects = n_isects
-    if ids_buf is None or n_isects > cap:
+    if ids_buf is None or not _cap_serves(cap, n_isects):
         ids_buf = empty(n_isects, dtype=i64, device=dev)
         flat_buf = empty(n_isects, dtype=i32, device=dev)
         wb = B.query("gs_isect_finish_work_bytes", n_isects)
@@ -136,7 +136,7 @@ def _finish(s, sp, stream, bufs, C, N, height, width, tile_height, tile_width, d
     B.call("gs_step_fwd_finish", sp, stream)
     isect_ids = ids_buf if ids_buf.shape[0] == n_isects else ids_buf[:n_isects]
     flatten_ids = flat_buf if flat_buf.shape[0] == n_isects else flat_buf[:n_isects]
-    _ISECT_CAP[key] = n_isects + (n_isects >> 5) + 4096
+    _ISECT_CAP[key] = _next_cap(n_isects)
     sums.release()
     # ---- the compositing buffers (made while the GPU is busy with the binning)
     render_colors = empty((C, height, width, 3), dtype=f32, device=dev)
@@ -161,6 +161,18 @@ def _finish(s, sp, stream, bufs, C, N, height, width, tile_height, tile_width, d
 
 _ISECT_CAP: dict = {}  # (device, C, N, tile grid) -> capacity for the next call's intersection buffers (last count + 3 %)
 _PREALLOC = os.environ.get("GS_ISECT_PREALLOC", "1") != "0"
+
+
+def _next_cap(n_isects: int) -> int:
+    """The capacity the next call of the same shape allocates before its read-back: this call's count + 3 % + 4096."""
+    return n_isects + (n_isects >> 5) + 4096
+
+
+def _cap_serves(cap: int, n_isects: int) -> bool:
+    """Whether buffers allocated for ``cap`` intersections are kept for a call that found ``n_isects``.  ``work`` was sized with
+    gs_isect_finish_work_bytes(cap) and the library checks it against gs_isect_finish_work_bytes(n_isects): that query is
+    non-decreasing in its argument (include/gsplat_hip.h, tests/test_sizes_cpu.py), so the count alone decides."""
+    return n_isects <= cap
 
 
 class _StepProject(torch.autograd.Function):

@@ -37,6 +37,14 @@ constexpr int SORT_ROUNDS_BIG = 16, SORT_ROUNDS_SMALL = 4;
 constexpr uint64_t SORT_SMALL_N = 2u << 20;
 constexpr int sort_tile(int rounds) { return GS_BLOCK * rounds; }
 inline int sort_rounds_for(uint64_t n) { return n <= SORT_SMALL_N ? SORT_ROUNDS_SMALL : SORT_ROUNDS_BIG; }
+// Rows of blocks the temp layouts RESERVE for the histogram [RADIX][blocks]: the 4096-key blocks above SORT_SMALL_N are fewer
+// than the 1024-key blocks just below it, and callers keep a temp buffer sized for a capacity for every smaller count
+// (_step.py), so the byte counts must never decrease in n -- above the switch at least the 2048 rows SORT_SMALL_N keys need.
+// Up to SORT_SMALL_N: exactly n_blocks, as ever.  (The kernels index the histogram with the real n_blocks either way.)
+inline size_t sort_hist_rows(uint64_t n, uint32_t n_blocks) {
+    const size_t at_switch = (size_t)(SORT_SMALL_N / sort_tile(SORT_ROUNDS_SMALL));
+    return (n > SORT_SMALL_N && n_blocks < at_switch) ? at_switch : (size_t)n_blocks;
+}
 
 struct DigitSpec {
     uint32_t shift;
@@ -389,7 +397,7 @@ SortLayout sort_layout(uint64_t n) {
     };
     L.off_keys = take(n * sizeof(uint64_t));
     L.off_vals = take(n * sizeof(int32_t));
-    L.off_hist = take((size_t)RADIX * L.n_blocks * sizeof(uint32_t));
+    L.off_hist = take((size_t)RADIX * sort_hist_rows(n, L.n_blocks) * sizeof(uint32_t));
     L.off_totals = take(RADIX * sizeof(uint32_t));
     L.total = o;
     return L;
@@ -545,7 +553,7 @@ Sort32Layout sort32_layout(uint64_t n) {
     };
     L.off_keys = take(n * sizeof(uint32_t));
     L.off_vals = take(n * sizeof(int32_t));
-    L.off_hist = take((size_t)RADIX * L.n_blocks * sizeof(uint32_t));
+    L.off_hist = take((size_t)RADIX * sort_hist_rows(n, L.n_blocks) * sizeof(uint32_t));
     L.off_totals = take(RADIX * sizeof(uint32_t));
     L.total = o;
     return L;

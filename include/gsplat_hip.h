@@ -432,7 +432,9 @@ int32_t gs_isect_emit_presorted(
 /* The whole second half of the sorted binning in ONE call (what rasterization() issues right after its host read-back of
  * n_isects, while the GPU still works off the depth pre-sort: three entry points' worth of host work in one):
  * gs_isect_emit_presorted(compact) -> gs_sort_isect_pairs -> gs_isect_offset_encode.  work: caller-allocated,
- * gs_isect_finish_work_bytes(n_isects) bytes, 16-byte aligned (the compact pairs and the sort's temporaries). */
+ * gs_isect_finish_work_bytes(n_isects) bytes, 16-byte aligned (the compact pairs and the sort's temporaries).
+ * gs_isect_finish_work_bytes is non-decreasing in n: a buffer sized for n serves every smaller count (callers allocate it for a
+ * capacity before they know the count). */
 size_t gs_isect_finish_work_bytes(uint64_t n_isects);
 int32_t gs_isect_finish_presorted(
     uint32_t n_elems, uint32_t N, uint64_t n_isects, const int32_t *perm, const uint32_t *n_valid, const int64_t *camera_ids,
@@ -465,6 +467,8 @@ int32_t gs_sort_isect_packed(
     uint64_t n, uint32_t *words, const int32_t *perm, const int64_t *sorted_keys /* NULL, or (depth bits << 32 | element) by
     position: replaces perm + depths */, const float *depths /* indexed by the flatten id */, int32_t key_bits,
     uint32_t pos_bits, int64_t *isect_ids, int32_t *flatten_ids, void *temp, size_t temp_bytes, gs_stream_t stream);
+/* non-decreasing in n: a buffer sized for n serves every smaller count (the sort's blocks are 1024 keys up to 2^21 keys and 4096
+ * above; the block histogram is reserved for the larger of the two layouts there) */
 size_t gs_sort_isect_temp_bytes(uint64_t n);
 int32_t gs_sort_isect_pairs(
     uint64_t n, uint32_t *keys32, int32_t *vals, const float *depths /* indexed by the flatten id */, int32_t key_bits,
@@ -473,7 +477,8 @@ int32_t gs_sort_isect_pairs(
 /* Stable LSD radix sort of (uint64 key, int32 value) pairs on key bits
  * [begin_bit, end_bit) -- the replacement for cub::DeviceRadixSort::SortPairs
  * (gsplat/cuda/csrc/isect_tiles.cu:245-299).  Inputs are not modified; the sorted
- * result is in keys_out / vals_out. */
+ * result is in keys_out / vals_out.
+ * gs_sort_temp_bytes is non-decreasing in n: a buffer sized for n serves every smaller count. */
 size_t gs_sort_temp_bytes(uint64_t n);
 int32_t gs_sort_pairs_u64_i32(
     uint64_t n,
@@ -511,8 +516,8 @@ int32_t gs_sort_first_hist_applicable(uint64_t n);
  *                        positions [1024 w, 1024 (w + 1)) with an LSD sort in LDS on the depth bits that differ inside its range.
  * A range above lds_capacity keys (0 = gs_presort_capacity() = 4096; smaller values are for tests) is sorted by its workgroup
  * through global memory: slower, same result -- with sampled splitters that takes adversarial input.
- * temp: gs_presort_temp_bytes(n).  side_vals / side_sums / side_shift: as in gs_sort_pairs_u64_i32_drop (side_sums is zeroed
- * by the call). */
+ * temp: gs_presort_temp_bytes(n) -- non-decreasing in n: a buffer sized for n serves every smaller count.
+ * side_vals / side_sums / side_shift: as in gs_sort_pairs_u64_i32_drop (side_sums is zeroed by the call). */
 int32_t gs_presort_applicable(uint64_t n);
 uint32_t gs_presort_capacity(void);
 size_t gs_presort_temp_bytes(uint64_t n);
@@ -558,7 +563,9 @@ int32_t gs_isect_offset_encode(
  *   [2] / [3] work items per XCD group of the forward / backward (0 = identity mapping; default 16)
  * a negative entry keeps the default.  Results never depend on the plan beyond floating-point association of the
  * gradient atomics.  scratch_bytes: size of the scratch buffer both calls take (forward checkpoints, the backward's
- * work list). */
+ * work list).  Unlike the sort's size queries, scratch_bytes carries NO guarantee of being non-decreasing in n_isects
+ * (the segment length doubles where the checkpoints would pass their bound, which halves them): callers size the scratch
+ * exactly, from the plan of the very call, and the calls insist on that plan. */
 typedef struct gs_raster_plan {
     uint32_t magic, n_tiles_all, n_isects, channels;
     int32_t seg, solo_min;

@@ -260,7 +260,9 @@ def test_isect_packed_and_empty(ops):
     assert int(offs.abs().sum()) == 0
 
 
-@pytest.mark.parametrize("n,end_bit", [(1, 40), (63, 46), (4096, 46), (4097, 33), (200_003, 46), (1_000_000, 64), (300_000, 8)])
+# (the last five: both sides of the switch from 1024- to 4096-key blocks at 2^21 keys, and one block more than a multiple of 4096)
+@pytest.mark.parametrize("n,end_bit", [(1, 40), (63, 46), (4096, 46), (4097, 33), (200_003, 46), (1_000_000, 64), (300_000, 8),
+                                       (2_097_151, 46), (2_097_152, 46), (2_097_153, 46), (2_097_152 + 4097, 46), (2_097_153, 64)])
 def test_radix_sort_stable_bit_exact(ops, n, end_bit):
     from gscodec_studio_amd import _backend as B
 
@@ -287,7 +289,7 @@ def test_radix_sort_stable_bit_exact(ops, n, end_bit):
     assert np.array_equal(N(vo), vals[order])
 
 
-@pytest.mark.parametrize("n", [1, 1000, 4097, 300_000, 2_200_000, 3_000_001])
+@pytest.mark.parametrize("n", [1, 1000, 4097, 300_000, 2_097_152, 2_097_153, 2_200_000, 3_000_001])
 def test_radix_sort_drop_variant_and_gather_cumsum(ops, n):
     """gs_sort_pairs_u64_i32_drop: keys with a given upper word vanish in the first pass, the survivors come out in stable
     sorted order, their count lands on the device; gs_cumsum_gather_i32 honours that device-side count.  Sizes on both

@@ -54,8 +54,13 @@ def _case(n, kind, seed, vis=0.3, C=1):
 @pytest.mark.parametrize("n,kind,vis", [
     (1, "uniform", 1.0), (63, "uniform", 0.5), (1000, "uniform", 0.0), (5000, "clustered", 0.3), (100_000, "uniform", 0.3),
     (100_000, "equal", 0.9), (300_000, "clustered", 0.6), (1_006_065, "uniform", 0.29), (1_006_065, "clustered", 1.0),
-    (1_006_065, "ascending", 0.3), (700_001, "descending", 0.3), (1_000_000, "periodic", 0.5), (2_000_000, "uniform", 0.2)])
+    (1_006_065, "ascending", 0.3), (700_001, "descending", 0.3), (1_000_000, "periodic", 0.5), (2_000_000, "uniform", 0.2),
+    (2_097_152, "uniform", 0.2),      # the last size the bucketed route accepts
+    (2_097_153, "clustered", 0.3)])   # gs_presort_applicable is 0: on=True must take the radix sort (4096-key blocks) and give its result
 def test_bucketed_presort_equals_radix_sort(n, kind, vis):
+    from gscodec_studio_amd import _backend as B
+
+    assert int(B.query("gs_presort_applicable", n)) == int(n <= 2_097_152)
     m2, radii, d = _case(n, kind, seed=n % 1000 + len(kind), vis=vis)
     args = (T(m2), T(radii), T(d))
     ref_perm, ref_k, ref_g, ref_t = _state(*args, on=False)
