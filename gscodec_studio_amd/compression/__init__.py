@@ -17,9 +17,15 @@
   atomics in the update), defined by the numpy code ``kmeans_reference`` that the kernels match element for element;
   ``kmeans_encode(method="fixed")`` and ``kmeans_method="fixed"`` of the two codecs below.
 
+* ``_container``: the directory layer under the three file codecs below -- the preparation of the splats (opacity filter, log
+  transform, normalised quats, square crop, ``use_sort`` ordering), the loop over the attributes with ``meta.json``, the
+  empty-attribute rule and the ``<name>.npz`` fallback, the PNG plane files and their names, a self-contained 8-bit PNG reader /
+  writer (``png_read`` / ``png_write``; the image has no imageio) and the masked K-means file pair.  Each codec hands it one
+  callback per direction that says what to do with an attribute.
+
 * ``png_compression``: the file level -- ``PngCompression.compress(dir, splats)`` / ``decompress(dir)`` with the reference's
-  directory layout (PNG image grids, ``shN.npz`` + ``mask.bin``, ``meta.json``) and a self-contained 8-bit PNG reader /
-  writer (the image has no imageio), so directories written by either implementation are read by the other.
+  directory layout (PNG image grids, ``shN.npz`` + ``mask.bin``, ``meta.json``), so directories written by either
+  implementation are read by the other.
 
 * ``stg_compression``: ``STGPngCompression``, the reference's ``--compression stg`` of the two dynamic trainers -- the spacetime
   attributes (means, scales, quats, opacities, trbf_center, trbf_scale, motion in three images, omega, colors, features_dir,
@@ -36,7 +42,8 @@
   model files and meta keys around a bitstream defined by the numpy coder ``gauss_ans_reference``.
 """
 from .decode import decode_to_dynamic_inputs, decode_to_rasterizer_inputs, kmeans_decode, kmeans_encode, morton_order, reorder_splats, sort_splats
-from .png_compression import PngCompression, png_read, png_write
+from ._container import png_read, png_write
+from .png_compression import PngCompression
 from .ans import ans_decode, ans_encode, normalize_frequencies, symbol_histogram
 from .gauss_ans import gauss_ans_decode, gauss_ans_encode, gaussian_params
 from .entropy_coding_compression import EntropyCodingCompression

@@ -29,7 +29,6 @@ to ``mins``.
 """
 from __future__ import annotations
 
-import json
 import os
 from dataclasses import InitVar, dataclass, field
 from typing import Any, Dict, Optional, Union
@@ -42,33 +41,31 @@ from . import gauss_ans_reference as GR
 from .ans import ans_decode, ans_encode, probabilities, symbol_histogram
 from .gauss_ans import check_entropy_model, gauss_ans_decode, gauss_ans_encode, gaussian_params
 from .grid_codec import dequantize_grid, inverse_log_transform, quantize_grid
-from .png_compression import (_meta_of, compress_masked_kmeans, decompress_masked_kmeans, png_read, png_write,
-                              prepare_splats)
+from ._container import (compress_masked_kmeans, decompress_masked_kmeans, prepare_splats, read_directory, read_planes,
+                         write_directory, write_planes)
 
 _ENCODINGS = ("encoding_xyz", "encoding_xy", "encoding_xz", "encoding_yz")
 
 
 def _compress_png_16bit(compress_dir: str, param_name: str, params: Tensor, n_sidelen: int, **kwargs) -> Dict[str, Any]:
-    (lo, hi), meta = quantize_grid(params, n_sidelen, bits=16)
-    png_write(os.path.join(compress_dir, f"{param_name}_l.png"), lo.cpu().numpy())
-    png_write(os.path.join(compress_dir, f"{param_name}_u.png"), hi.cpu().numpy())
+    planes, meta = quantize_grid(params, n_sidelen, bits=16)
+    write_planes(compress_dir, param_name, "16", planes)
     return meta
 
 
 def _decompress_png_16bit(compress_dir: str, param_name: str, meta: Dict[str, Any], device="cuda") -> Tensor:
-    planes = [torch.from_numpy(png_read(os.path.join(compress_dir, f"{param_name}_{h}.png"))) for h in "lu"]
-    return dequantize_grid(planes, meta, device=device)
+    return dequantize_grid(read_planes(compress_dir, param_name, "16"), meta, device=device)
 
 
 def _compress_png(compress_dir: str, param_name: str, params: Tensor, n_sidelen: int, **kwargs) -> Dict[str, Any]:
     """The plain 8-bit form (211-250), not the k-bit one: no "quantization" entry in the meta."""
-    (plane,), meta = quantize_grid(params, n_sidelen, bits=8)
-    png_write(os.path.join(compress_dir, f"{param_name}.png"), plane.cpu().numpy())
+    planes, meta = quantize_grid(params, n_sidelen, bits=8)
+    write_planes(compress_dir, param_name, "plain", planes)
     return meta
 
 
 def _decompress_png(compress_dir: str, param_name: str, meta: Dict[str, Any], device="cuda") -> Tensor:
-    return dequantize_grid([torch.from_numpy(png_read(os.path.join(compress_dir, f"{param_name}.png")))], meta, device=device)
+    return dequantize_grid(read_planes(compress_dir, param_name), meta, device=device)
 
 
 def _compress_factorized_ans(compress_dir: str, param_name: str, params: Tensor, n_sidelen: int, stream_len: int = 1024,
@@ -176,16 +173,6 @@ def _decompress_masked_kmeans(compress_dir: str, param_name: str, meta: Dict[str
     return decompress_masked_kmeans(compress_dir, param_name, meta, device)
 
 
-def _compress_npz(compress_dir: str, param_name: str, params: Tensor, **kwargs) -> Dict[str, Any]:
-    np.savez_compressed(os.path.join(compress_dir, f"{param_name}.npz"), arr=params.cpu().numpy())
-    return _meta_of(params)
-
-
-def _decompress_npz(compress_dir: str, param_name: str, meta: Dict[str, Any], device="cuda") -> Tensor:
-    arr = np.load(os.path.join(compress_dir, f"{param_name}.npz"))["arr"]
-    return torch.tensor(arr).reshape(meta["shape"]).to(dtype=getattr(torch, meta["dtype"]), device=device)
-
-
 # the names attribute_codec_registry may use (entropy_coding_compression.py:74-86)
 _AVAILABLE = {fn.__name__: fn for fn in (
     _compress_png_16bit, _compress_png, _compress_factorized_ans, _compress_gaussian_ans, _compress_masked_kmeans,
@@ -195,9 +182,7 @@ _AVAILABLE = {fn.__name__: fn for fn in (
 @dataclass
 class EntropyCodingCompression:
     """The reference's ``EntropyCodingCompression``: same fields, same files (see the module docstring for the one difference,
-    the payload of the ``.bin`` files).  ``use_sort`` as in ``PngCompression`` here: True = PLAS (external package, ImportError
-    without it), "morton" = the deterministic Morton order, "grid" = the library's grid sort, False = keep the order.
-    ``attribute_codec_registry`` maps an
+    the payload of the ``.bin`` files).  ``use_sort`` as in ``PngCompression`` here.  ``attribute_codec_registry`` maps an
     attribute to ``{"encode": <name>, "decode": <name>}`` with the reference's function names as strings, e.g.
     ``{"scales": {"encode": "_compress_png", "decode": "_decompress_png"}}``.  Works on detached copies; the caller's dictionary
     is not written to.  A channel with ``maxs == mins`` is coded as symbol 0 and decodes to ``mins``.  ``kmeans_method`` as in
@@ -227,12 +212,6 @@ class EntropyCodingCompression:
                     else:
                         print(f"Warning: Unknown func: {attr_codec[key]}")
 
-    def _get_compress_fn(self, param_name: str):
-        return _AVAILABLE[self.compress_fn_map[param_name]] if param_name in self.compress_fn_map else _compress_npz
-
-    def _get_decompress_fn(self, param_name: str):
-        return _AVAILABLE[self.decompress_fn_map[param_name]] if param_name in self.decompress_fn_map else _decompress_npz
-
     @torch.no_grad()
     def compress(self, compress_dir: str, splats: Dict[str, Tensor], entropy_models=None) -> None:
         """``entropy_models`` must be given, as in the reference (121-122); the factorized codec does not read them.  An
@@ -240,41 +219,39 @@ class EntropyCodingCompression:
         just written), so ``means`` must precede it in ``splats``."""
         if entropy_models is None:
             raise ValueError("EntropyCodingCompression should require entropy_models")
-        os.makedirs(compress_dir, exist_ok=True)
         splats, side = prepare_splats(splats, self.opacity_threshold, self.use_sort, self.verbose)
-        meta: Dict[str, Any] = {}
-        for name, value in splats.items():
-            if value.numel() == 0:
-                meta[name] = _meta_of(value)
-            else:
-                fn, extra = self._get_compress_fn(name), {}
-                if fn is _compress_gaussian_ans and name in entropy_models and entropy_models[name] is not None:
-                    if "means" not in meta:
-                        raise ValueError(f"{name} is coded against the decoded means: 'means' must precede it in the splats")
-                    extra = {"entropy_model": entropy_models[name],
-                             "decoded_means": self.get_decompressed_means(compress_dir, meta["means"], value.device)}
-                meta[name] = fn(compress_dir, name, value, n_sidelen=side, n_clusters=self.n_clusters, verbose=self.verbose,
-                                kmeans_method=self.kmeans_method, **extra)
-        with open(os.path.join(compress_dir, "meta.json"), "w") as f:
-            json.dump(meta, f)
+
+        def encode(name, value, meta):
+            if name not in self.compress_fn_map:
+                return None
+            fn, extra = _AVAILABLE[self.compress_fn_map[name]], {}
+            if fn is _compress_gaussian_ans and name in entropy_models and entropy_models[name] is not None:
+                if "means" not in meta:
+                    raise ValueError(f"{name} is coded against the decoded means: 'means' must precede it in the splats")
+                extra = {"entropy_model": entropy_models[name],
+                         "decoded_means": self.get_decompressed_means(compress_dir, meta["means"], value.device)}
+            return fn(compress_dir, name, value, n_sidelen=side, n_clusters=self.n_clusters, verbose=self.verbose,
+                      kmeans_method=self.kmeans_method, **extra)
+
+        write_directory(compress_dir, splats, encode)
 
     @torch.no_grad()
     def decompress(self, compress_dir: str, device="cuda") -> Dict[str, Tensor]:
-        with open(os.path.join(compress_dir, "meta.json"), "r") as f:
-            meta = json.load(f)
-        splats: Dict[str, Tensor] = {}
-        for name, m in meta.items():
-            if not np.all(m["shape"]):
-                splats[name] = torch.zeros(m["shape"], dtype=getattr(torch, m["dtype"]), device=device)
-            elif self._get_decompress_fn(name) is _decompress_gaussian_ans:
+        def decode(name, m, splats):
+            if name not in self.decompress_fn_map:
+                return None
+            fn = _AVAILABLE[self.decompress_fn_map[name]]
+            if fn is _decompress_gaussian_ans:
                 if "means" not in splats:
                     raise ValueError(f"{name} is coded against the decoded means: 'means' must precede it in meta.json")
-                splats[name] = _decompress_gaussian_ans(compress_dir, name, m, inverse_log_transform(splats["means"]), device=device)
-            else:
-                splats[name] = self._get_decompress_fn(name)(compress_dir, name, m, device=device)
+                return fn(compress_dir, name, m, inverse_log_transform(splats["means"]), device=device)
+            return fn(compress_dir, name, m, device=device)
+
+        splats = read_directory(compress_dir, decode, device)
         splats["means"] = inverse_log_transform(splats["means"])
         return splats
 
     def get_decompressed_means(self, compress_dir: str, meta_means: Dict[str, Any], device="cuda") -> Tensor:
         """193-201: the means as ``decompress`` will see them, from the files of ``compress_dir``."""
-        return inverse_log_transform(self._get_decompress_fn("means")(compress_dir, "means", meta_means, device=device))
+        fn = _AVAILABLE[self.decompress_fn_map["means"]]
+        return inverse_log_transform(fn(compress_dir, "means", meta_means, device=device))

@@ -1,7 +1,7 @@
 """Min-max grid quantization of splat attributes (array level of the reference's PNG codec)."""
 from __future__ import annotations
 
-from typing import Any, Dict, List, Tuple
+from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -81,8 +81,13 @@ def dequantize_grid(planes: List[Tensor], meta: Dict[str, Any], device=None) -> 
     return out.reshape(shape).to(dtype)
 
 
-def _crop_to_square(splats: Dict[str, Tensor]) -> Tuple[Dict[str, Tensor], int]:
-    """Drop the lowest-opacity splats so that the count is a square (png_compression.py:112-119, 157-162)."""
+def transform_and_crop(splats: Dict[str, Tensor], normalize_quats: Optional[Callable] = None) -> Tuple[Dict[str, Tensor], int]:
+    """What every codec does in front of the quantizers (png_compression.py:100-119, 157-162), on a copy of the dict: log
+    transform of the means, normalised quats (``normalize_quats``: default ``F.normalize`` over the last dimension), and the
+    lowest-opacity splats dropped so that the count is a square.  Returns (splats, side length)."""
+    splats = dict(splats)
+    splats["means"] = log_transform(splats["means"])
+    splats["quats"] = normalize_quats(splats["quats"]) if normalize_quats else torch.nn.functional.normalize(splats["quats"], dim=-1)
     n = len(splats["means"])
     side = int(n**0.5)
     n_crop = n - side * side
@@ -99,10 +104,7 @@ def compress_to_arrays(splats: Dict[str, Tensor]) -> Tuple[Dict[str, List[Tensor
     attribute with its codec.  Other attributes (shN, ...) are passed through untouched under ``arrays[name] = [tensor]``
     with ``meta[name] = {"raw": True}`` (the reference uses a K-means codebook / npz for them).  No outlier filtering, no
     PLAS sort."""
-    splats = dict(splats)
-    splats["means"] = log_transform(splats["means"])
-    splats["quats"] = torch.nn.functional.normalize(splats["quats"], dim=-1)
-    splats, side = _crop_to_square(splats)
+    splats, side = transform_and_crop(splats)
     arrays, meta = {}, {}
     for name, value in splats.items():
         if name in ATTRIBUTE_CODECS:

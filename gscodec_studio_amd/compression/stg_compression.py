@@ -26,41 +26,27 @@ Three deliberate differences from the reference:
   meta dict for a zero-size shape): here an attribute with a zero in its shape is written as meta only and decodes to
   ``torch.zeros(shape)``, as in ``PngCompression``.
 * CPU tensors raise ``RuntimeError`` (no CPU fallback), as everywhere in ``compression``.
-
-``use_sort`` as in ``PngCompression``: True = PLAS through ``sort_splats`` (ImportError without the package, as in the reference),
-"morton" / "grid" = this library's own orderings, False = keep the order.
 """
 from __future__ import annotations
 
-import json
-import os
 from dataclasses import dataclass
-from typing import Any, Dict, List, Tuple, Union
+from typing import Dict, Tuple, Union
 
 import numpy as np
 import torch
 from torch import Tensor
 
-from .decode import DYNAMIC_ATTRIBUTES, decode_to_dynamic_inputs, morton_order, sort_splats
-from .grid_codec import _crop_to_square, dequantize_grid, inverse_log_transform, log_transform, quantize_grid
-from .grid_sort import sort_splats_grid
-from .png_compression import _meta_of, png_read, png_write
+from ._container import DEFERRED, plane_files, prepare_splats, read_directory, read_planes, write_directory, write_planes
+from .decode import DYNAMIC_ATTRIBUTES, decode_to_dynamic_inputs
+from .grid_codec import dequantize_grid, inverse_log_transform, quantize_grid
 
 # attribute -> (codec kind, bits, files): the reference's compress_fn_map / decompress_fn_map (stg_compression.py:47-83);
-# "16" = _compress_png_16bit, "kbit" = _compress_png_kbit, "plain" = _compress_png, "multi" = _compress_multiple_png
+# "16" = _compress_png_16bit, "kbit" = _compress_png_kbit, "plain" = _compress_png, "multi" = _compress_multiple_png (3 images)
 STG_ATTRIBUTE_CODECS: Dict[str, Tuple[str, int, Tuple[str, ...]]] = {
-    "means": ("16", 16, ("means_l.png", "means_u.png")),
-    "scales": ("kbit", 8, ("scales.png",)),
-    "quats": ("kbit", 8, ("quats.png",)),
-    "opacities": ("plain", 8, ("opacities.png",)),
-    "trbf_center": ("plain", 8, ("trbf_center.png",)),
-    "trbf_scale": ("plain", 8, ("trbf_scale.png",)),
-    "motion": ("multi", 8, ("motion_0.png", "motion_1.png", "motion_2.png")),
-    "omega": ("plain", 8, ("omega.png",)),
-    "colors": ("plain", 8, ("colors.png",)),
-    "features_dir": ("plain", 8, ("features_dir.png",)),
-    "features_time": ("plain", 8, ("features_time.png",)),
-}
+    name: (kind, 16 if kind == "16" else 8, plane_files(name, kind, 3))
+    for name, kind in (("means", "16"), ("scales", "kbit"), ("quats", "kbit"), ("opacities", "plain"), ("trbf_center", "plain"),
+                       ("trbf_scale", "plain"), ("motion", "multi"), ("omega", "plain"), ("colors", "plain"),
+                       ("features_dir", "plain"), ("features_time", "plain"))}
 _REQUIRED = tuple(name for name, _ in DYNAMIC_ATTRIBUTES[:9])  # what the one-launch decode cannot do without
 
 
@@ -84,9 +70,7 @@ def _normalize_quats(q: Tensor) -> Tensor:
 
 @dataclass
 class STGPngCompression:
-    """The reference's ``STGPngCompression`` (same constructor arguments, same files).  ``use_sort``: True = PLAS (external
-    package, as in the reference), "morton" = the deterministic Morton order, "grid" = the library's grid sort, False = keep
-    the order."""
+    """The reference's ``STGPngCompression`` (same constructor arguments, same files).  ``use_sort`` as in ``PngCompression``."""
 
     use_sort: Union[bool, str] = True
     verbose: bool = True
@@ -95,64 +79,39 @@ class STGPngCompression:
     def compress(self, compress_dir: str, splats: Dict[str, Tensor]) -> None:
         for value in splats.values():
             _require_device("compress", value.device)
-        os.makedirs(compress_dir, exist_ok=True)
-        splats = {k: v.detach() for k, v in splats.items()}
-        splats["means"] = log_transform(splats["means"])
-        splats["quats"] = _normalize_quats(splats["quats"])
-        n_before = len(splats["means"])
-        splats, side = _crop_to_square(splats)
-        if len(splats["means"]) != n_before:  # (the reference prints this unconditionally)
-            print(f"Warning: Number of Gaussians was not square. Removed {n_before - len(splats['means'])} Gaussians.")
-        if self.use_sort == "morton":
-            order = morton_order(splats["means"])
-            splats = {k: v[order] for k, v in splats.items()}
-        elif self.use_sort == "grid":
-            splats = sort_splats_grid(splats, verbose=self.verbose)
-        elif self.use_sort:
-            splats = sort_splats(splats, verbose=self.verbose)
+        splats, side = prepare_splats(splats, None, self.use_sort, self.verbose, normalize_quats=_normalize_quats,
+                                      always_warn=True)  # (the reference prints the crop warning unconditionally)
 
-        meta: Dict[str, Any] = {}
-        for name, value in splats.items():
-            if value.numel() == 0:
-                meta[name] = _meta_of(value)
-            elif name in STG_ATTRIBUTE_CODECS:
-                kind, bits, files = STG_ATTRIBUTE_CODECS[name]
-                planes, meta[name] = quantize_grid(value, side, bits=bits, kbit=(kind == "kbit"))
-                if kind == "multi":  # one grid over all channels, three channels per image
-                    grid = planes[0].reshape(side, side, -1)
-                    num_img = (grid.shape[-1] + 2) // 3
-                    planes = [grid[..., 3 * i:3 * i + 3] for i in range(num_img)]
-                    files = tuple(f"{name}_{i}.png" for i in range(num_img))
-                    meta[name]["num_img"] = num_img
-                for fn, plane in zip(files, planes):
-                    png_write(os.path.join(compress_dir, fn), plane.cpu().numpy())
-            else:
-                np.savez_compressed(os.path.join(compress_dir, f"{name}.npz"), arr=value.cpu().numpy())
-                meta[name] = _meta_of(value)
-        with open(os.path.join(compress_dir, "meta.json"), "w") as f:
-            json.dump(meta, f)
+        def encode(name, value, _):
+            if name not in STG_ATTRIBUTE_CODECS:
+                return None
+            kind, bits = STG_ATTRIBUTE_CODECS[name][:2]
+            planes, m = quantize_grid(value, side, bits=bits, kbit=(kind == "kbit"))
+            if kind == "multi":  # one grid over all channels, three channels per image
+                grid = planes[0].reshape(side, side, -1)
+                m["num_img"] = (grid.shape[-1] + 2) // 3
+                planes = [grid[..., 3 * i:3 * i + 3] for i in range(m["num_img"])]
+            write_planes(compress_dir, name, kind, planes)
+            return m
+
+        write_directory(compress_dir, splats, encode)
 
     @torch.no_grad()
     def decompress(self, compress_dir: str, device="cuda") -> Dict[str, Tensor]:
         _require_device("decompress", device)
-        with open(os.path.join(compress_dir, "meta.json"), "r") as f:
-            meta = json.load(f)
-        splats: Dict[str, Tensor] = {}
-        arrays: Dict[str, List[Tensor]] = {}
-        for name, m in meta.items():
-            if not np.all(m["shape"]):
-                splats[name] = torch.zeros(m["shape"], dtype=getattr(torch, m["dtype"]), device=device)
-            elif name in STG_ATTRIBUTE_CODECS:
-                kind, _, files = STG_ATTRIBUTE_CODECS[name]
-                if kind == "multi":
-                    files = tuple(f"{name}_{i}.png" for i in range(int(m["num_img"])))
-                arrays[name] = [torch.from_numpy(png_read(os.path.join(compress_dir, fn))) for fn in files]
-                splats[name] = None  # (keeps the meta's order)
-            else:
-                arr = np.load(os.path.join(compress_dir, f"{name}.npz"))["arr"]
-                splats[name] = torch.tensor(arr).reshape(m["shape"]).to(dtype=getattr(torch, m["dtype"]), device=device)
+        arrays, meta = {}, {}  # of the table's attributes: planes as read, meta.json entries
+
+        def decode(name, m, _):  # only reads the planes: they are decoded together below
+            if name not in STG_ATTRIBUTE_CODECS:
+                return None
+            kind = STG_ATTRIBUTE_CODECS[name][0]
+            arrays[name] = read_planes(compress_dir, name, kind, int(m["num_img"]) if kind == "multi" else 0)
+            meta[name] = m
+            return DEFERRED
+
+        splats = read_directory(compress_dir, decode, device)
         if all(k in arrays for k in _REQUIRED):
-            splats.update(decode_to_dynamic_inputs(arrays, {k: meta[k] for k in arrays}, device=device))
+            splats.update(decode_to_dynamic_inputs(arrays, meta, device=device))
         else:  # not a full spacetime set (e.g. no colors next to sh0 / shN): the same arithmetic, attribute by attribute
             for name, planes in arrays.items():
                 if STG_ATTRIBUTE_CODECS[name][0] == "multi":

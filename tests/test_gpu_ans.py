@@ -188,7 +188,7 @@ def _splats(n=2500):
 
 def test_directory_round_trip(tmp_path):
     from gscodec_studio_amd.compression import EntropyCodingCompression, ans, dequantize_grid, inverse_log_transform, quantize_grid
-    from gscodec_studio_amd.compression.png_compression import prepare_splats
+    from gscodec_studio_amd.compression._container import prepare_splats
 
     splats = _splats()
     before = {k: v.clone() for k, v in splats.items()}

@@ -240,3 +240,68 @@ def test_png_compression_directory_round_trip(tmp_path):
         rows = out["shN"][has].reshape(int(has.sum()), -1)
         assert torch.unique(rows, dim=0).shape[0] <= 256
         assert float((rows - kept["shN"][has].reshape(rows.shape)).abs().mean()) < 0.2
+
+
+_DIRECTORY_FILES = {
+    "PngCompression": "means_l.png means_u.png scales.png quats.png opacities.png sh0.png shN.npz mask.bin motion.npz extra.npz",
+    "STGPngCompression": "means_l.png means_u.png scales.png quats.png opacities.png motion_0.png motion_1.png motion_2.png "
+                         "sh0.npz shN.npz extra.npz",
+    "EntropyCodingCompression": "means_l.png means_u.png scales.bin scales_prob.npy quats.bin quats_prob.npy opacities.png sh0.png "
+                                "shN.npz mask.bin motion.npz extra.npz",
+}
+
+
+@pytest.mark.parametrize("use_sort", [False, "morton"])
+@pytest.mark.parametrize("cls", list(_DIRECTORY_FILES))
+def test_directory_layer_of_every_file_codec(cls, use_sort, tmp_path):
+    """What the three file codecs share above their attribute codecs: 33^2 + 5 splats (the crop drops some, and the rANS routes get
+    more than one stream of 1024), a zero-size attribute and one no table knows, between the known ones.  The files written,
+    the key order of meta.json and of the decoded dict, zeros for the zero-size attribute, and the unknown attribute bit for bit
+    after the same filter (not STG), crop and order."""
+    import json
+    import os
+
+    from gscodec_studio_amd import compression as C
+
+    g = torch.Generator().manual_seed(11)
+    n = 33 * 33 + 5
+    opacities = torch.randn(n, generator=g) * 2 + 1
+    opacities[::50] = -8.0 - 0.01 * torch.arange(len(opacities[::50]))  # below the opacity threshold, and no ties for the crop
+    splats = {"means": torch.randn(n, 3, generator=g) * 4, "empty": torch.zeros(n, 0), "scales": torch.randn(n, 3, generator=g) - 3,
+              "extra": torch.randn(n, 5, generator=g), "quats": torch.randn(n, 4, generator=g), "opacities": opacities,
+              "sh0": torch.randn(n, 1, 3, generator=g), "shN": torch.randn(n, 3, 3, generator=g) * 0.1,
+              "motion": torch.randn(n, 9, generator=g) * 0.02}
+    splats = {k: v.cuda() for k, v in splats.items()}
+    before = {k: v.clone() for k, v in splats.items()}
+
+    d = str(tmp_path / "dir")
+    if cls == "STGPngCompression":
+        codec = C.STGPngCompression(use_sort=use_sort, verbose=False)
+        codec.compress(d, splats)
+    else:
+        codec = getattr(C, cls)(use_sort=use_sort, verbose=False, n_clusters=64)
+        codec.compress(d, splats, **({"entropy_models": {}} if cls == "EntropyCodingCompression" else {}))
+    assert list(splats) == list(before) and all(torch.equal(splats[k], before[k]) for k in before)
+    assert sorted(os.listdir(d)) == sorted(_DIRECTORY_FILES[cls].split() + ["meta.json"])
+    with open(os.path.join(d, "meta.json")) as f:
+        meta = json.load(f)
+    assert list(meta) == list(splats)
+    out = codec.decompress(d)
+    assert list(out) == list(meta)
+
+    kept = dict(splats)
+    if cls != "STGPngCompression":
+        keep = torch.sigmoid(splats["opacities"]) >= 0.005
+        assert int(keep.sum()) < n - 5
+        kept = {k: v[keep] for k, v in kept.items()}
+    side = int(len(kept["means"]) ** 0.5)
+    assert side * side < len(kept["means"]) and side == (33 if cls == "STGPngCompression" else 32)
+    crop = torch.argsort(kept["opacities"], descending=True)[: side * side]
+    kept = {k: v[crop] for k, v in kept.items()}
+    if use_sort == "morton":
+        order = C.morton_order(C.log_transform(kept["means"]))
+        kept = {k: v[order] for k, v in kept.items()}
+    assert meta["empty"] == {"shape": [side * side, 0], "dtype": "float32"}
+    assert out["empty"].shape == (side * side, 0) and out["empty"].dtype == torch.float32 and out["empty"].is_cuda
+    assert meta["extra"] == {"shape": [side * side, 5], "dtype": "float32"}
+    assert out["extra"].is_cuda and torch.equal(out["extra"], kept["extra"])

@@ -199,7 +199,7 @@ np.savez(sys.argv[2], **{k: v.cpu().numpy() for k, v in out.items()})
 def test_directory_round_trip(tmp_path):
     from gscodec_studio_amd.compression import EntropyCodingCompression, dequantize_grid, quantize_grid
     from gscodec_studio_amd.compression import gauss_ans_reference as R
-    from gscodec_studio_amd.compression.png_compression import prepare_splats
+    from gscodec_studio_amd.compression._container import prepare_splats
     from gscodec_studio_amd.compression_simulation import Entropy_gaussian, HashGridCompressionSimulation, STE_binary
 
     splats = _splats()

@@ -130,7 +130,7 @@ def root(tmp_path_factory):
 
 def test_round_trip_is_the_unsorted_result_permuted(root):
     from gscodec_studio_amd.compression import sort_splats_grid
-    from gscodec_studio_amd.compression.png_compression import prepare_splats
+    from gscodec_studio_amd.compression._container import prepare_splats
 
     _, plain = _compressed(False, root)
     _, grid = _compressed("grid", root)

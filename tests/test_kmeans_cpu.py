@@ -120,7 +120,7 @@ def test_refused_inputs_raise_before_any_launch(monkeypatch):
 
 def test_the_default_method_is_the_torch_path():
     from gscodec_studio_amd.compression import EntropyCodingCompression, PngCompression, kmeans_encode
-    from gscodec_studio_amd.compression.png_compression import compress_masked_kmeans
+    from gscodec_studio_amd.compression._container import compress_masked_kmeans
 
     assert inspect.signature(kmeans_encode).parameters["method"].default == "torch"
     assert inspect.signature(compress_masked_kmeans).parameters["method"].default == "torch"

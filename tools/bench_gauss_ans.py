@@ -93,7 +93,7 @@ def prepared(splats, sim):
     import torch
 
     from gscodec_studio_amd.compression import dequantize_grid, gauss_ans as GA, inverse_log_transform, quantize_grid
-    from gscodec_studio_amd.compression.png_compression import prepare_splats
+    from gscodec_studio_amd.compression._container import prepare_splats
 
     kept, side = prepare_splats(splats, 0.005, "morton", False)
     planes, m = quantize_grid(kept["means"], side, bits=16)
