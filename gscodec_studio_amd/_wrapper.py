@@ -1392,6 +1392,21 @@ def _split_elems() -> int:
 # (camera, tile) key + depth rank as ONE 32-bit word through emission and pair sort when they fit (gs_isect_finish_presorted's
 # n_kept_host): GS_PACKED_PAIRS=0 keeps the (key, flatten id) pairs
 _PACKED_PAIRS = os.environ.get("GS_PACKED_PAIRS", "1") != "0"
+# row binning, gs_isect_finish_presorted's third route (tile rows by one counting pass, rows expanded into columns): the switch
+# is the library's own, process-wide, because the native step driver reaches the same function; GS_ROW_BINNING=0 turns it off
+_ROW_BINNING = os.environ.get("GS_ROW_BINNING", "1") != "0"
+if not _ROW_BINNING:
+    B.query("gs_isect_row_binning", 0)
+
+
+def set_row_binning(on: Optional[bool] = None) -> bool:
+    """Switch the row-binning route on or off for the calls that follow (``None``: only read); returns the previous state."""
+    return bool(B.query("gs_isect_row_binning", -1 if on is None else int(bool(on))))
+
+
+def isect_last_route() -> str:
+    """Route of the last ``gs_isect_finish_presorted`` call that had pairs to bin: "none", "pairs", "packed" or "rows"."""
+    return ("none", "pairs", "packed", "rows")[int(B.query("gs_isect_last_route"))]
 
 
 @torch.no_grad()

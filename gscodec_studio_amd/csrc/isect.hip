@@ -9,6 +9,8 @@
 // oracle.  The file is compiled with -ffp-contract=off.
 #include "gs_common.h"
 
+#include <atomic>
+
 namespace {
 
 __global__ void __launch_bounds__(GS_BLOCK) isect_count_kernel(
@@ -489,6 +491,406 @@ int32_t cumsum_impl(uint64_t n, const int32_t *in, const int32_t *idx, const uin
     return 0;
 }
 
+// ---------------------------------------------------------------------------
+// Row binning (see gsplat_hip.h): tile rows by one counting pass over the (splat, row) entries, then every row list expanded
+// into its columns.  A "row" is (camera, tile row) = camera * th + y; at most RB_KEYS rows and RB_KEYS columns, one thread each.
+// ---------------------------------------------------------------------------
+constexpr uint32_t RB_KEYS = 256;              // = GS_ROW_BINNING_MAX_WIDTH = GS_ROW_BINNING_MAX_ROWS = GS_BLOCK
+constexpr uint32_t RB_WAVES = GS_BLOCK / GS_WAVE;
+constexpr uint32_t RB_POS_ROUNDS = 2;          // positions per thread of a stage-1/3 block
+constexpr uint32_t RB_POS_ITEMS = GS_BLOCK * RB_POS_ROUNDS;
+constexpr uint32_t RB_ROUNDS = 2;              // entries per thread of a chunk
+constexpr uint32_t RB_ITEMS = GS_BLOCK * RB_ROUNDS; // entries per chunk of a row list
+constexpr uint32_t RB_STAGE_CAP = 4096;        // pairs of a chunk the expansion can stage in LDS (mean 3.2 per entry on a 1080p frame)
+static_assert(RB_KEYS == GS_BLOCK && GS_ROW_BINNING_MAX_WIDTH == RB_KEYS && GS_ROW_BINNING_MAX_ROWS == RB_KEYS, "one thread per row / column");
+static_assert(GS_ROW_BINNING_MAX_WIDTH < (1u << 16), "x0 | x1 << 16 in one word");
+
+struct RbItem {
+    int32_t row0, row1, x0, x1; // rows [row0, row1), columns [x0, x1); empty: row0 == row1
+};
+
+// the splat at position `pos` of the depth order (pos < nv), as isect_emit_scan_kernel gathers it
+GS_DEV RbItem rb_item(uint32_t pos, uint32_t nv, uint32_t N, uint32_t C, const int32_t *__restrict__ perm, const float *__restrict__ means2d,
+                      uint32_t s_m2, const int32_t *__restrict__ radii, float tile_size, int32_t tw, int32_t th) {
+    RbItem it = {0, 0, 0, 0};
+    if (pos >= nv) return it;
+    const uint32_t e = (uint32_t)perm[pos];
+    const int32_t r = radii[e];
+    if (r <= 0) return it;
+    const float2 m = *reinterpret_cast<const float2 *>(means2d + (size_t)e * s_m2);
+    const TileBox b = tile_box(m.x, m.y, r, tile_size, tw, th);
+    const uint32_t cid = e / N;
+    if (b.x1 <= b.x0 || b.y1 <= b.y0 || cid >= C) return it;
+    it.row0 = (int32_t)cid * th + b.y0;
+    it.row1 = (int32_t)cid * th + b.y1;
+    it.x0 = b.x0;
+    it.x1 = b.x1;
+    return it;
+}
+
+// inclusive scan of one int per thread over the workgroup (WAVES waves); s_w: WAVES ints, free again on return
+template <uint32_t WAVES>
+GS_DEV int32_t rb_block_inclusive_scan(int32_t v, int32_t *s_w) {
+    const uint32_t lane = threadIdx.x % GS_WAVE, wave = threadIdx.x / GS_WAVE;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int32_t o = __shfl_up(v, off, 64);
+        if (lane >= (uint32_t)off) v += o;
+    }
+    if (lane == GS_WAVE - 1) s_w[wave] = v;
+    __syncthreads();
+    int32_t base = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < WAVES; ++w)
+        if (w < wave) base += s_w[w];
+    __syncthreads();
+    return base + v;
+}
+
+GS_DEV uint32_t rb_nv(uint32_t n_elems, uint32_t n_kept, const uint32_t *__restrict__ n_valid) {
+    const uint32_t nv = min(n_elems, n_kept);
+    return n_valid != nullptr ? min(nv, *n_valid) : nv;
+}
+
+// Stage 1: per block of RB_ITEMS positions, the number of splats that cover each row and the pairs they have there
+// (difference arrays in LDS: integer sums, their order does not matter).  row_cnt / row_pairs: [rows][n_blocks].
+__global__ void __launch_bounds__(GS_BLOCK) rb_row_hist_kernel(
+    uint32_t n_elems, uint32_t n_kept, uint32_t N, uint32_t C, const int32_t *__restrict__ perm, const uint32_t *__restrict__ n_valid,
+    const float *__restrict__ means2d, uint32_t s_m2, const int32_t *__restrict__ radii, float tile_size, int32_t tw, int32_t th,
+    uint32_t rows, uint32_t n_blocks, uint32_t *__restrict__ row_cnt, uint32_t *__restrict__ row_pairs, uint2 *__restrict__ items) {
+    __shared__ int32_t s_cnt[RB_KEYS + 1], s_pairs[RB_KEYS + 1], s_w[RB_WAVES];
+    const uint32_t tid = threadIdx.x;
+    s_cnt[tid] = 0;
+    s_pairs[tid] = 0;
+    if (tid == 0) s_cnt[RB_KEYS] = s_pairs[RB_KEYS] = 0;
+    __syncthreads();
+    const uint32_t nv = rb_nv(n_elems, n_kept, n_valid);
+    RbItem its[RB_POS_ROUNDS]; // (all gathers of the thread in flight together)
+#pragma unroll
+    for (uint32_t k = 0; k < RB_POS_ROUNDS; ++k)
+        its[k] = rb_item(blockIdx.x * RB_POS_ITEMS + k * GS_BLOCK + tid, nv, N, C, perm, means2d, s_m2, radii, tile_size, tw, th);
+#pragma unroll
+    for (uint32_t k = 0; k < RB_POS_ROUNDS; ++k) {
+        const RbItem it = its[k];
+        // the item, for stage 3 (rows | columns, 16 bits each): the gathers through perm happen once
+        const uint32_t pos = blockIdx.x * RB_POS_ITEMS + k * GS_BLOCK + tid;
+        if (pos < nv) items[pos] = make_uint2((uint32_t)it.row0 | ((uint32_t)it.row1 << 16), (uint32_t)it.x0 | ((uint32_t)it.x1 << 16));
+        if (it.row1 > it.row0) {
+            const int32_t w = it.x1 - it.x0;
+            atomicAdd(&s_cnt[it.row0], 1);
+            atomicAdd(&s_cnt[it.row1], -1);
+            atomicAdd(&s_pairs[it.row0], w);
+            atomicAdd(&s_pairs[it.row1], -w);
+        }
+    }
+    __syncthreads();
+    const int32_t c = rb_block_inclusive_scan<RB_WAVES>(s_cnt[tid], s_w);
+    const int32_t p = rb_block_inclusive_scan<RB_WAVES>(s_pairs[tid], s_w);
+    if (tid < rows) {
+        row_cnt[(size_t)tid * n_blocks + blockIdx.x] = (uint32_t)c;
+        row_pairs[(size_t)tid * n_blocks + blockIdx.x] = (uint32_t)p;
+    }
+}
+
+// Stage 2 (one workgroup per row): exclusive scan of the row's counts over the blocks, in place -- the place of every block's
+// first entry inside the row's list -- and the row's totals: row_total[r] entries, row_total[rows + r] pairs.
+__global__ void __launch_bounds__(GS_BLOCK) rb_row_scan_kernel(
+    uint32_t rows, uint32_t n_blocks, uint32_t *__restrict__ row_cnt, const uint32_t *__restrict__ row_pairs,
+    uint32_t *__restrict__ row_total, uint32_t tw, int32_t *__restrict__ tile_total) {
+    __shared__ int32_t s_w[RB_WAVES];
+    __shared__ uint32_t s_tot;
+    const uint32_t tid = threadIdx.x, r = blockIdx.x;
+    if (tid < tw) tile_total[(size_t)r * tw + tid] = 0; // stage 4 adds the chunks' column counts up here (the offsets array)
+    uint32_t *cnt = row_cnt + (size_t)r * n_blocks;
+    const uint32_t *pairs = row_pairs + (size_t)r * n_blocks;
+    uint32_t carry = 0, psum = 0;
+    for (uint32_t b0 = 0; b0 < n_blocks; b0 += GS_BLOCK) {
+        const uint32_t b = b0 + tid;
+        const uint32_t c = b < n_blocks ? cnt[b] : 0u;
+        psum += b < n_blocks ? pairs[b] : 0u;
+        const uint32_t inc = (uint32_t)rb_block_inclusive_scan<RB_WAVES>((int32_t)c, s_w);
+        if (b < n_blocks) cnt[b] = carry + inc - c;
+        if (tid == GS_BLOCK - 1) s_tot = inc;
+        __syncthreads();
+        carry += s_tot;
+        __syncthreads();
+    }
+    const uint32_t ptot = (uint32_t)rb_block_inclusive_scan<RB_WAVES>((int32_t)psum, s_w);
+    if (tid == GS_BLOCK - 1) {
+        row_total[r] = carry;
+        row_total[rows + r] = ptot;
+    }
+}
+
+// What the later stages need of the rows, from row_total, by every workgroup for itself (rows <= 256 values, one scan each):
+// s_rs[r] = where list r begins (s_rs[rows] = all entries); s_cf[r] = number of chunks (RB_ITEMS entries, never across two
+// rows) in front of row r.  Both hold rows + 1 values.  Returns the pairs of the rows in front of row `tid` (0 from `rows` on).
+GS_DEV uint32_t rb_row_tables(uint32_t rows, const uint32_t *__restrict__ row_total, uint32_t *s_rs, uint32_t *s_cf, int32_t *s_w) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t len = tid < rows ? row_total[tid] : 0u, pairs = tid < rows ? row_total[rows + tid] : 0u;
+    const uint32_t nc = (len + RB_ITEMS - 1) / RB_ITEMS;
+    const uint32_t rs = (uint32_t)rb_block_inclusive_scan<RB_WAVES>((int32_t)len, s_w);
+    const uint32_t cf = (uint32_t)rb_block_inclusive_scan<RB_WAVES>((int32_t)nc, s_w);
+    const uint32_t pb = (uint32_t)rb_block_inclusive_scan<RB_WAVES>((int32_t)pairs, s_w);
+    s_rs[tid] = rs - len;
+    s_cf[tid] = cf - nc;
+    if (tid == GS_BLOCK - 1) {
+        s_rs[RB_KEYS] = rs;
+        s_cf[RB_KEYS] = cf;
+    }
+    __syncthreads();
+    return pb - pairs;
+}
+
+// the same tables as stage 3's first workgroup left them in memory (stages 4 to 6); ends with a barrier
+GS_DEV void rb_load_tables(uint32_t rows, const uint32_t *__restrict__ tables, uint32_t *s_rs, uint32_t *s_cf) {
+    for (uint32_t i = threadIdx.x; i <= rows; i += GS_BLOCK) {
+        s_rs[i] = tables[i];
+        s_cf[i] = tables[(rows + 1) + i];
+    }
+    __syncthreads();
+}
+
+// Rank of every item among the EARLIER items of the workgroup's list that cover the same key (row or column), for every key
+// in the item's range [lo, hi).  Thread t holds the items k * GS_BLOCK + t of the list, k < R; R * 4 wave slots in list order.
+// The lanes of a slot OR their lane bit into one 64-bit mask per key; rank = the bits below the lane's own + the counts of
+// the earlier slots (s_sbase) -- a function of the list order alone.  rb_rank_prepare builds masks and slot bases and returns
+// the list's number of items that cover key `tid`; all threads of the workgroup call it together, and a barrier has to follow
+// before rb_rank_of is used (and another before the next call).
+template <uint32_t R>
+GS_DEV uint32_t rb_rank_prepare(const int32_t (&lo)[R], const int32_t (&hi)[R], uint32_t n_keys, unsigned long long (*s_mask)[RB_KEYS],
+                                uint32_t (*s_sbase)[RB_KEYS]) {
+    const uint32_t tid = threadIdx.x, lane = tid % GS_WAVE, wave = tid / GS_WAVE;
+#pragma unroll
+    for (uint32_t s = 0; s < R * RB_WAVES; ++s) s_mask[s][tid] = 0ull;
+    __syncthreads();
+    const unsigned long long bit = 1ull << lane;
+#pragma unroll
+    for (uint32_t k = 0; k < R; ++k)
+        for (int32_t key = lo[k]; key < hi[k]; ++key) atomicOr(&s_mask[k * RB_WAVES + wave][key], bit);
+    __syncthreads();
+    uint32_t b = 0;
+    if (tid < n_keys) {
+#pragma unroll
+        for (uint32_t s = 0; s < R * RB_WAVES; ++s) {
+            s_sbase[s][tid] = b;
+            b += (uint32_t)__popcll(s_mask[s][tid]);
+        }
+    }
+    return b;
+}
+GS_DEV uint32_t rb_rank_of(uint32_t k, int32_t key, const unsigned long long (*s_mask)[RB_KEYS], const uint32_t (*s_sbase)[RB_KEYS]) {
+    const uint32_t lane = threadIdx.x % GS_WAVE, s = k * RB_WAVES + threadIdx.x / GS_WAVE;
+    return s_sbase[s][key] + (uint32_t)__popcll(s_mask[s][key] & ((1ull << lane) - 1ull));
+}
+
+// Stage 3: one 8-byte entry (position, x0 | x1 << 16) per splat and covered row, into that row's list in position order.
+__global__ void __launch_bounds__(GS_BLOCK) rb_row_scatter_kernel(
+    uint32_t n_elems, uint32_t n_kept, const uint32_t *__restrict__ n_valid, const uint2 *__restrict__ items, uint32_t rows, uint32_t n_blocks,
+    const uint32_t *__restrict__ row_base, const uint32_t *__restrict__ row_total, uint32_t *__restrict__ tables, uint2 *__restrict__ entries,
+    uint32_t capacity) {
+    __shared__ unsigned long long s_mask[RB_POS_ROUNDS * RB_WAVES][RB_KEYS];
+    __shared__ uint32_t s_sbase[RB_POS_ROUNDS * RB_WAVES][RB_KEYS];
+    __shared__ uint32_t s_gbase[RB_KEYS], s_rs[RB_KEYS + 1], s_cf[RB_KEYS + 1];
+    __shared__ int32_t s_w[RB_WAVES];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nv = rb_nv(n_elems, n_kept, n_valid);
+    int32_t lo[RB_POS_ROUNDS], hi[RB_POS_ROUNDS];
+    uint2 ent[RB_POS_ROUNDS];
+#pragma unroll
+    for (uint32_t k = 0; k < RB_POS_ROUNDS; ++k) {
+        const uint32_t pos = blockIdx.x * RB_POS_ITEMS + k * GS_BLOCK + tid;
+        const uint2 it = pos < nv ? items[pos] : make_uint2(0u, 0u);
+        lo[k] = (int32_t)min(it.x & 0xffffu, rows);
+        hi[k] = (int32_t)min(it.x >> 16, rows);
+        ent[k] = make_uint2(pos, it.y);
+    }
+    const uint32_t pb = rb_row_tables(rows, row_total, s_rs, s_cf, s_w);
+    if (blockIdx.x == 0) { // the same in every workgroup: the first one leaves them for stages 4 to 6 (row_start | chunk_first | pairs_before)
+        for (uint32_t i = tid; i <= rows; i += GS_BLOCK) {
+            tables[i] = s_rs[i];
+            tables[(rows + 1) + i] = s_cf[i];
+        }
+        if (tid < rows) tables[2 * (rows + 1) + tid] = pb;
+    }
+    s_gbase[tid] = tid < rows ? s_rs[tid] + row_base[(size_t)tid * n_blocks + blockIdx.x] : 0u;
+    rb_rank_prepare<RB_POS_ROUNDS>(lo, hi, rows, s_mask, s_sbase);
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < RB_POS_ROUNDS; ++k)
+        for (int32_t row = lo[k]; row < hi[k]; ++row) {
+            const uint32_t place = s_gbase[row] + rb_rank_of(k, row, s_mask, s_sbase);
+            if (place < capacity) entries[place] = ent[k];
+        }
+}
+
+// chunk -> (row, entry range).  s_cf / s_rs: chunk_first / row_start in LDS (rows + 1 values each).
+GS_DEV uint32_t rb_chunk_row(uint32_t chunk, uint32_t rows, const uint32_t *s_cf) {
+    uint32_t r = 0; // largest r with chunk_first[r] <= chunk (rows without entries share their successor's value and are skipped)
+#pragma unroll
+    for (uint32_t step = RB_KEYS / 2; step > 0; step >>= 1)
+        if (r + step < rows && s_cf[r + step] <= chunk) r += step;
+    return r;
+}
+
+// Stage 4: per chunk of a row list, the number of its entries that cover each column.  col_cnt: [chunks][tw].
+__global__ void __launch_bounds__(GS_BLOCK) rb_col_hist_kernel(
+    uint32_t rows, uint32_t tw, const uint32_t *__restrict__ tables, const uint2 *__restrict__ entries, uint32_t capacity,
+    uint32_t max_chunks, uint32_t *__restrict__ col_cnt, int32_t *__restrict__ tile_total) {
+    __shared__ uint32_t s_cf[RB_KEYS + 1], s_rs[RB_KEYS + 1];
+    __shared__ int32_t s_diff[RB_KEYS + 1], s_w[RB_WAVES];
+    const uint32_t tid = threadIdx.x;
+    rb_load_tables(rows, tables, s_rs, s_cf);
+    const uint32_t n_chunks = min(s_cf[rows], max_chunks);
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint32_t r = rb_chunk_row(chunk, rows, s_cf);
+        const uint32_t start = s_rs[r] + (chunk - s_cf[r]) * RB_ITEMS, end = min(min(start + RB_ITEMS, s_rs[r + 1]), capacity);
+        s_diff[tid] = 0;
+        if (tid == 0) s_diff[RB_KEYS] = 0;
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < RB_ROUNDS; ++k) {
+            const uint32_t i = start + k * GS_BLOCK + tid;
+            if (i < end) {
+                const uint32_t xx = entries[i].y;
+                atomicAdd(&s_diff[min(xx & 0xffffu, RB_KEYS)], 1);
+                atomicAdd(&s_diff[min(xx >> 16, RB_KEYS)], -1);
+            }
+        }
+        __syncthreads();
+        const int32_t c = rb_block_inclusive_scan<RB_WAVES>(s_diff[tid], s_w);
+        if (tid < tw) {
+            col_cnt[(size_t)chunk * tw + tid] = (uint32_t)c;
+            if (c != 0) atomicAdd(&tile_total[(size_t)r * tw + tid], c); // (an integer sum: the same whatever the order)
+        }
+    }
+}
+
+// Stage 5, two kinds of workgroups in one launch.  Workgroup r < rows: offsets[tile] of row r from the tile totals stage 4
+// left there = pairs of the rows in front + pairs of the row's tiles in front -- every tile is written, the empty ones too.
+// The others: one wave per tile, the exclusive scan of the tile's counts over its row's chunks, in place (64 chunks a step).
+__global__ void __launch_bounds__(GS_BLOCK) rb_col_scan_kernel(
+    uint32_t rows, uint32_t tw, const uint32_t *__restrict__ tables, uint32_t max_chunks, uint32_t *__restrict__ col_cnt,
+    int32_t *__restrict__ offsets) {
+    __shared__ int32_t s_w[RB_WAVES];
+    const uint32_t tid = threadIdx.x, lane = tid % GS_WAVE;
+    if (blockIdx.x < rows) { // (block-uniform)
+        const uint32_t r = blockIdx.x;
+        const uint32_t tot = tid < tw ? (uint32_t)offsets[(size_t)r * tw + tid] : 0u;
+        const uint32_t inc = (uint32_t)rb_block_inclusive_scan<RB_WAVES>((int32_t)tot, s_w);
+        if (tid < tw) offsets[(size_t)r * tw + tid] = (int32_t)(tables[2 * (rows + 1) + r] + inc - tot);
+        return;
+    }
+    const uint32_t task = (blockIdx.x - rows) * RB_WAVES + tid / GS_WAVE;
+    if (task >= rows * tw) return; // (wave-uniform; no barrier below)
+    const uint32_t r = task / tw, x = task - r * tw;
+    const uint32_t c0 = min(tables[(rows + 1) + r], max_chunks), c1 = min(tables[(rows + 1) + r + 1], max_chunks);
+    uint32_t carry = 0;
+    for (uint32_t cb = c0; cb < c1; cb += GS_WAVE) {
+        const uint32_t c = cb + lane;
+        uint32_t *p = col_cnt + (size_t)c * tw + x;
+        const uint32_t v = c < c1 ? *p : 0u;
+        uint32_t inc = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = __shfl_up(inc, off, 64);
+            if (lane >= (uint32_t)off) inc += o;
+        }
+        if (c < c1) *p = carry + inc - v;
+        carry += __shfl(inc, GS_WAVE - 1, 64);
+    }
+}
+
+// Stage 6: every chunk writes, for each of its entries and each column the entry covers, the pair's id and flatten id at
+// offsets[tile] + the chunk's base in the tile + the entry's rank among the chunk's earlier entries that cover the column.
+// The pairs of a chunk in one tile are neighbours in the output: they are first put in output order in LDS (column | entry,
+// 4 bytes a pair) and written from there, consecutive lanes to consecutive places; a chunk with more than RB_STAGE_CAP pairs
+// writes every pair straight from its entry's lane.
+__global__ void __launch_bounds__(GS_BLOCK) rb_expand_kernel(
+    uint32_t n_elems, uint32_t rows, uint32_t tw, uint32_t th, uint32_t tile_n_bits, const uint32_t *__restrict__ tables,
+    const uint2 *__restrict__ entries, uint32_t capacity, uint32_t max_chunks, const uint32_t *__restrict__ col_base,
+    const int32_t *__restrict__ offsets, const int32_t *__restrict__ perm, const uint64_t *__restrict__ sorted_keys,
+    const float *__restrict__ depths, uint32_t n_isects, int64_t *__restrict__ isect_ids, int32_t *__restrict__ flatten_ids) {
+    __shared__ unsigned long long s_mask[RB_ROUNDS * RB_WAVES][RB_KEYS];
+    __shared__ uint32_t s_sbase[RB_ROUNDS * RB_WAVES][RB_KEYS];
+    __shared__ uint32_t s_gbase[RB_KEYS], s_colpre[RB_KEYS + 1], s_cf[RB_KEYS + 1], s_rs[RB_KEYS + 1];
+    __shared__ uint32_t s_stage[RB_STAGE_CAP];
+    __shared__ int32_t s_v[RB_ITEMS], s_db[RB_ITEMS];
+    __shared__ int32_t s_w[RB_WAVES];
+    const uint32_t tid = threadIdx.x;
+    rb_load_tables(rows, tables, s_rs, s_cf);
+    const uint32_t n_chunks = min(s_cf[rows], max_chunks);
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint32_t r = rb_chunk_row(chunk, rows, s_cf);
+        const uint32_t start = s_rs[r] + (chunk - s_cf[r]) * RB_ITEMS, end = min(min(start + RB_ITEMS, s_rs[r + 1]), capacity);
+        const uint32_t cid = r / th, y = r - cid * th;
+        const uint32_t key_row = (cid << tile_n_bits) | (y * tw); // + column = the pair's 32-bit key
+        if (tid < tw) s_gbase[tid] = (uint32_t)offsets[(size_t)r * tw + tid] + col_base[(size_t)chunk * tw + tid];
+        int32_t lo[RB_ROUNDS], hi[RB_ROUNDS], v[RB_ROUNDS], db[RB_ROUNDS];
+        uint2 ent[RB_ROUNDS];
+#pragma unroll
+        for (uint32_t k = 0; k < RB_ROUNDS; ++k) {
+            const uint32_t i = start + k * GS_BLOCK + tid;
+            ent[k] = i < end ? entries[i] : make_uint2(0u, 0u);
+            if (ent[k].x >= n_elems) ent[k] = make_uint2(0u, 0u); // (never: positions come from stage 3; keeps the gathers in bounds)
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < RB_ROUNDS; ++k) {
+            lo[k] = (int32_t)min(ent[k].y & 0xffffu, tw);
+            hi[k] = (int32_t)min(ent[k].y >> 16, tw);
+            v[k] = 0;
+            db[k] = 0;
+            if (hi[k] > lo[k]) {
+                if (sorted_keys != nullptr) { // depths of visible splats are positive: their bits are the key's high half
+                    const uint64_t sk = sorted_keys[ent[k].x];
+                    v[k] = (int32_t)(uint32_t)sk;
+                    db[k] = (int32_t)(uint32_t)(sk >> 32);
+                } else {
+                    v[k] = perm[ent[k].x];
+                    db[k] = __float_as_int(depths[v[k]]);
+                }
+            }
+            s_v[k * GS_BLOCK + tid] = v[k];
+            s_db[k * GS_BLOCK + tid] = db[k];
+        }
+        const uint32_t cnt = rb_rank_prepare<RB_ROUNDS>(lo, hi, tw, s_mask, s_sbase);
+        const uint32_t inc = (uint32_t)rb_block_inclusive_scan<RB_WAVES>((int32_t)cnt, s_w); // (cnt is 0 from column tw on)
+        s_colpre[tid] = inc - cnt;
+        if (tid == GS_BLOCK - 1) s_colpre[RB_KEYS] = inc;
+        __syncthreads();
+        const uint32_t total = s_colpre[RB_KEYS];
+        // the id as the other routes form it: key << 32 | the depth's bits, sign-extended (isect_tiles.cu:91)
+        if (total <= RB_STAGE_CAP) { // (block-uniform)
+#pragma unroll
+            for (uint32_t k = 0; k < RB_ROUNDS; ++k)
+                for (int32_t x = lo[k]; x < hi[k]; ++x) {
+                    const uint32_t at = s_colpre[x] + rb_rank_of(k, x, s_mask, s_sbase);
+                    if (at < RB_STAGE_CAP) s_stage[at] = ((uint32_t)x << 16) | (k * GS_BLOCK + tid);
+                }
+            __syncthreads();
+            for (uint32_t i = tid; i < total; i += GS_BLOCK) {
+                const uint32_t w = s_stage[i], x = w >> 16, e = w & 0xffffu;
+                const uint32_t place = s_gbase[x] + (i - s_colpre[x]);
+                if (place < n_isects) {
+                    isect_ids[place] = (int64_t)((uint64_t)(key_row + x) << 32) | (int64_t)s_db[e];
+                    flatten_ids[place] = s_v[e];
+                }
+            }
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < RB_ROUNDS; ++k)
+                for (int32_t x = lo[k]; x < hi[k]; ++x) {
+                    const uint32_t place = s_gbase[x] + rb_rank_of(k, x, s_mask, s_sbase);
+                    if (place < n_isects) {
+                        isect_ids[place] = (int64_t)((uint64_t)(key_row + (uint32_t)x) << 32) | (int64_t)db[k];
+                        flatten_ids[place] = v[k];
+                    }
+                }
+        }
+        __syncthreads(); // the next chunk sets the tables and clears the masks
+    }
+}
+
 } // namespace
 
 extern "C" int32_t gs_isect_count(
@@ -706,6 +1108,67 @@ extern "C" size_t gs_isect_finish_work_bytes(uint64_t n_isects) {
     return 2 * finish_pairs_bytes(n_isects) + gs_sort_isect_temp_bytes(n_isects);
 }
 
+// ---- row binning: layout of its arrays in the work buffer, switch, route query
+namespace {
+struct RowBinLayout {
+    uint32_t n_blocks, max_chunks; // stage-1/3 blocks; upper bound of the chunks: sum ceil(len_r / RB_ITEMS) <= entries / RB_ITEMS + rows
+    size_t off_row_cnt, off_row_pairs, off_row_total, off_tables, off_items, off_col_cnt, total;
+};
+RowBinLayout rowbin_layout(uint64_t n_isects, uint32_t n_kept, uint32_t rows, uint32_t tw) {
+    RowBinLayout L;
+    L.n_blocks = gs_div_up(n_kept, RB_POS_ITEMS);
+    L.max_chunks = (uint32_t)(n_isects / RB_ITEMS) + rows;
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        size_t r = o;
+        o += (bytes + 255) & ~(size_t)255;
+        return r;
+    };
+    take((size_t)n_isects * sizeof(uint2)); // the row entries: at most one per pair (where the word arrays of the other routes live)
+    L.off_row_cnt = take((size_t)rows * L.n_blocks * sizeof(uint32_t));
+    L.off_row_pairs = take((size_t)rows * L.n_blocks * sizeof(uint32_t));
+    L.off_row_total = take((size_t)2 * rows * sizeof(uint32_t)); // entries | pairs of every row
+    L.off_tables = take((size_t)3 * (rows + 1) * sizeof(uint32_t)); // row_start | chunk_first | pairs_before
+    L.off_items = take((size_t)n_kept * sizeof(uint2));         // stage 1's item per position: rows | columns
+    L.off_col_cnt = take((size_t)L.max_chunks * tw * sizeof(uint32_t));
+    L.total = o;
+    return L;
+}
+std::atomic<int32_t> g_row_binning{1}, g_last_route{GS_ISECT_ROUTE_NONE};
+} // namespace
+
+extern "C" int32_t gs_isect_row_binning(int32_t on) { return on < 0 ? g_row_binning.load() : g_row_binning.exchange(on != 0 ? 1 : 0); }
+extern "C" int32_t gs_isect_last_route(void) { return g_last_route.load(); }
+extern "C" size_t gs_isect_row_binning_work_bytes(uint64_t n_isects, uint32_t n_kept, uint32_t rows, uint32_t tile_width) {
+    return rowbin_layout(n_isects, n_kept, rows, tile_width).total;
+}
+
+static int32_t isect_finish_rows(
+    uint32_t n_elems, uint32_t N, uint32_t n_isects, const int32_t *perm, const uint32_t *n_valid, const float *means2d, uint32_t s_m2,
+    const int32_t *radii, const float *depths, uint32_t tile_size, uint32_t tw, uint32_t th, uint32_t tile_n_bits, uint32_t C,
+    int64_t *isect_ids, int32_t *flatten_ids, int32_t *offsets, void *work, const RowBinLayout &L, uint32_t n_kept, const int64_t *sorted_keys,
+    hipStream_t st) {
+    const uint32_t rows = C * th;
+    uint2 *entries = (uint2 *)work;
+    uint32_t *row_cnt = (uint32_t *)((char *)work + L.off_row_cnt), *row_pairs = (uint32_t *)((char *)work + L.off_row_pairs);
+    uint32_t *row_total = (uint32_t *)((char *)work + L.off_row_total), *col_cnt = (uint32_t *)((char *)work + L.off_col_cnt);
+    uint2 *items = (uint2 *)((char *)work + L.off_items);
+    uint32_t *tables = (uint32_t *)((char *)work + L.off_tables);
+    // the chunk kernels walk the chunks with a stride: the host knows their number only as a bound
+    const uint32_t chunk_grid = min(L.max_chunks, 2048u);
+    hipLaunchKernelGGL(rb_row_hist_kernel, dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n_elems, n_kept, N, C, perm, n_valid, means2d, s_m2, radii,
+                       (float)tile_size, (int32_t)tw, (int32_t)th, rows, L.n_blocks, row_cnt, row_pairs, items);
+    hipLaunchKernelGGL(rb_row_scan_kernel, dim3(rows), dim3(GS_BLOCK), 0, st, rows, L.n_blocks, row_cnt, row_pairs, row_total, tw, offsets);
+    hipLaunchKernelGGL(rb_row_scatter_kernel, dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n_elems, n_kept, n_valid, items, rows, L.n_blocks, row_cnt,
+                       row_total, tables, entries, n_isects);
+    hipLaunchKernelGGL(rb_col_hist_kernel, dim3(chunk_grid), dim3(GS_BLOCK), 0, st, rows, tw, tables, entries, n_isects, L.max_chunks, col_cnt, offsets);
+    hipLaunchKernelGGL(rb_col_scan_kernel, dim3(rows + gs_div_up((uint64_t)rows * tw, RB_WAVES)), dim3(GS_BLOCK), 0, st, rows, tw, tables, L.max_chunks, col_cnt, offsets);
+    hipLaunchKernelGGL(rb_expand_kernel, dim3(chunk_grid), dim3(GS_BLOCK), 0, st, n_elems, rows, tw, th, tile_n_bits, tables, entries, n_isects,
+                       L.max_chunks, col_cnt, offsets, perm, (const uint64_t *)sorted_keys, depths, n_isects, isect_ids, flatten_ids);
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int32_t gs_isect_finish_presorted(
     uint32_t n_elems, uint32_t N, uint64_t n_isects, const int32_t *perm, const uint32_t *n_valid, const int64_t *camera_ids,
     const float *means2d, uint32_t means2d_stride, const int32_t *radii, const float *depths, const int32_t *tiles_per_gauss,
@@ -727,8 +1190,26 @@ extern "C" int32_t gs_isect_finish_presorted(
         while (n_kept_host > 0 && ((uint64_t)1 << pos_bits) < (uint64_t)n_kept_host) ++pos_bits;
         while (((uint32_t)1 << cam_bits) < C) ++cam_bits;
         const uint32_t key_bits_eff = tile_n_bits + cam_bits;
+        // ROW route: (splat, tile row) entries into row order by one counting pass, rows expanded into columns (see the header).
+        // Within its limits, and when its arrays fit the buffer that came in (the query is a function of n_isects alone).
+        const uint64_t rows64 = (uint64_t)C * tile_height;
+        if (g_row_binning.load() != 0 && n_kept_host > 0 && perm != nullptr && camera_ids == nullptr && key_bits_eff <= 31 &&
+            tile_n_bits < 32 && ((uint64_t)tile_width * tile_height >> tile_n_bits) == 0 && N > 0 && tile_size > 0 && means2d != nullptr &&
+            radii != nullptr && (sorted_keys != nullptr || depths != nullptr) && isect_ids != nullptr && flatten_ids != nullptr &&
+            means2d_stride >= 2 && means2d_stride % 2 == 0 && tile_width >= 1 && tile_width <= GS_ROW_BINNING_MAX_WIDTH && rows64 >= 1 &&
+            rows64 <= GS_ROW_BINNING_MAX_ROWS && n_isects < (1ull << 31) &&
+            rows64 * gs_div_up(n_kept_host, RB_POS_ITEMS) <= GS_ROW_BINNING_MAX_COUNTERS) {
+            const RowBinLayout L = rowbin_layout(n_isects, n_kept_host, (uint32_t)rows64, tile_width);
+            if (L.total <= work_bytes) {
+                g_last_route.store(GS_ISECT_ROUTE_ROWS);
+                return isect_finish_rows(n_elems, N, (uint32_t)n_isects, perm, n_valid, means2d, means2d_stride, radii, depths, tile_size,
+                                         tile_width, tile_height, tile_n_bits, C, isect_ids, flatten_ids, offsets, work, L, n_kept_host,
+                                         sorted_keys, (hipStream_t)stream);
+            }
+        }
         if (n_kept_host > 0 && perm != nullptr && camera_ids == nullptr && key_bits_eff >= 1 && key_bits_eff + pos_bits <= 32 &&
             key_bits_eff <= 31) {
+            g_last_route.store(GS_ISECT_ROUTE_PACKED);
             int32_t rc = gs_isect_emit_packed(n_elems, N, perm, n_valid, camera_ids, means2d, means2d_stride, radii, depths, tiles_per_gauss,
                                               group_sums, group_prefix, tile_size, tile_width, tile_height, tile_n_bits, pos_bits, keys32, stream);
             if (rc != 0) return rc;
@@ -737,6 +1218,7 @@ extern "C" int32_t gs_isect_finish_presorted(
             if (rc != 0) return rc;
             return gs_isect_offset_encode((uint32_t)n_isects, isect_ids, C, tile_width * tile_height, tile_n_bits, offsets, stream);
         }
+        g_last_route.store(GS_ISECT_ROUTE_PAIRS);
         int32_t rc = gs_isect_emit_presorted(n_elems, N, perm, n_valid, camera_ids, means2d, means2d_stride, radii, depths, tiles_per_gauss,
                                              group_sums, group_prefix, tile_size, tile_width, tile_height, tile_n_bits, 1, nullptr,
                                              keys32, vals, stream);

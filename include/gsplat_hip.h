@@ -451,6 +451,30 @@ int32_t gs_isect_finish_presorted(
                             gs_sort_pairs_u64_i32_drop, keys_in of gs_presort_buckets after the call): the packed route's last pass
                             then fetches flatten id and depth bits with one gather */,
     gs_stream_t stream);
+/* Row binning: the third route of gs_isect_finish_presorted.  The pairs of one splat are a rectangle of tiles and the splats
+ * arrive in depth order, so nothing has to be sorted pair by pair: the (splat, tile row) entries -- a quarter of the pairs on a
+ * 1080p frame -- are put into row order by ONE counting pass (row histogram per block of positions, scan, scatter of 8-byte
+ * entries position | x0 | x1), and every row list is then expanded into its columns (column histogram per chunk of a row
+ * list, scan, expand), which writes each output pair exactly once and yields the tile offsets from its own counts: six launches,
+ * no pair array, no offsets launch.  Ranks depend on list order alone (lane masks per wave, wave order inside a block, block
+ * order from the scans); same three outputs, bit for bit.  Taken when the packed route's preconditions hold (perm, n_kept_host
+ * > 0, no camera_ids), tile_width <= GS_ROW_BINNING_MAX_WIDTH and C * tile_height <= GS_ROW_BINNING_MAX_ROWS (the counters of a
+ * block live in LDS, one thread per column / row), C * tile_height * ceil(n_kept_host / 512) <= GS_ROW_BINNING_MAX_COUNTERS
+ * (row counters per block of 512 positions: they stay a small fraction of the entries), n_isects < 2^31, at most 31 key bits in use, and
+ * gs_isect_row_binning_work_bytes(...) fits the work buffer that was handed in (8 bytes per pair and per kept splat plus the
+ * counters, against the 16 bytes per pair of gs_isect_finish_work_bytes, which is unchanged: it fits when the kept splats
+ * cover two tiles or more on average); every other call takes the packed or the pair route as before.
+ *   gs_isect_row_binning(on): process-wide switch; on = 0 / 1 sets it, a negative value only reads; returns the previous state.
+ *   gs_isect_last_route(): GS_ISECT_ROUTE_* of the last gs_isect_finish_presorted call of this process that had pairs to bin. */
+enum {
+    GS_ROW_BINNING_MAX_WIDTH = 256,
+    GS_ROW_BINNING_MAX_ROWS = 256,
+    GS_ROW_BINNING_MAX_COUNTERS = 131072
+};
+enum { GS_ISECT_ROUTE_NONE = 0, GS_ISECT_ROUTE_PAIRS = 1, GS_ISECT_ROUTE_PACKED = 2, GS_ISECT_ROUTE_ROWS = 3 };
+int32_t gs_isect_row_binning(int32_t on);
+int32_t gs_isect_last_route(void);
+size_t gs_isect_row_binning_work_bytes(uint64_t n_isects, uint32_t n_kept, uint32_t rows, uint32_t tile_width);
 /* Packed pairs.  A pair is ONE 32-bit word  (camera << tile_n_bits | tile) << pos_bits | emission position, the position being
  * the splat's index in perm = its depth rank: the words of one tile are in depth order when the array is sorted stably on the
  * key bits, so no value array rides along, and the last pass writes the reference's outputs through perm:
