@@ -8,6 +8,7 @@
 // (correctly rounded) division / floor / ceil, so they are bit-exact against the
 // oracle.  The file is compiled with -ffp-contract=off.
 #include "gs_common.h"
+#include "scan_dev.h"
 
 #include <atomic>
 
@@ -131,8 +132,65 @@ struct EmitRec {
 constexpr uint32_t EMIT_SPW = GS_EMIT_SPW;
 constexpr uint32_t EMIT_WAVES = GS_BLOCK / GS_WAVE;
 
-// COMPACT: the pair is written as (32-bit key camera << tile_n_bits | tile, flatten id) = 8 bytes for the 32-bit pair sort
-// (gs_sort_isect_pairs rebuilds the 64-bit id with the depth bits in its last pass); else the reference's 64-bit id.
+// MODE 0: 64-bit ids + flatten ids; 1 (compact): 32-bit (camera, tile) key + flatten id for the 32-bit pair sort
+// (gs_sort_isect_pairs rebuilds the 64-bit id with the depth bits in its last pass); 2 (packed): ONE 32-bit word per pair,
+// key << pos_bits | emission position -- the position is the splat's depth rank, nothing else has to ride through the sort.
+
+// The emission record of element `e` at position `pos` of the emission order (has == false: the position holds no element).
+// Radius and mean go out together; a culled element leaves a record that owns no pair.
+template <int MODE>
+GS_DEV EmitRec emit_rec_of(bool has, uint32_t e, uint32_t pos, uint32_t N, const int64_t *__restrict__ camera_ids,
+                           const float *__restrict__ means2d, uint32_t s_m2, const int32_t *__restrict__ radii,
+                           const float *__restrict__ depths, float tile_size, int32_t tw, int32_t th, uint32_t tile_n_bits) {
+    EmitRec rec = {0, 0, 0, 0, 1};
+    int32_t r = 0;
+    float2 m = make_float2(0.f, 0.f);
+    if (has) {
+        r = radii[e];
+        m = *reinterpret_cast<const float2 *>(means2d + (size_t)e * s_m2);
+    }
+    if (r > 0) {
+        const TileBox b = tile_box(m.x, m.y, r, tile_size, tw, th);
+        const int64_t cid = camera_ids != nullptr ? camera_ids[e] : (int64_t)(e / N);
+        // raw IEEE bits of the (positive) depth, sign-extended like the reference's
+        // (int64_t)*(int32_t*)&depth  (isect_tiles.cu:91)
+        rec.key_base = MODE != 0 ? (cid << tile_n_bits) : ((cid << (32 + tile_n_bits)) | (int64_t)__float_as_int(depths[e]));
+        rec.id = MODE == 2 ? (int32_t)pos : (int32_t)e; // (packed: the emission position)
+        rec.x0 = b.x0;
+        rec.y0 = b.y0;
+        rec.w = max(b.x1 - b.x0, 1);
+    }
+    return rec;
+}
+
+// A wave writes the `total` pairs of its EMIT_SPW records to the output range that begins at out0, 64 slots at a time.
+// wstart: EMIT_SPW + 1 starts (last = total), published to the wave before the call.
+template <int MODE>
+GS_DEV void expand_pairs(const EmitRec *wrec, const int32_t *wstart, int32_t total, int64_t out0, int32_t tw,
+                         int64_t *__restrict__ isect_ids, uint32_t *__restrict__ keys32, int32_t *__restrict__ flatten_ids,
+                         uint32_t pos_bits) {
+    for (int32_t t = (int32_t)(threadIdx.x % GS_WAVE); t < total; t += GS_WAVE) {
+        // largest s with start[s] <= t (zero-count lanes share their successor's start and are skipped)
+        int32_t sidx = 0;
+#pragma unroll
+        for (int step = EMIT_SPW / 2; step > 0; step >>= 1)
+            if (wstart[sidx + step] <= t) sidx += step;
+        const EmitRec o = wrec[sidx];
+        const int32_t k = t - wstart[sidx];
+        // k / w without the ~30-instruction integer division: float quotient, then one exact correction step (the float
+        // result is off by at most one for any k < 2^24; k < tiles of the grid, which emit_check_args bounds)
+        int32_t dy = (int32_t)(((float)k + 0.5f) * __builtin_amdgcn_rcpf((float)o.w));
+        int32_t dx = k - dy * o.w;
+        if (dx < 0) { dy -= 1; dx += o.w; }
+        else if (dx >= o.w) { dy += 1; dx -= o.w; }
+        const int64_t tile_id = (int64_t)(o.y0 + dy) * tw + (o.x0 + dx);
+        if (MODE == 2) keys32[out0 + t] = ((uint32_t)(o.key_base | tile_id) << pos_bits) | (uint32_t)o.id;
+        else if (MODE == 1) keys32[out0 + t] = (uint32_t)(o.key_base | tile_id);
+        else isect_ids[out0 + t] = o.key_base | (tile_id << 32);
+        if (MODE != 2) flatten_ids[out0 + t] = o.id;
+    }
+}
+
 template <bool COMPACT>
 __global__ void __launch_bounds__(GS_BLOCK) isect_emit_kernel(
     uint32_t n_elems, uint32_t N, const int32_t *__restrict__ perm, const uint32_t *__restrict__ n_valid,
@@ -156,48 +214,17 @@ __global__ void __launch_bounds__(GS_BLOCK) isect_emit_kernel(
     if (out1 == out0) return; // nothing visible in this wave (wave-uniform)
     EmitRec *wrec = s_rec + wave * EMIT_SPW;
     int32_t *wstart = s_start + wave * (EMIT_SPW + 1);
-    if (lane < EMIT_SPW) {
-        EmitRec rec = {0, 0, 0, 0, 1};
-        int32_t start = (int32_t)(out1 - out0);
-        if (pos < n_elems) {
-            start = (int32_t)(((pos == 0) ? 0 : cum_tiles[pos - 1]) - out0);
-            // positions behind *n_valid hold no element (perm is only defined for the kept ones)
-            const bool has = n_valid == nullptr || pos < *n_valid;
-            const uint32_t i = has ? (perm != nullptr ? (uint32_t)perm[pos] : pos) : 0u;
-            const int32_t r = has ? radii[i] : 0;
-            if (r > 0) {
-                const float2 m = *reinterpret_cast<const float2 *>(means2d + (size_t)i * s_m2);
-                const TileBox b = tile_box(m.x, m.y, r, tile_size, tw, th);
-                const int64_t cid = camera_ids != nullptr ? camera_ids[i] : (int64_t)(i / N);
-                // raw IEEE bits of the (positive) depth, sign-extended like the reference's
-                // (int64_t)*(int32_t*)&depth  (isect_tiles.cu:91)
-                rec.key_base = COMPACT ? (cid << tile_n_bits) : ((cid << (32 + tile_n_bits)) | (int64_t)__float_as_int(depths[i]));
-                rec.id = (int32_t)i;
-                rec.x0 = b.x0;
-                rec.y0 = b.y0;
-                rec.w = max(b.x1 - b.x0, 1);
-            }
-        }
-        wrec[lane] = rec;
-        wstart[lane] = start;
-    }
-    if (lane == 0) wstart[EMIT_SPW] = (int32_t)(out1 - out0);
-    __builtin_amdgcn_wave_barrier();
     const int32_t total = (int32_t)(out1 - out0);
-    for (int32_t t = (int32_t)lane; t < total; t += GS_WAVE) {
-        // largest s with start[s] <= t (zero-count lanes share their successor's start and are skipped)
-        int32_t sidx = 0;
-#pragma unroll
-        for (int step = EMIT_SPW / 2; step > 0; step >>= 1)
-            if (wstart[sidx + step] <= t) sidx += step;
-        const EmitRec o = wrec[sidx];
-        const int32_t k = t - wstart[sidx];
-        const int32_t dy = k / o.w, dx = k - dy * o.w;
-        const int64_t tile_id = (int64_t)(o.y0 + dy) * tw + (o.x0 + dx);
-        if (COMPACT) keys32[out0 + t] = (uint32_t)(o.key_base | tile_id);
-        else isect_ids[out0 + t] = o.key_base | (tile_id << 32);
-        flatten_ids[out0 + t] = o.id;
+    if (lane < EMIT_SPW) {
+        // positions behind *n_valid hold no element (perm is only defined for the kept ones)
+        const bool has = pos < n_elems && (n_valid == nullptr || pos < *n_valid);
+        const uint32_t i = has ? (perm != nullptr ? (uint32_t)perm[pos] : pos) : 0u;
+        wrec[lane] = emit_rec_of<COMPACT ? 1 : 0>(has, i, pos, N, camera_ids, means2d, s_m2, radii, depths, tile_size, tw, th, tile_n_bits);
+        wstart[lane] = pos < n_elems ? (int32_t)(((pos == 0) ? 0 : cum_tiles[pos - 1]) - out0) : total;
     }
+    if (lane == 0) wstart[EMIT_SPW] = total;
+    __builtin_amdgcn_wave_barrier();
+    expand_pairs<COMPACT ? 1 : 0>(wrec, wstart, total, out0, tw, isect_ids, keys32, flatten_ids, 0u);
 }
 
 // Emission for the PRE-SORTED path with the prefix scan folded in (round 3: the two launches of gs_cumsum_gather_i32 and the
@@ -213,8 +240,7 @@ constexpr uint32_t EMIT_SCAN_SHIFT = 7; // 128 positions per workgroup: two grou
 constexpr uint32_t EMIT_SCAN_TILE = 1u << EMIT_SCAN_SHIFT;
 static_assert(EMIT_SCAN_TILE <= GS_BLOCK && EMIT_SCAN_TILE % EMIT_SPW == 0, "one position per thread");
 
-// MODE 0: 64-bit ids + flatten ids; 1 (compact): 32-bit (camera, tile) key + flatten id; 2 (packed): ONE 32-bit word per pair,
-// key << pos_bits | emission position -- the position is the splat's depth rank, nothing else has to ride through the sort
+// MODE: see emit_rec_of
 template <int MODE>
 __global__ void __launch_bounds__(GS_BLOCK) isect_emit_scan_kernel(
     uint32_t n_elems, uint32_t N, const int32_t *__restrict__ perm, const uint32_t *__restrict__ n_valid,
@@ -222,7 +248,6 @@ __global__ void __launch_bounds__(GS_BLOCK) isect_emit_scan_kernel(
     const float *__restrict__ depths, const int32_t *__restrict__ tiles_per_gauss, const uint32_t *__restrict__ group_sums,
     const int64_t *__restrict__ group_prefix, float tile_size, int32_t tw, int32_t th, uint32_t tile_n_bits,
     int64_t *__restrict__ isect_ids, uint32_t *__restrict__ keys32, int32_t *__restrict__ flatten_ids, uint32_t pos_bits) {
-    constexpr bool COMPACT = MODE != 0;
     __shared__ int32_t s_cum[EMIT_SCAN_TILE + 1]; // s_cum[j] = tiles of the block's positions [0, j)
     __shared__ int64_t s_red[GS_BLOCK / GS_WAVE];
     __shared__ int32_t s_wsum[GS_BLOCK / GS_WAVE];
@@ -249,31 +274,11 @@ __global__ void __launch_bounds__(GS_BLOCK) isect_emit_scan_kernel(
         e = pos < nv ? (perm != nullptr ? perm[pos] : (int32_t)pos) : -1;
         // the three gathers that hang off the element index go out together (they used to be two dependent phases: the tile
         // count here, radius and mean inside the per-group loop below -- once per group and wave)
-        int32_t r = 0;
-        float2 m = make_float2(0.f, 0.f);
-        if (e >= 0) {
-            c = tiles_per_gauss[e];
-            r = radii[e];
-            m = *reinterpret_cast<const float2 *>(means2d + (size_t)e * s_m2);
-        }
-        EmitRec rec = {0, 0, 0, 0, 1};
-        if (r > 0) {
-            const TileBox b = tile_box(m.x, m.y, r, tile_size, tw, th);
-            const int64_t cid = camera_ids != nullptr ? camera_ids[e] : (int64_t)((uint32_t)e / N);
-            rec.key_base = COMPACT ? (cid << tile_n_bits) : ((cid << (32 + tile_n_bits)) | (int64_t)__float_as_int(depths[e]));
-            rec.id = MODE == 2 ? (int32_t)pos : e; // (packed: the emission position)
-            rec.x0 = b.x0;
-            rec.y0 = b.y0;
-            rec.w = max(b.x1 - b.x0, 1);
-        }
-        s_rec[tid] = rec;
+        if (e >= 0) c = tiles_per_gauss[e];
+        s_rec[tid] = emit_rec_of<MODE>(e >= 0, (uint32_t)e, pos, N, camera_ids, means2d, s_m2, radii, depths, tile_size, tw, th, tile_n_bits);
     }
-    int32_t inc = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int32_t o = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off) inc += o;
-    }
+    // (the cross-wave part of the scan stays here: its two barriers also publish s_red and s_rec)
+    const int32_t inc = wave_inclusive_scan(c);
     if (lane == GS_WAVE - 1) s_wsum[wave] = inc;
     __syncthreads();
     int32_t wbase = 0;
@@ -297,25 +302,7 @@ __global__ void __launch_bounds__(GS_BLOCK) isect_emit_scan_kernel(
         __builtin_amdgcn_wave_barrier();
         const int32_t total = g1 - g0;
         const int64_t out0 = block_out0 + g0;
-        for (int32_t t = (int32_t)lane; t < total; t += GS_WAVE) {
-            int32_t sidx = 0;
-#pragma unroll
-            for (int step = EMIT_SPW / 2; step > 0; step >>= 1)
-                if (wstart[sidx + step] <= t) sidx += step;
-            const EmitRec o = wrec[sidx];
-            const int32_t k = t - wstart[sidx];
-            // k / w without the ~30-instruction integer division: float quotient, then one exact correction step (the float
-            // result is off by at most one for any k < 2^24)
-            int32_t dy = (int32_t)(((float)k + 0.5f) * __builtin_amdgcn_rcpf((float)o.w));
-            int32_t dx = k - dy * o.w;
-            if (dx < 0) { dy -= 1; dx += o.w; }
-            else if (dx >= o.w) { dy += 1; dx -= o.w; }
-            const int64_t tile_id = (int64_t)(o.y0 + dy) * tw + (o.x0 + dx);
-            if (MODE == 2) keys32[out0 + t] = ((uint32_t)(o.key_base | tile_id) << pos_bits) | (uint32_t)o.id;
-            else if (MODE == 1) keys32[out0 + t] = (uint32_t)(o.key_base | tile_id);
-            else isect_ids[out0 + t] = o.key_base | (tile_id << 32);
-            if (MODE != 2) flatten_ids[out0 + t] = o.id;
-        }
+        expand_pairs<MODE>(wrec, wstart, total, out0, tw, isect_ids, keys32, flatten_ids, pos_bits);
         __builtin_amdgcn_wave_barrier(); // the next group reuses wstart
     }
 }
@@ -369,34 +356,6 @@ constexpr int SCAN_TILE = GS_BLOCK * SCAN_ITEMS;
 // first position is valid reads cum_tiles up to its LAST position: an emit wave must never straddle a scan block
 static_assert(SCAN_TILE % EMIT_SPW == 0, "GS_EMIT_SPW must divide the scan tile (2048)");
 
-GS_DEV int64_t wave_inclusive_scan_i64(int64_t v) {
-    uint32_t lane = lane_id();
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int64_t o = __shfl_up(v, off, 64);
-        if (lane >= (uint32_t)off) v += o;
-    }
-    return v;
-}
-
-// block-wide exclusive scan of one int64 per thread; returns the exclusive prefix and
-// the block total.
-GS_DEV int64_t block_exclusive_scan_i64(int64_t v, int64_t &total, int64_t *s_wave /*[4]*/) {
-    uint32_t lane = threadIdx.x % GS_WAVE, wave = threadIdx.x / GS_WAVE;
-    int64_t inc = wave_inclusive_scan_i64(v);
-    if (lane == GS_WAVE - 1) s_wave[wave] = inc;
-    __syncthreads();
-    int64_t base = 0, t = 0;
-#pragma unroll
-    for (int w = 0; w < GS_BLOCK / GS_WAVE; ++w) {
-        if ((uint32_t)w < wave) base += s_wave[w];
-        t += s_wave[w];
-    }
-    total = t;
-    __syncthreads();
-    return base + inc - v;
-}
-
 // idx != nullptr: the scanned value is in[idx[i]]; n_valid != nullptr: positions >= *n_valid count as 0
 __global__ void __launch_bounds__(GS_BLOCK) scan_block_sums_kernel(
     uint64_t n, const int32_t *__restrict__ in, const int32_t *__restrict__ idx, const uint32_t *__restrict__ n_valid,
@@ -414,8 +373,7 @@ __global__ void __launch_bounds__(GS_BLOCK) scan_block_sums_kernel(
         uint64_t i = base + (uint64_t)k * GS_BLOCK + threadIdx.x;
         if (i < nv) s += idx != nullptr ? in[idx[i]] : in[i];
     }
-    int64_t total;
-    block_exclusive_scan_i64(s, total, s_wave);
+    const int64_t total = block_scan<GS_BLOCK / GS_WAVE>(s, s_wave).total;
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
@@ -426,10 +384,9 @@ __global__ void __launch_bounds__(GS_BLOCK) scan_spine_kernel(uint32_t n_blocks,
     for (uint32_t base = 0; base < n_blocks; base += GS_BLOCK) {
         uint32_t i = base + threadIdx.x;
         int64_t v = i < n_blocks ? block_sums[i] : 0;
-        int64_t total;
-        int64_t ex = block_exclusive_scan_i64(v, total, s_wave);
-        if (i < n_blocks) block_sums[i] = carry + ex;
-        carry += total;
+        const BlockScan<int64_t> sc = block_scan<GS_BLOCK / GS_WAVE>(v, s_wave);
+        if (i < n_blocks) block_sums[i] = carry + sc.exc;
+        carry += sc.total;
     }
 }
 
@@ -448,9 +405,7 @@ __global__ void __launch_bounds__(GS_BLOCK) scan_apply_kernel(
     if (raw_sums) {
         int64_t pre = 0;
         for (uint32_t i = threadIdx.x; i < blockIdx.x; i += GS_BLOCK) pre += block_sums[i];
-        int64_t tot;
-        block_exclusive_scan_i64(pre, tot, s_wave);
-        offset = tot;
+        offset = block_scan<GS_BLOCK / GS_WAVE>(pre, s_wave).total;
     } else {
         offset = block_sums[blockIdx.x];
     }
@@ -464,8 +419,7 @@ __global__ void __launch_bounds__(GS_BLOCK) scan_apply_kernel(
         v[k] = i < nv ? (idx != nullptr ? in[idx[i]] : in[i]) : 0;
         s += v[k];
     }
-    int64_t total;
-    int64_t run = block_exclusive_scan_i64(s, total, s_wave) + offset;
+    int64_t run = block_scan<GS_BLOCK / GS_WAVE>(s, s_wave).exc + offset;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
         uint64_t i = base + k;
@@ -528,25 +482,6 @@ GS_DEV RbItem rb_item(uint32_t pos, uint32_t nv, uint32_t N, uint32_t C, const i
     return it;
 }
 
-// inclusive scan of one int per thread over the workgroup (WAVES waves); s_w: WAVES ints, free again on return
-template <uint32_t WAVES>
-GS_DEV int32_t rb_block_inclusive_scan(int32_t v, int32_t *s_w) {
-    const uint32_t lane = threadIdx.x % GS_WAVE, wave = threadIdx.x / GS_WAVE;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int32_t o = __shfl_up(v, off, 64);
-        if (lane >= (uint32_t)off) v += o;
-    }
-    if (lane == GS_WAVE - 1) s_w[wave] = v;
-    __syncthreads();
-    int32_t base = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < WAVES; ++w)
-        if (w < wave) base += s_w[w];
-    __syncthreads();
-    return base + v;
-}
-
 GS_DEV uint32_t rb_nv(uint32_t n_elems, uint32_t n_kept, const uint32_t *__restrict__ n_valid) {
     const uint32_t nv = min(n_elems, n_kept);
     return n_valid != nullptr ? min(nv, *n_valid) : nv;
@@ -584,8 +519,8 @@ __global__ void __launch_bounds__(GS_BLOCK) rb_row_hist_kernel(
         }
     }
     __syncthreads();
-    const int32_t c = rb_block_inclusive_scan<RB_WAVES>(s_cnt[tid], s_w);
-    const int32_t p = rb_block_inclusive_scan<RB_WAVES>(s_pairs[tid], s_w);
+    const int32_t c = block_scan<RB_WAVES>(s_cnt[tid], s_w).inc;
+    const int32_t p = block_scan<RB_WAVES>(s_pairs[tid], s_w).inc;
     if (tid < rows) {
         row_cnt[(size_t)tid * n_blocks + blockIdx.x] = (uint32_t)c;
         row_pairs[(size_t)tid * n_blocks + blockIdx.x] = (uint32_t)p;
@@ -598,7 +533,6 @@ __global__ void __launch_bounds__(GS_BLOCK) rb_row_scan_kernel(
     uint32_t rows, uint32_t n_blocks, uint32_t *__restrict__ row_cnt, const uint32_t *__restrict__ row_pairs,
     uint32_t *__restrict__ row_total, uint32_t tw, int32_t *__restrict__ tile_total) {
     __shared__ int32_t s_w[RB_WAVES];
-    __shared__ uint32_t s_tot;
     const uint32_t tid = threadIdx.x, r = blockIdx.x;
     if (tid < tw) tile_total[(size_t)r * tw + tid] = 0; // stage 4 adds the chunks' column counts up here (the offsets array)
     uint32_t *cnt = row_cnt + (size_t)r * n_blocks;
@@ -608,18 +542,36 @@ __global__ void __launch_bounds__(GS_BLOCK) rb_row_scan_kernel(
         const uint32_t b = b0 + tid;
         const uint32_t c = b < n_blocks ? cnt[b] : 0u;
         psum += b < n_blocks ? pairs[b] : 0u;
-        const uint32_t inc = (uint32_t)rb_block_inclusive_scan<RB_WAVES>((int32_t)c, s_w);
-        if (b < n_blocks) cnt[b] = carry + inc - c;
-        if (tid == GS_BLOCK - 1) s_tot = inc;
-        __syncthreads();
-        carry += s_tot;
-        __syncthreads();
+        const BlockScan<int32_t> sc = block_scan<RB_WAVES>((int32_t)c, s_w);
+        if (b < n_blocks) cnt[b] = carry + (uint32_t)sc.exc;
+        carry += (uint32_t)sc.total;
     }
-    const uint32_t ptot = (uint32_t)rb_block_inclusive_scan<RB_WAVES>((int32_t)psum, s_w);
-    if (tid == GS_BLOCK - 1) {
+    const uint32_t ptot = (uint32_t)block_scan<RB_WAVES>((int32_t)psum, s_w).total;
+    if (tid == 0) {
         row_total[r] = carry;
         row_total[rows + r] = ptot;
     }
+}
+
+// rb_row_scatter_kernel's scan (through rb_row_tables), kept as the parent commit had it: with block_scan the kernel measured
+// 9.90 us against the parent's 9.77 us at config 2, over the bar of parent mean + spread (9.85 us; six alternating pairs,
+// profiles/binning_shared_stages_ab.txt).  Inclusive scan of one int per thread over the workgroup; s_w: WAVES ints, free again on return.
+template <uint32_t WAVES>
+GS_DEV int32_t rb_block_inclusive_scan(int32_t v, int32_t *s_w) {
+    const uint32_t lane = threadIdx.x % GS_WAVE, wave = threadIdx.x / GS_WAVE;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int32_t o = __shfl_up(v, off, 64);
+        if (lane >= (uint32_t)off) v += o;
+    }
+    if (lane == GS_WAVE - 1) s_w[wave] = v;
+    __syncthreads();
+    int32_t base = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < WAVES; ++w)
+        if (w < wave) base += s_w[w];
+    __syncthreads();
+    return base + v;
 }
 
 // What the later stages need of the rows, from row_total, by every workgroup for itself (rows <= 256 values, one scan each):
@@ -758,7 +710,7 @@ __global__ void __launch_bounds__(GS_BLOCK) rb_col_hist_kernel(
             }
         }
         __syncthreads();
-        const int32_t c = rb_block_inclusive_scan<RB_WAVES>(s_diff[tid], s_w);
+        const int32_t c = block_scan<RB_WAVES>(s_diff[tid], s_w).inc;
         if (tid < tw) {
             col_cnt[(size_t)chunk * tw + tid] = (uint32_t)c;
             if (c != 0) atomicAdd(&tile_total[(size_t)r * tw + tid], c); // (an integer sum: the same whatever the order)
@@ -777,7 +729,7 @@ __global__ void __launch_bounds__(GS_BLOCK) rb_col_scan_kernel(
     if (blockIdx.x < rows) { // (block-uniform)
         const uint32_t r = blockIdx.x;
         const uint32_t tot = tid < tw ? (uint32_t)offsets[(size_t)r * tw + tid] : 0u;
-        const uint32_t inc = (uint32_t)rb_block_inclusive_scan<RB_WAVES>((int32_t)tot, s_w);
+        const uint32_t inc = (uint32_t)block_scan<RB_WAVES>((int32_t)tot, s_w).inc;
         if (tid < tw) offsets[(size_t)r * tw + tid] = (int32_t)(tables[2 * (rows + 1) + r] + inc - tot);
         return;
     }
@@ -790,12 +742,7 @@ __global__ void __launch_bounds__(GS_BLOCK) rb_col_scan_kernel(
         const uint32_t c = cb + lane;
         uint32_t *p = col_cnt + (size_t)c * tw + x;
         const uint32_t v = c < c1 ? *p : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= (uint32_t)off) inc += o;
-        }
+        const uint32_t inc = wave_inclusive_scan(v);
         if (c < c1) *p = carry + inc - v;
         carry += __shfl(inc, GS_WAVE - 1, 64);
     }
@@ -840,21 +787,12 @@ __global__ void __launch_bounds__(GS_BLOCK) rb_expand_kernel(
             hi[k] = (int32_t)min(ent[k].y >> 16, tw);
             v[k] = 0;
             db[k] = 0;
-            if (hi[k] > lo[k]) {
-                if (sorted_keys != nullptr) { // depths of visible splats are positive: their bits are the key's high half
-                    const uint64_t sk = sorted_keys[ent[k].x];
-                    v[k] = (int32_t)(uint32_t)sk;
-                    db[k] = (int32_t)(uint32_t)(sk >> 32);
-                } else {
-                    v[k] = perm[ent[k].x];
-                    db[k] = __float_as_int(depths[v[k]]);
-                }
-            }
+            if (hi[k] > lo[k]) pair_id_of(ent[k].x, sorted_keys, perm, depths, &v[k], &db[k]);
             s_v[k * GS_BLOCK + tid] = v[k];
             s_db[k * GS_BLOCK + tid] = db[k];
         }
         const uint32_t cnt = rb_rank_prepare<RB_ROUNDS>(lo, hi, tw, s_mask, s_sbase);
-        const uint32_t inc = (uint32_t)rb_block_inclusive_scan<RB_WAVES>((int32_t)cnt, s_w); // (cnt is 0 from column tw on)
+        const uint32_t inc = (uint32_t)block_scan<RB_WAVES>((int32_t)cnt, s_w).inc; // (cnt is 0 from column tw on)
         s_colpre[tid] = inc - cnt;
         if (tid == GS_BLOCK - 1) s_colpre[RB_KEYS] = inc;
         __syncthreads();
@@ -986,20 +924,47 @@ extern "C" int32_t gs_gather_i32(uint32_t n, const int32_t *src, const int32_t *
     return 0;
 }
 
+// The argument checks the emission entry points share.  `who` is the name the error text carries (GS_CHECK_ARG would print
+// this function's); ptr_msg: the entry point's own pointer check, NULL when it passed.
+static int32_t emit_check_args(const char *who, const char *ptr_msg, const int64_t *camera_ids, uint32_t N, uint32_t tile_n_bits,
+                               uint32_t means2d_stride, uint32_t tile_width, uint32_t tile_height) {
+    const char *msg = ptr_msg != nullptr                               ? ptr_msg
+                      : !(camera_ids != nullptr || N > 0)              ? "N must be > 0 when camera_ids is NULL"
+                      : !(tile_n_bits < 32)                            ? "tile_n_bits must be < 32"
+                      : !(means2d_stride >= 2 && means2d_stride % 2 == 0) ? "means2d_stride must be even and >= 2"
+                      // expand_pairs divides a pair's offset inside its splat's box (< tiles of the grid) in float arithmetic
+                      : !((uint64_t)tile_width * tile_height <= (1ull << 24)) ? "the tile grid must have at most 2^24 tiles"
+                                                                       : nullptr;
+    if (msg == nullptr) return 0;
+    gs_set_error("%s: %s", who, msg);
+    return 1;
+}
+
+template <bool COMPACT>
+static int32_t emit_launch(
+    const char *who, const char *ptr_msg, uint32_t n_elems, uint32_t N, const int32_t *perm, const uint32_t *n_valid,
+    const int64_t *camera_ids, const float *means2d, uint32_t means2d_stride, const int32_t *radii, const float *depths,
+    const int64_t *cum_tiles_per_gauss, uint32_t tile_size, uint32_t tile_width, uint32_t tile_height, uint32_t tile_n_bits,
+    int64_t *isect_ids, uint32_t *keys32, int32_t *flatten_ids, gs_stream_t stream) {
+    if (emit_check_args(who, ptr_msg, camera_ids, N, tile_n_bits, means2d_stride, tile_width, tile_height)) return 1;
+    hipLaunchKernelGGL(isect_emit_kernel<COMPACT>, dim3(gs_div_up(n_elems, EMIT_WAVES * EMIT_SPW)), dim3(GS_BLOCK), 0,
+                       (hipStream_t)stream, n_elems, N, perm, n_valid, camera_ids, means2d, means2d_stride, radii, depths,
+                       cum_tiles_per_gauss, (float)tile_size, (int32_t)tile_width, (int32_t)tile_height,
+                       tile_n_bits, isect_ids, keys32, flatten_ids);
+    return 0;
+}
+
 extern "C" int32_t gs_isect_emit(
     uint32_t n_elems, uint32_t N, const int32_t *perm, const uint32_t *n_valid, const int64_t *camera_ids, const float *means2d,
     uint32_t means2d_stride, const int32_t *radii, const float *depths, const int64_t *cum_tiles_per_gauss,
     uint32_t tile_size, uint32_t tile_width, uint32_t tile_height, uint32_t tile_n_bits,
     int64_t *isect_ids, int32_t *flatten_ids, gs_stream_t stream) {
     if (n_elems == 0) return 0;
-    GS_CHECK_ARG(means2d && radii && depths && cum_tiles_per_gauss, "null pointer");
-    GS_CHECK_ARG(camera_ids != nullptr || N > 0, "N must be > 0 when camera_ids is NULL");
-    GS_CHECK_ARG(tile_n_bits < 32, "tile_n_bits must be < 32");
-    GS_CHECK_ARG(means2d_stride >= 2 && means2d_stride % 2 == 0, "means2d_stride must be even and >= 2");
-    hipLaunchKernelGGL(isect_emit_kernel<false>, dim3(gs_div_up(n_elems, EMIT_WAVES * EMIT_SPW)), dim3(GS_BLOCK), 0,
-                       (hipStream_t)stream, n_elems, N, perm, n_valid, camera_ids, means2d, means2d_stride, radii, depths,
-                       cum_tiles_per_gauss, (float)tile_size, (int32_t)tile_width, (int32_t)tile_height,
-                       tile_n_bits, isect_ids, (uint32_t *)nullptr, flatten_ids);
+    const bool ptrs = means2d && radii && depths && cum_tiles_per_gauss;
+    if (int32_t rc = emit_launch<false>(__func__, ptrs ? nullptr : "null pointer", n_elems, N, perm, n_valid, camera_ids, means2d,
+                                        means2d_stride, radii, depths, cum_tiles_per_gauss, tile_size, tile_width, tile_height,
+                                        tile_n_bits, isect_ids, nullptr, flatten_ids, stream))
+        return rc;
     GS_CHECK_LAUNCH();
     return 0;
 }
@@ -1010,14 +975,11 @@ extern "C" int32_t gs_isect_emit_compact(
     uint32_t tile_size, uint32_t tile_width, uint32_t tile_height, uint32_t tile_n_bits,
     uint32_t *keys32, int32_t *flatten_ids, gs_stream_t stream) {
     if (n_elems == 0) return 0;
-    GS_CHECK_ARG(means2d && radii && depths && cum_tiles_per_gauss && keys32 && flatten_ids, "null pointer");
-    GS_CHECK_ARG(camera_ids != nullptr || N > 0, "N must be > 0 when camera_ids is NULL");
-    GS_CHECK_ARG(tile_n_bits < 32, "tile_n_bits must be < 32");
-    GS_CHECK_ARG(means2d_stride >= 2 && means2d_stride % 2 == 0, "means2d_stride must be even and >= 2");
-    hipLaunchKernelGGL(isect_emit_kernel<true>, dim3(gs_div_up(n_elems, EMIT_WAVES * EMIT_SPW)), dim3(GS_BLOCK), 0,
-                       (hipStream_t)stream, n_elems, N, perm, n_valid, camera_ids, means2d, means2d_stride, radii, depths,
-                       cum_tiles_per_gauss, (float)tile_size, (int32_t)tile_width, (int32_t)tile_height,
-                       tile_n_bits, (int64_t *)nullptr, keys32, flatten_ids);
+    const bool ptrs = means2d && radii && depths && cum_tiles_per_gauss && keys32 && flatten_ids;
+    if (int32_t rc = emit_launch<true>(__func__, ptrs ? nullptr : "null pointer", n_elems, N, perm, n_valid, camera_ids, means2d,
+                                       means2d_stride, radii, depths, cum_tiles_per_gauss, tile_size, tile_width, tile_height,
+                                       tile_n_bits, nullptr, keys32, flatten_ids, stream))
+        return rc;
     GS_CHECK_LAUNCH();
     return 0;
 }
@@ -1033,27 +995,17 @@ static int32_t emit_presorted_launch(
     const float *means2d, uint32_t means2d_stride, const int32_t *radii, const float *depths, const int32_t *tiles_per_gauss,
     const uint32_t *group_sums, const int64_t *group_prefix, uint32_t tile_size, uint32_t tile_width, uint32_t tile_height,
     uint32_t tile_n_bits, int64_t *isect_ids, uint32_t *keys32, int32_t *flatten_ids, gs_stream_t stream) {
-    const int32_t compact = mode != 0;
     if (n_elems == 0) return 0;
-    GS_CHECK_ARG(means2d && radii && depths && tiles_per_gauss && (group_sums || group_prefix) && (flatten_ids || mode == 2), "null pointer");
-    GS_CHECK_ARG(compact ? keys32 != nullptr : isect_ids != nullptr, "null output");
-    GS_CHECK_ARG(camera_ids != nullptr || N > 0, "N must be > 0 when camera_ids is NULL");
-    GS_CHECK_ARG(tile_n_bits < 32, "tile_n_bits must be < 32");
-    GS_CHECK_ARG(means2d_stride >= 2 && means2d_stride % 2 == 0, "means2d_stride must be even and >= 2");
+    const char *ptr_msg = !(means2d && radii && depths && tiles_per_gauss && (group_sums || group_prefix) && (flatten_ids || mode == 2)) ? "null pointer"
+                          : !(mode != 0 ? keys32 != nullptr : isect_ids != nullptr)                                                    ? "null output"
+                                                                                                                                        : nullptr;
+    if (emit_check_args(__func__, ptr_msg, camera_ids, N, tile_n_bits, means2d_stride, tile_width, tile_height)) return 1;
     GS_CHECK_ARG(n_elems < (1u << 31), "n_elems must be < 2^31");
-    const dim3 grid(gs_div_up(n_elems, EMIT_SCAN_TILE));
-    if (mode == 2)
-        hipLaunchKernelGGL(isect_emit_scan_kernel<2>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, n_elems, N, perm, n_valid, camera_ids,
-                           means2d, means2d_stride, radii, depths, tiles_per_gauss, group_sums, group_prefix, (float)tile_size, (int32_t)tile_width,
-                           (int32_t)tile_height, tile_n_bits, (int64_t *)nullptr, keys32, (int32_t *)nullptr, pos_bits);
-    else if (compact)
-        hipLaunchKernelGGL(isect_emit_scan_kernel<1>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, n_elems, N, perm, n_valid, camera_ids,
-                           means2d, means2d_stride, radii, depths, tiles_per_gauss, group_sums, group_prefix, (float)tile_size, (int32_t)tile_width,
-                           (int32_t)tile_height, tile_n_bits, (int64_t *)nullptr, keys32, flatten_ids, 0u);
-    else
-        hipLaunchKernelGGL(isect_emit_scan_kernel<0>, grid, dim3(GS_BLOCK), 0, (hipStream_t)stream, n_elems, N, perm, n_valid, camera_ids,
-                           means2d, means2d_stride, radii, depths, tiles_per_gauss, group_sums, group_prefix, (float)tile_size, (int32_t)tile_width,
-                           (int32_t)tile_height, tile_n_bits, isect_ids, (uint32_t *)nullptr, flatten_ids, 0u);
+    // (a mode's kernel never touches the outputs of the other modes)
+    const auto kernel = mode == 2 ? isect_emit_scan_kernel<2> : mode == 1 ? isect_emit_scan_kernel<1> : isect_emit_scan_kernel<0>;
+    hipLaunchKernelGGL(kernel, dim3(gs_div_up(n_elems, EMIT_SCAN_TILE)), dim3(GS_BLOCK), 0, (hipStream_t)stream, n_elems, N, perm, n_valid,
+                       camera_ids, means2d, means2d_stride, radii, depths, tiles_per_gauss, group_sums, group_prefix, (float)tile_size,
+                       (int32_t)tile_width, (int32_t)tile_height, tile_n_bits, isect_ids, keys32, flatten_ids, pos_bits);
     GS_CHECK_LAUNCH();
     return 0;
 }
@@ -1118,20 +1070,15 @@ RowBinLayout rowbin_layout(uint64_t n_isects, uint32_t n_kept, uint32_t rows, ui
     RowBinLayout L;
     L.n_blocks = gs_div_up(n_kept, RB_POS_ITEMS);
     L.max_chunks = (uint32_t)(n_isects / RB_ITEMS) + rows;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o += (bytes + 255) & ~(size_t)255;
-        return r;
-    };
-    take((size_t)n_isects * sizeof(uint2)); // the row entries: at most one per pair (where the word arrays of the other routes live)
-    L.off_row_cnt = take((size_t)rows * L.n_blocks * sizeof(uint32_t));
-    L.off_row_pairs = take((size_t)rows * L.n_blocks * sizeof(uint32_t));
-    L.off_row_total = take((size_t)2 * rows * sizeof(uint32_t)); // entries | pairs of every row
-    L.off_tables = take((size_t)3 * (rows + 1) * sizeof(uint32_t)); // row_start | chunk_first | pairs_before
-    L.off_items = take((size_t)n_kept * sizeof(uint2));         // stage 1's item per position: rows | columns
-    L.off_col_cnt = take((size_t)L.max_chunks * tw * sizeof(uint32_t));
-    L.total = o;
+    Carve cv;
+    cv.take((size_t)n_isects * sizeof(uint2)); // the row entries: at most one per pair (where the word arrays of the other routes live)
+    L.off_row_cnt = cv.take((size_t)rows * L.n_blocks * sizeof(uint32_t));
+    L.off_row_pairs = cv.take((size_t)rows * L.n_blocks * sizeof(uint32_t));
+    L.off_row_total = cv.take((size_t)2 * rows * sizeof(uint32_t)); // entries | pairs of every row
+    L.off_tables = cv.take((size_t)3 * (rows + 1) * sizeof(uint32_t)); // row_start | chunk_first | pairs_before
+    L.off_items = cv.take((size_t)n_kept * sizeof(uint2));         // stage 1's item per position: rows | columns
+    L.off_col_cnt = cv.take((size_t)L.max_chunks * tw * sizeof(uint32_t));
+    L.total = cv.total;
     return L;
 }
 std::atomic<int32_t> g_row_binning{1}, g_last_route{GS_ISECT_ROUTE_NONE};

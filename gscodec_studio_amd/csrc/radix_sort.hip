@@ -24,6 +24,7 @@
 // launch, grouped so that no look-back chain forms -- was built and measured in round 2: correct, but 68 us per 4 M-pair
 // pass against 45 us for the three launches; in-launch hand-offs cost more than kernel boundaries here.)
 #include "gs_common.h"
+#include "scan_dev.h"
 
 namespace {
 
@@ -140,30 +141,15 @@ __global__ void __launch_bounds__(GS_BLOCK) sort_scan_kernel(
     uint32_t n_blocks, uint32_t *__restrict__ hist, uint32_t *__restrict__ totals, uint32_t *__restrict__ zero_side, uint32_t n_side) {
     __shared__ uint32_t s_wave[SORT_WAVES];
     uint32_t *row = hist + (size_t)blockIdx.x * n_blocks;
-    uint32_t lane = threadIdx.x % GS_WAVE, wave = threadIdx.x / GS_WAVE;
     uint32_t carry = 0;
     if (zero_side != nullptr)
         for (uint32_t i = blockIdx.x * GS_BLOCK + threadIdx.x; i < n_side; i += RADIX * GS_BLOCK) zero_side[i] = 0u;
     for (uint32_t base = 0; base < n_blocks; base += GS_BLOCK) {
         uint32_t i = base + threadIdx.x;
         uint32_t v = i < n_blocks ? row[i] : 0;
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            uint32_t o = __shfl_up(inc, off, 64);
-            if (lane >= (uint32_t)off) inc += o;
-        }
-        if (lane == GS_WAVE - 1) s_wave[wave] = inc;
-        __syncthreads();
-        uint32_t wbase = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < SORT_WAVES; ++w) {
-            if ((uint32_t)w < wave) wbase += s_wave[w];
-            total += s_wave[w];
-        }
-        if (i < n_blocks) row[i] = carry + wbase + inc - v;
-        carry += total;
-        __syncthreads();
+        const BlockScan<uint32_t> sc = block_scan<SORT_WAVES>(v, s_wave);
+        if (i < n_blocks) row[i] = carry + sc.exc;
+        carry += sc.total;
     }
     if (threadIdx.x == 0) totals[blockIdx.x] = carry;
 }
@@ -269,24 +255,8 @@ __global__ void __launch_bounds__(GS_BLOCK) sort_scatter_kernel(
             s_cnt[w][tid] = run;
             run += c;
         }
-        auto block_excl_scan = [&](uint32_t t) { // exclusive scan over the 256 threads (digits)
-            uint32_t inc = t;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                uint32_t o = __shfl_up(inc, off, 64);
-                if (lane >= (uint32_t)off) inc += o;
-            }
-            __syncthreads(); // s_scan may still be read by the previous call
-            if (lane == GS_WAVE - 1) s_scan[wave] = inc;
-            __syncthreads();
-            uint32_t wbase = 0;
-#pragma unroll
-            for (int w = 0; w < SORT_WAVES; ++w)
-                if ((uint32_t)w < wave) wbase += s_scan[w];
-            return wbase + inc - t;
-        };
-        const uint32_t gbase = block_excl_scan(my_total) + my_hist;
-        const uint32_t lbase = block_excl_scan(run);
+        const uint32_t gbase = block_scan<SORT_WAVES>(my_total, s_scan).exc + my_hist; // (exclusive scans over the 256 digits)
+        const uint32_t lbase = block_scan<SORT_WAVES>(run, s_scan).exc;
         s_lbase[tid] = lbase;
         if (tid == RADIX - 1) s_count = lbase + run; // keys of this block that take part
         s_gofs[tid] = gbase - lbase; // (unsigned wrap-around is fine: only s_gofs[dg] + j is used)
@@ -319,17 +289,9 @@ __global__ void __launch_bounds__(GS_BLOCK) sort_scatter_kernel(
                 // the word's low bits are the emission position = the depth rank: flatten id and depth through perm
                 const uint32_t w32 = (uint32_t)kk;
                 const uint32_t at = w32 & ((1u << ep.pos_bits) - 1u);
-                int32_t v;
-                int64_t db;
-                if (ep.sorted_keys != nullptr) { // (uniform) depths of visible splats are positive: their bits ARE the key's high half
-                    const uint64_t sk = ep.sorted_keys[at];
-                    v = (int32_t)(uint32_t)sk;
-                    db = (int64_t)(sk >> 32);
-                } else {
-                    v = ep.perm[at];
-                    db = (int64_t)__float_as_int(ep.depths[v]);
-                }
-                ep.isect_ids[pos[k]] = (int64_t)((uint64_t)(w32 >> ep.pos_bits) << 32) | db;
+                int32_t v, db;
+                pair_id_of(at, ep.sorted_keys, ep.perm, ep.depths, &v, &db);
+                ep.isect_ids[pos[k]] = (int64_t)((uint64_t)(w32 >> ep.pos_bits) << 32) | (int64_t)db;
                 ep.flatten_ids[pos[k]] = v;
             } else if (FINAL_ISECT) kept_key[FINAL_ISECT ? k : 0] = kk;
             else keys_out[pos[k]] = kk;
@@ -358,54 +320,84 @@ __global__ void __launch_bounds__(GS_BLOCK) sort_scatter_kernel(
                 vals_out[pos[k]] = v;
             }
         }
-        // side sums: consecutive lanes hold consecutive output positions inside a digit run, i.e. mostly the same group:
-        // segmented wave sums, one atomic per (wave, run of equal groups) instead of one per key on a shared counter
+        // side sums over the groups of output positions (whole waves take part)
         if (!FINAL_ISECT && side.side_sums != nullptr) { // (block-uniform)
             const bool on = j < block_count;
-            const uint32_t grp = on ? (pos[k] >> side.side_shift) : 0xffffffffu;
-            uint32_t inc = on ? (uint32_t)side.side_vals[s_vals[j]] : 0u;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t o = __shfl_up(inc, off, 64);
-                if (lane >= (uint32_t)off) inc += o;
-            }
-            const uint32_t prevg = __shfl_up(grp, 1, 64);
-            const bool head = lane == 0u || grp != prevg;
-            const unsigned long long hm = __ballot(head);
-            const unsigned long long above = lane == 63u ? 0ull : (hm >> (lane + 1u));
-            const uint32_t last = above ? lane + (uint32_t)__builtin_ctzll(above) : 63u; // last lane of my run
-            const uint32_t upto = __shfl(inc, (int)last, 64);
-            const uint32_t before = __shfl_up(inc, 1, 64);
-            if (head && on) atomicAdd(&side.side_sums[grp], upto - (lane == 0u ? 0u : before));
+            segmented_side_add(side.side_sums, on, pos[k] >> side.side_shift, on ? (uint32_t)side.side_vals[s_vals[j]] : 0u);
         }
     }
 }
 
+// temp layout of a sort of n keys of key_bytes each: keys[n] | vals[n] | hist[RADIX][blocks] | totals[RADIX]
 struct SortLayout {
     uint32_t n_blocks;
     size_t off_keys, off_vals, off_hist, off_totals, total;
 };
 
-SortLayout sort_layout(uint64_t n) {
+SortLayout sort_layout(uint64_t n, size_t key_bytes) {
     SortLayout L;
     L.n_blocks = gs_div_up(n, sort_tile(sort_rounds_for(n)));
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o += (bytes + 255) & ~(size_t)255;
-        return r;
-    };
-    L.off_keys = take(n * sizeof(uint64_t));
-    L.off_vals = take(n * sizeof(int32_t));
-    L.off_hist = take((size_t)RADIX * sort_hist_rows(n, L.n_blocks) * sizeof(uint32_t));
-    L.off_totals = take(RADIX * sizeof(uint32_t));
-    L.total = o;
+    Carve cv;
+    L.off_keys = cv.take(n * key_bytes);
+    L.off_vals = cv.take(n * sizeof(int32_t));
+    L.off_hist = cv.take((size_t)RADIX * sort_hist_rows(n, L.n_blocks) * sizeof(uint32_t));
+    L.off_totals = cv.take(RADIX * sizeof(uint32_t));
+    L.total = cv.total;
     return L;
+}
+
+// The passes of an LSD sort on key bits [begin_bit, begin_bit + n_bits): 8 bits a pass, and the FIRST pass takes the remainder
+// (e.g. 14 bits -> 6 + 8): it meets the data in its least ordered state, and fewer bins there mean longer runs per bin and block.
+// (Remainder LAST, for longer store runs in the pass that writes 12 bytes per pair, measured 34.6 + 28.8 us against
+// 36.0 + 25.0 us for the binning's pairs: no.  Measured again for the packed words: 0.7274 / 0.7475 / 0.7414 against
+// 0.7276 / 0.7207 / 0.7207 ms/step: no.)
+struct PassPlan {
+    int begin_bit, passes, first_bits;
+    bool signed_top; // the last digit holds the sign bit of the int64 the keys stand for: CUB orders those as SIGNED values
+    PassPlan(int begin, int n_bits, bool top)
+        : begin_bit(begin), passes((n_bits + RADIX_BITS - 1) / RADIX_BITS), first_bits(n_bits - (passes - 1) * RADIX_BITS), signed_top(top) {}
+    bool last(int p) const { return p == passes - 1; }
+    DigitSpec digit_spec(int p) const {
+        const int bits = (p == 0) ? first_bits : RADIX_BITS;
+        DigitSpec d;
+        d.shift = (uint32_t)(begin_bit + (p == 0 ? 0 : first_bits + (p - 1) * RADIX_BITS));
+        d.mask = (1u << bits) - 1u;
+        d.flip = (signed_top && last(p)) ? (1u << (bits - 1)) : 0u;
+        d.drop = d.drop_hi = 0u;
+        d.split = nullptr;
+        return d;
+    }
+};
+
+// What a pass works in, besides its keys: the histogram's place, and what the scatter does on the side.
+struct PassBuffers {
+    uint32_t n_blocks, *hist, *totals;
+    const uint32_t *n_dev;  // or NULL: the element count when it lives on the device
+    uint32_t *n_kept_out;   // or NULL: see sort_scatter_kernel
+    ScatterSide side;
+    uint32_t *zero_side;    // or NULL: n_side side sums the scan launch zeroes -- the scatter's, or those of a kernel behind it
+    uint32_t n_side;
+};
+
+// One pass: histogram (unless its producer left it in place: hist_ready), scan, scatter -- with the 1024-key blocks (small) or the
+// 4096-key ones.
+template <typename KeyT, bool FINAL_ISECT, bool BUCKET = false, bool KEYS_ONLY = false>
+void launch_pass(bool small, bool hist_ready, uint64_t n, const KeyT *src_k, const int32_t *src_v, KeyT *dst_k, int32_t *dst_v,
+                 const DigitSpec &d, const PassBuffers &b, const IsectEpilogue &ep, hipStream_t st) {
+    constexpr int BIG = BUCKET ? SORT_ROUNDS_SMALL : SORT_ROUNDS_BIG; // (the bucketed partition pass exists for the small blocks only)
+    const dim3 grid(b.n_blocks), block(GS_BLOCK);
+    const auto hist_kernel = small ? sort_hist_kernel<KeyT, SORT_ROUNDS_SMALL> : sort_hist_kernel<KeyT, BIG>;
+    const auto scatter_kernel = small ? sort_scatter_kernel<KeyT, SORT_ROUNDS_SMALL, FINAL_ISECT, BUCKET, KEYS_ONLY>
+                                      : sort_scatter_kernel<KeyT, BIG, FINAL_ISECT, BUCKET, KEYS_ONLY>;
+    if (!hist_ready) hipLaunchKernelGGL(hist_kernel, grid, block, 0, st, n, b.n_dev, src_k, d, b.n_blocks, b.hist);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(RADIX), block, 0, st, b.n_blocks, b.hist, b.totals, b.zero_side, b.n_side);
+    hipLaunchKernelGGL(scatter_kernel, grid, block, 0, st, n, b.n_dev, src_k, src_v, dst_k, dst_v, d, b.n_blocks, b.hist, b.totals, b.n_kept_out,
+                       ep, b.side);
 }
 
 } // namespace
 
-extern "C" size_t gs_sort_temp_bytes(uint64_t n) { return sort_layout(n).total; }
+extern "C" size_t gs_sort_temp_bytes(uint64_t n) { return sort_layout(n, sizeof(uint64_t)).total; }
 
 // Where the FIRST pass of a sort of n 64-bit keys expects its per-block digit histogram inside `temp` ([256][n_blocks],
 // blocks of 1024 consecutive keys), for a producer of the keys that can count the digits while it writes them
@@ -414,7 +406,7 @@ extern "C" int32_t gs_sort_first_hist_applicable(uint64_t n) { return (n > 0 && 
 
 uint32_t *sort_first_hist_slot(uint64_t n, void *temp, size_t temp_bytes, uint32_t *n_blocks) {
     if (n == 0 || temp == nullptr || sort_rounds_for(n) != SORT_ROUNDS_SMALL) return nullptr;
-    const SortLayout L = sort_layout(n);
+    const SortLayout L = sort_layout(n, sizeof(uint64_t));
     if (temp_bytes < L.total) return nullptr;
     *n_blocks = L.n_blocks;
     return (uint32_t *)((char *)temp + L.off_hist);
@@ -425,8 +417,9 @@ static int32_t sort_impl(uint64_t n, const int64_t *keys_in, const int32_t *vals
                          size_t temp_bytes, hipStream_t st, const char *who, bool first_hist_ready = false,
                          const int32_t *side_vals = nullptr, uint32_t *side_sums = nullptr, uint32_t side_shift = 0) {
     if (n == 0) return 0;
-    int passes = (end_bit - begin_bit + RADIX_BITS - 1) / RADIX_BITS;
-    if (passes == 0) {
+    // int64 keys: when the range includes bit 63 CUB orders them as signed values
+    const PassPlan plan(begin_bit, end_bit - begin_bit, end_bit == 64);
+    if (plan.passes == 0) {
         if (drop) {
             gs_set_error("%s: dropping keys needs at least one sorted bit", who);
             return 1;
@@ -435,7 +428,7 @@ static int32_t sort_impl(uint64_t n, const int64_t *keys_in, const int32_t *vals
         (void)hipMemcpyAsync(vals_out, vals_in, n * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
         return 0;
     }
-    SortLayout L = sort_layout(n);
+    const SortLayout L = sort_layout(n, sizeof(uint64_t));
     if (temp == nullptr || temp_bytes < L.total) {
         gs_set_error("%s: temp too small (%zu < %zu)", who, temp_bytes, L.total);
         return 1;
@@ -443,55 +436,29 @@ static int32_t sort_impl(uint64_t n, const int64_t *keys_in, const int32_t *vals
     char *tp = (char *)temp;
     uint64_t *tkeys = (uint64_t *)(tp + L.off_keys);
     int32_t *tvals = (int32_t *)(tp + L.off_vals);
-    uint32_t *hist = (uint32_t *)(tp + L.off_hist);
-    uint32_t *totals = (uint32_t *)(tp + L.off_totals);
-    const uint32_t n_side = side_sums != nullptr ? (uint32_t)((n + (1ull << side_shift) - 1) >> side_shift) : 0u;
+    PassBuffers b = {L.n_blocks, (uint32_t *)(tp + L.off_hist), (uint32_t *)(tp + L.off_totals), nullptr, nullptr, {nullptr, nullptr, 0u}, nullptr, 0u};
+    const bool small = sort_rounds_for(n) == SORT_ROUNDS_SMALL;
 
     // ping-pong between {temp, out}; the first destination is chosen so the last pass
     // lands in *_out without ever writing the inputs.
     const uint64_t *src_k = (const uint64_t *)keys_in;
     const int32_t *src_v = vals_in;
-    bool to_out = (passes % 2) == 1;
-    // the FIRST pass takes the remainder bits (e.g. 14 bits -> 6 + 8): it meets the data in its least
-    // ordered state, and fewer bins there mean longer runs per bin and block
-    const int first_bits = (end_bit - begin_bit) - (passes - 1) * RADIX_BITS;
-    int shift = begin_bit;
-    const uint32_t *n_dev = nullptr; // after a dropping first pass the element count lives on the device
-    const bool small = sort_rounds_for(n) == SORT_ROUNDS_SMALL;
-    auto digit_spec = [&](int p, int at_shift) {
-        DigitSpec d;
-        d.shift = (uint32_t)at_shift;
-        const int bits = (p == 0) ? first_bits : RADIX_BITS;
-        d.mask = (1u << bits) - 1u;
-        // int64 keys: when the range includes bit 63 CUB orders them as signed values
-        d.flip = (end_bit == 64 && p == passes - 1) ? (1u << (bits - 1)) : 0u;
+    bool to_out = (plan.passes % 2) == 1;
+    for (int p = 0; p < plan.passes; ++p) {
+        DigitSpec d = plan.digit_spec(p);
         d.drop = (drop && p == 0) ? 1u : 0u;
         d.drop_hi = drop_hi;
-        d.split = nullptr;
-        return d;
-    };
-    for (int p = 0; p < passes; ++p) {
-        const DigitSpec d = digit_spec(p, shift);
-        shift += (p == 0) ? first_bits : RADIX_BITS;
-        const bool last = p == passes - 1;
         uint64_t *dst_k = to_out ? (uint64_t *)keys_out : tkeys;
         int32_t *dst_v = to_out ? vals_out : tvals;
-        if (p == 0 && first_hist_ready && small) {
-            // the producer of the keys counted this pass's digits already (see sort_first_hist_slot)
-        } else if (small)
-            hipLaunchKernelGGL((sort_hist_kernel<uint64_t, SORT_ROUNDS_SMALL>), dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n, n_dev, src_k, d, L.n_blocks, hist);
-        else
-            hipLaunchKernelGGL((sort_hist_kernel<uint64_t, SORT_ROUNDS_BIG>), dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n, n_dev, src_k, d, L.n_blocks, hist);
-        ScatterSide side = {nullptr, nullptr, 0u};
-        if (last && side_sums != nullptr) side = {side_vals, side_sums, side_shift};
-        hipLaunchKernelGGL(sort_scan_kernel, dim3(RADIX), dim3(GS_BLOCK), 0, st, L.n_blocks, hist, totals, side.side_sums, n_side);
-        if (small)
-            hipLaunchKernelGGL((sort_scatter_kernel<uint64_t, SORT_ROUNDS_SMALL, false>), dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n, n_dev, src_k, src_v,
-                               dst_k, dst_v, d, L.n_blocks, hist, totals, (drop && p == 0) ? n_valid_out : nullptr, IsectEpilogue{}, side);
-        else
-            hipLaunchKernelGGL((sort_scatter_kernel<uint64_t, SORT_ROUNDS_BIG, false>), dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n, n_dev, src_k, src_v,
-                               dst_k, dst_v, d, L.n_blocks, hist, totals, (drop && p == 0) ? n_valid_out : nullptr, IsectEpilogue{}, side);
-        if (drop && p == 0) n_dev = n_valid_out;
+        b.n_kept_out = (drop && p == 0) ? n_valid_out : nullptr;
+        if (plan.last(p) && side_sums != nullptr) {
+            b.side = {side_vals, side_sums, side_shift};
+            b.zero_side = side_sums;
+            b.n_side = (uint32_t)((n + (1ull << side_shift) - 1) >> side_shift);
+        }
+        // (first_hist_ready: the producer of the keys counted the first pass's digits already, see sort_first_hist_slot)
+        launch_pass<uint64_t, false>(small, p == 0 && first_hist_ready && small, n, src_k, src_v, dst_k, dst_v, d, b, IsectEpilogue{}, st);
+        if (drop && p == 0) b.n_dev = n_valid_out; // after a dropping first pass the element count lives on the device
         src_k = dst_k;
         src_v = dst_v;
         to_out = !to_out;
@@ -533,63 +500,40 @@ extern "C" int32_t gs_sort_pairs_u64_i32_drop(
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Sort of the binning's compact (32-bit (camera, tile) key, flatten id) pairs; the last pass writes the reference's outputs.
+// Sorts of the binning's 32-bit pairs; the last pass writes the reference's outputs (IsectEpilogue).
 // temp layout: keys32[n] | vals[n] | hist[RADIX][n_blocks] | totals[RADIX]
-namespace {
+extern "C" size_t gs_sort_isect_temp_bytes(uint64_t n) { return sort_layout(n, sizeof(uint32_t)).total; }
 
-struct Sort32Layout {
-    uint32_t n_blocks;
-    size_t off_keys, off_vals, off_hist, off_totals, total;
-};
-
-Sort32Layout sort32_layout(uint64_t n) {
-    Sort32Layout L;
-    L.n_blocks = gs_div_up(n, sort_tile(sort_rounds_for(n)));
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o += (bytes + 255) & ~(size_t)255;
-        return r;
-    };
-    L.off_keys = take(n * sizeof(uint32_t));
-    L.off_vals = take(n * sizeof(int32_t));
-    L.off_hist = take((size_t)RADIX * sort_hist_rows(n, L.n_blocks) * sizeof(uint32_t));
-    L.off_totals = take(RADIX * sizeof(uint32_t));
-    L.total = o;
-    return L;
+// The body of both: a stable sort on the bits [begin_bit, begin_bit + key_bits) of keys, vals riding along unless KEYS_ONLY.
+// Ping-pong between the caller's arrays (destroyed) and the temp pair.
+template <bool KEYS_ONLY>
+static int32_t sort_isect_impl(const char *who, uint64_t n, uint32_t *keys, int32_t *vals, int begin_bit, int32_t key_bits,
+                               const IsectEpilogue &ep, void *temp, size_t temp_bytes, hipStream_t st) {
+    const SortLayout L = sort_layout(n, sizeof(uint32_t));
+    if (temp == nullptr || temp_bytes < L.total) {
+        gs_set_error("%s: temp too small (%zu < %zu)", who, temp_bytes, L.total);
+        return 1;
+    }
+    char *tp = (char *)temp;
+    uint32_t *tkeys = (uint32_t *)(tp + L.off_keys);
+    int32_t *tvals = KEYS_ONLY ? nullptr : (int32_t *)(tp + L.off_vals);
+    const PassBuffers b = {L.n_blocks, (uint32_t *)(tp + L.off_hist), (uint32_t *)(tp + L.off_totals), nullptr, nullptr, {nullptr, nullptr, 0u}, nullptr, 0u};
+    // with all 32 key bits in use the id's bit 63 is set for the upper half of the cameras: the reference sorts int64
+    // keys as SIGNED values (cub::DeviceRadixSort over [0, 64)), i.e. those come first
+    const PassPlan plan(begin_bit, key_bits, key_bits == 32);
+    const bool small = sort_rounds_for(n) == SORT_ROUNDS_SMALL;
+    const uint32_t *src_k = keys;
+    const int32_t *src_v = vals;
+    for (int p = 0; p < plan.passes; ++p) {
+        uint32_t *dst_k = (p % 2 == 0) ? tkeys : keys;
+        int32_t *dst_v = (p % 2 == 0) ? tvals : vals;
+        if (plan.last(p)) launch_pass<uint32_t, true, false, KEYS_ONLY>(small, false, n, src_k, src_v, dst_k, dst_v, plan.digit_spec(p), b, ep, st);
+        else launch_pass<uint32_t, false, false, KEYS_ONLY>(small, false, n, src_k, src_v, dst_k, dst_v, plan.digit_spec(p), b, ep, st);
+        src_k = dst_k;
+        src_v = dst_v;
+    }
+    return 0;
 }
-
-template <int ROUNDS>
-void launch_pass32(uint64_t n, const uint32_t *src_k, const int32_t *src_v, uint32_t *dst_k, int32_t *dst_v, DigitSpec d,
-                   const Sort32Layout &L, uint32_t *hist, uint32_t *totals, bool final, const IsectEpilogue &ep, hipStream_t st) {
-    hipLaunchKernelGGL((sort_hist_kernel<uint32_t, ROUNDS>), dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n, (const uint32_t *)nullptr, src_k, d, L.n_blocks, hist);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(RADIX), dim3(GS_BLOCK), 0, st, L.n_blocks, hist, totals, (uint32_t *)nullptr, 0u);
-    const ScatterSide none = {nullptr, nullptr, 0u};
-    if (final)
-        hipLaunchKernelGGL((sort_scatter_kernel<uint32_t, ROUNDS, true>), dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n, (const uint32_t *)nullptr, src_k, src_v,
-                           dst_k, dst_v, d, L.n_blocks, hist, totals, (uint32_t *)nullptr, ep, none);
-    else
-        hipLaunchKernelGGL((sort_scatter_kernel<uint32_t, ROUNDS, false>), dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n, (const uint32_t *)nullptr, src_k, src_v,
-                           dst_k, dst_v, d, L.n_blocks, hist, totals, (uint32_t *)nullptr, ep, none);
-}
-
-template <int ROUNDS>
-void launch_pass32_keys(uint64_t n, const uint32_t *src_k, uint32_t *dst_k, DigitSpec d, const Sort32Layout &L, uint32_t *hist,
-                        uint32_t *totals, bool final, const IsectEpilogue &ep, hipStream_t st) {
-    hipLaunchKernelGGL((sort_hist_kernel<uint32_t, ROUNDS>), dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n, (const uint32_t *)nullptr, src_k, d, L.n_blocks, hist);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(RADIX), dim3(GS_BLOCK), 0, st, L.n_blocks, hist, totals, (uint32_t *)nullptr, 0u);
-    const ScatterSide none = {nullptr, nullptr, 0u};
-    if (final)
-        hipLaunchKernelGGL((sort_scatter_kernel<uint32_t, ROUNDS, true, false, true>), dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n, (const uint32_t *)nullptr,
-                           src_k, (const int32_t *)nullptr, dst_k, (int32_t *)nullptr, d, L.n_blocks, hist, totals, (uint32_t *)nullptr, ep, none);
-    else
-        hipLaunchKernelGGL((sort_scatter_kernel<uint32_t, ROUNDS, false, false, true>), dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n, (const uint32_t *)nullptr,
-                           src_k, (const int32_t *)nullptr, dst_k, (int32_t *)nullptr, d, L.n_blocks, hist, totals, (uint32_t *)nullptr, ep, none);
-}
-
-} // namespace
-
-extern "C" size_t gs_sort_isect_temp_bytes(uint64_t n) { return sort32_layout(n).total; }
 
 // Packed pairs: one 32-bit word per pair, key << pos_bits | emission position.  The positions are the depth ranks, so a stable
 // sort on the key bits [pos_bits, pos_bits + key_bits) is all it takes, and nothing but the words moves; the last pass writes
@@ -601,86 +545,22 @@ extern "C" int32_t gs_sort_isect_packed(uint64_t n, uint32_t *words, const int32
     GS_CHECK_ARG(words && ((perm && depths) || sorted_keys) && isect_ids && flatten_ids, "null pointer");
     GS_CHECK_ARG(key_bits >= 1 && key_bits <= 31 && (uint32_t)key_bits + pos_bits <= 32, "key_bits (<= 31) + pos_bits must fit 32 bits");
     GS_CHECK_ARG(n < (1ull << 32), "n must be < 2^32");
-    const Sort32Layout L = sort32_layout(n);
-    if (temp == nullptr || temp_bytes < L.total) {
-        gs_set_error("gs_sort_isect_packed: temp too small (%zu < %zu)", temp_bytes, L.total);
-        return 1;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    char *tp = (char *)temp;
-    uint32_t *tkeys = (uint32_t *)(tp + L.off_keys);
-    uint32_t *hist = (uint32_t *)(tp + L.off_hist), *totals = (uint32_t *)(tp + L.off_totals);
-    const int passes = (key_bits + RADIX_BITS - 1) / RADIX_BITS;
-    const int first_bits = key_bits - (passes - 1) * RADIX_BITS;
+    // (key_bits < 32 here: the id's sign bit is never set)
     const IsectEpilogue ep = {depths, isect_ids, flatten_ids, perm, pos_bits, (const uint64_t *)sorted_keys};
-    const bool small = sort_rounds_for(n) == SORT_ROUNDS_SMALL;
-    const uint32_t *src_k = words;
-    int shift = (int)pos_bits;
-    for (int p = 0; p < passes; ++p) {
-        DigitSpec d;
-        const bool final = p == passes - 1;
-        // (remainder bits FIRST, as for the pairs; remainder last -- longer store runs in the pass that writes 12 bytes per pair --
-        // was measured again for the packed words: 0.7274 / 0.7475 / 0.7414 against 0.7276 / 0.7207 / 0.7207 ms/step: no)
-        const int bits = (p == 0) ? first_bits : RADIX_BITS;
-        d.shift = (uint32_t)shift;
-        shift += bits;
-        d.mask = (1u << bits) - 1u;
-        d.drop = d.drop_hi = 0u;
-        d.split = nullptr;
-        d.flip = 0u; // (key_bits < 32 here: the id's sign bit is never set)
-        uint32_t *dst_k = (p % 2 == 0) ? tkeys : words;
-        if (small) launch_pass32_keys<SORT_ROUNDS_SMALL>(n, src_k, dst_k, d, L, hist, totals, final, ep, st);
-        else launch_pass32_keys<SORT_ROUNDS_BIG>(n, src_k, dst_k, d, L, hist, totals, final, ep, st);
-        src_k = dst_k;
-    }
+    if (int32_t rc = sort_isect_impl<true>(__func__, n, words, nullptr, (int)pos_bits, key_bits, ep, temp, temp_bytes, (hipStream_t)stream)) return rc;
     GS_CHECK_LAUNCH();
     return 0;
 }
 
+// Compact pairs: (32-bit (camera, tile) key, flatten id); the last pass gathers the depth bits of the ids.
 extern "C" int32_t gs_sort_isect_pairs(uint64_t n, uint32_t *keys32, int32_t *vals, const float *depths, int32_t key_bits,
                                        int64_t *isect_ids, int32_t *flatten_ids, void *temp, size_t temp_bytes, gs_stream_t stream) {
     if (n == 0) return 0;
     GS_CHECK_ARG(keys32 && vals && depths && isect_ids && flatten_ids, "null pointer");
     GS_CHECK_ARG(key_bits >= 1 && key_bits <= 32, "key_bits must be in [1, 32]");
     GS_CHECK_ARG(n < (1ull << 32), "n must be < 2^32");
-    const Sort32Layout L = sort32_layout(n);
-    if (temp == nullptr || temp_bytes < L.total) {
-        gs_set_error("gs_sort_isect_pairs: temp too small (%zu < %zu)", temp_bytes, L.total);
-        return 1;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    char *tp = (char *)temp;
-    uint32_t *tkeys = (uint32_t *)(tp + L.off_keys);
-    int32_t *tvals = (int32_t *)(tp + L.off_vals);
-    uint32_t *hist = (uint32_t *)(tp + L.off_hist), *totals = (uint32_t *)(tp + L.off_totals);
-    const int passes = (key_bits + RADIX_BITS - 1) / RADIX_BITS;
-    // the first pass takes the remainder (14 bits -> 6 + 8).  (Remainder LAST, for longer store runs in the pass that
-    // writes 12 bytes per pair, measured 34.6 + 28.8 us against 36.0 + 25.0 us: no.)
-    const int first_bits = key_bits - (passes - 1) * RADIX_BITS;
     const IsectEpilogue ep = {depths, isect_ids, flatten_ids, nullptr, 0u, nullptr};
-    const bool small = sort_rounds_for(n) == SORT_ROUNDS_SMALL;
-    const uint32_t *src_k = keys32;
-    const int32_t *src_v = vals;
-    int shift = 0;
-    for (int p = 0; p < passes; ++p) { // ping-pong between the caller's pair (destroyed) and the temp pair
-        DigitSpec d;
-        const bool final = p == passes - 1;
-        const int bits = (p == 0) ? first_bits : RADIX_BITS;
-        d.shift = (uint32_t)shift;
-        shift += bits;
-        d.mask = (1u << bits) - 1u;
-        d.drop = d.drop_hi = 0u;
-        d.split = nullptr;
-        // with all 32 key bits in use the id's bit 63 is set for the upper half of the cameras: the reference sorts int64
-        // keys as SIGNED values (cub::DeviceRadixSort over [0, 64)), i.e. those come first
-        d.flip = (key_bits == 32 && final) ? (1u << (bits - 1)) : 0u;
-        uint32_t *dst_k = (p % 2 == 0) ? tkeys : keys32;
-        int32_t *dst_v = (p % 2 == 0) ? tvals : vals;
-        if (small) launch_pass32<SORT_ROUNDS_SMALL>(n, src_k, src_v, dst_k, dst_v, d, L, hist, totals, final, ep, st);
-        else launch_pass32<SORT_ROUNDS_BIG>(n, src_k, src_v, dst_k, dst_v, d, L, hist, totals, final, ep, st);
-        src_k = dst_k;
-        src_v = dst_v;
-    }
+    if (int32_t rc = sort_isect_impl<false>(__func__, n, keys32, vals, 0, key_bits, ep, temp, temp_bytes, (hipStream_t)stream)) return rc;
     GS_CHECK_LAUNCH();
     return 0;
 }
@@ -739,28 +619,6 @@ GS_DEV LdsSort lds_sort_carve(unsigned char *lds, uint32_t capacity) {
 }
 constexpr size_t lds_sort_bytes(uint32_t capacity) {
     return (size_t)capacity * (2 * sizeof(uint2) + 2) + PS_WAVES * RADIX * 4 + RADIX * 4 + (2 * PS_WAVES + 8) * 4 + 64;
-}
-
-// exclusive scan of one value per thread over the FIRST 256 threads of the workgroup (the digits); every thread calls it
-GS_DEV uint32_t ps_scan256(uint32_t t, uint32_t *s_scan, uint32_t *total) {
-    const uint32_t lane = threadIdx.x % GS_WAVE, wave = threadIdx.x / GS_WAVE;
-    uint32_t inc = wave < 4u ? t : 0u;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off) inc += o;
-    }
-    __syncthreads();
-    if (lane == GS_WAVE - 1 && wave < 4u) s_scan[wave] = inc;
-    __syncthreads();
-    uint32_t wbase = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        if ((uint32_t)w < wave) wbase += s_scan[w];
-        tot += s_scan[w];
-    }
-    if (total != nullptr) *total = tot;
-    return wbase + inc - t;
 }
 
 // Stable sort of the m pairs in L.a by their .x, in LDS; returns the buffer holding the result (L.a or L.b).
@@ -849,12 +707,7 @@ GS_DEV uint2 *lds_stable_sort(const LdsSort &L, uint32_t m, uint32_t max_bits = 
                 L.cnt[w][tid] = run;
                 run += c[w];
             }
-            inc = run;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t o = __shfl_up(inc, off, 64);
-                if (lane >= (uint32_t)off) inc += o;
-            }
+            inc = wave_inclusive_scan(run); // (the cross-wave part shares this pass's barriers)
             if (lane == GS_WAVE - 1) L.red[wave] = inc;
         }
         __syncthreads();
@@ -997,20 +850,7 @@ __global__ void __launch_bounds__(PS_THREADS) presort_split_kernel(uint64_t *__r
         tsum += s_hist[tid * CPT + i];
         c4[i] = tsum;
     }
-    uint32_t inc = tsum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off) inc += o;
-    }
-    __syncthreads();
-    if (lane == GS_WAVE - 1) L.red[wave] = inc;
-    __syncthreads();
-    uint32_t wbase = 0;
-#pragma unroll
-    for (int w = 0; w < PS_WAVES; ++w)
-        if ((uint32_t)w < wave) wbase += L.red[w];
-    const uint32_t excl = wbase + inc - tsum;
+    const uint32_t excl = block_scan<PS_WAVES>(tsum, L.red).exc;
 #pragma unroll
     for (uint32_t i = 0; i < CPT; ++i) s_hist[tid * CPT + i] = excl + c4[i];
     __syncthreads();
@@ -1032,25 +872,6 @@ __global__ void __launch_bounds__(PS_THREADS) presort_split_kernel(uint64_t *__r
     PS_STAMP(4);
 }
 
-// segmented wave sums of `inc` over runs of equal `grp` among consecutive lanes, one atomic per run (as in the scatter's side job)
-GS_DEV void ps_side_add(uint32_t *side_sums, bool on, uint32_t grp, uint32_t inc) {
-    const uint32_t lane = threadIdx.x % GS_WAVE;
-    if (!on) { grp = 0xffffffffu; inc = 0u; }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= (uint32_t)off) inc += o;
-    }
-    const uint32_t prevg = __shfl_up(grp, 1, 64);
-    const bool head = lane == 0u || grp != prevg;
-    const unsigned long long hm = __ballot(head);
-    const unsigned long long above = lane == 63u ? 0ull : (hm >> (lane + 1u));
-    const uint32_t last = above ? lane + (uint32_t)__builtin_ctzll(above) : 63u;
-    const uint32_t upto = __shfl(inc, (int)last, 64);
-    const uint32_t before = __shfl_up(inc, 1, 64);
-    if (head && on) atomicAdd(&side_sums[grp], upto - (lane == 0u ? 0u : before));
-}
-
 // 3. local sorts.  keys [*n_kept]: the partitioned keys (bucket order, stable); totals [256]: keys per bucket; alt [n]: scratch
 // for a range that does not fit LDS.  perm [*n_kept] out; side_sums[p >> side_shift] += side_vals[perm[p]].
 __global__ void __launch_bounds__(PS_THREADS) presort_local_kernel(const uint32_t *__restrict__ n_kept_p, const uint32_t *__restrict__ totals,
@@ -1066,7 +887,7 @@ __global__ void __launch_bounds__(PS_THREADS) presort_local_kernel(const uint32_
     // workgroup b finishes bucket b: 256 buckets, one workgroup per CU, all of them resident at once
     {
         const uint32_t tot = tid < GS_PRESORT_BUCKETS ? totals[tid] : 0u;
-        const uint32_t st = ps_scan256(tot, L.red, nullptr);
+        const uint32_t st = block_scan<4>(tot, L.red).exc; // (the 256 buckets: the first four waves)
         if (tid < GS_PRESORT_BUCKETS) {
             s_start[tid] = st;
             if (tid == GS_PRESORT_BUCKETS - 1) s_start[GS_PRESORT_BUCKETS] = st + tot;
@@ -1092,7 +913,7 @@ __global__ void __launch_bounds__(PS_THREADS) presort_local_kernel(const uint32_
             const uint32_t e = on ? sorted[j].y : 0u;
             if (on) perm[lo + j] = (int32_t)e;
             if (on && sorted_out != nullptr) sorted_out[lo + j] = ((uint64_t)sorted[j].x << 32) | (uint64_t)e;
-            if (side_sums != nullptr) ps_side_add(side_sums, on, (lo + j) >> side_shift, on ? (uint32_t)side_vals[e] : 0u);
+            if (side_sums != nullptr) segmented_side_add(side_sums, on, (lo + j) >> side_shift, on ? (uint32_t)side_vals[e] : 0u);
         }
         PS_STAMP(12);
         return;
@@ -1138,8 +959,7 @@ __global__ void __launch_bounds__(PS_THREADS) presort_local_kernel(const uint32_
         for (uint32_t j = tid; j < m; j += PS_THREADS) atomicAdd(&s_hist[(((uint32_t)(src[lo + j] >> 32) - kmin) >> shift) & 0xffu], 1u);
         __syncthreads();
         const uint32_t mine = tid < RADIX ? s_hist[tid] : 0u;
-        const uint32_t base0 = ps_scan256(mine, L.red, nullptr);
-        __syncthreads();
+        const uint32_t base0 = block_scan<4>(mine, L.red).exc;
         if (tid < RADIX) s_hist[tid] = base0; // running base of digit tid
         __syncthreads();
         for (uint32_t t0 = 0; t0 < m; t0 += PS_THREADS) {
@@ -1191,7 +1011,7 @@ __global__ void __launch_bounds__(PS_THREADS) presort_local_kernel(const uint32_
         const uint32_t e = (uint32_t)sk;
         if (on) perm[lo + j] = (int32_t)e;
         if (on && sorted_out != nullptr) sorted_out[lo + j] = sk;
-        if (side_sums != nullptr) ps_side_add(side_sums, on, (lo + j) >> side_shift, on ? (uint32_t)side_vals[e] : 0u);
+        if (side_sums != nullptr) segmented_side_add(side_sums, on, (lo + j) >> side_shift, on ? (uint32_t)side_vals[e] : 0u);
     }
 }
 
@@ -1230,7 +1050,7 @@ extern "C" int32_t gs_presort_buckets(uint64_t n, int64_t *keys_in, const int32_
     GS_CHECK_ARG(gs_presort_applicable(n), "gs_presort_applicable(n) is 0: use gs_sort_pairs_u64_i32_drop");
     GS_CHECK_ARG((side_vals == nullptr) == (side_sums == nullptr) && side_shift < 32, "side_vals and side_sums go together");
     GS_CHECK_ARG(lds_capacity <= PS_CAP, "lds_capacity exceeds gs_presort_capacity()");
-    const SortLayout L = sort_layout(n);
+    const SortLayout L = sort_layout(n, sizeof(uint64_t));
     // temp: the radix sort's layout (keys | vals | hist | totals: the histogram is where gs_isect_count_keys put it) + n more keys
     const size_t alt_off = (L.total + 255) & ~(size_t)255;
     GS_CHECK_ARG(temp != nullptr && temp_bytes >= alt_off + n * sizeof(uint64_t), "temp too small (gs_presort_temp_bytes)");
@@ -1243,10 +1063,9 @@ extern "C" int32_t gs_presort_buckets(uint64_t n, int64_t *keys_in, const int32_
     DigitSpec d;
     d.shift = 32; d.mask = 0xffu; d.flip = 0u; d.drop = 1u; d.drop_hi = 0x7fffffffu;
     d.split = (const uint64_t *)splitters;
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(RADIX), dim3(GS_BLOCK), 0, st, L.n_blocks, hist, totals, side_sums, n_side);
-    hipLaunchKernelGGL((sort_scatter_kernel<uint64_t, SORT_ROUNDS_SMALL, false, true, true>), dim3(L.n_blocks), dim3(GS_BLOCK), 0, st, n,
-                       (const uint32_t *)nullptr, (const uint64_t *)keys_in, (const int32_t *)nullptr, tkeys, (int32_t *)nullptr, d, L.n_blocks, hist,
-                       totals, n_kept, IsectEpilogue{}, ScatterSide{nullptr, nullptr, 0u});
+    // the partition pass: its histogram is in place; the scan zeroes the side sums the LOCAL sorts add up (not this scatter)
+    const PassBuffers b = {L.n_blocks, hist, totals, nullptr, n_kept, {nullptr, nullptr, 0u}, side_sums, n_side};
+    launch_pass<uint64_t, false, true, true>(true, true, n, (const uint64_t *)keys_in, nullptr, tkeys, nullptr, d, b, IsectEpilogue{}, st);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(presort_local_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)PS_LOCAL_LDS);
     GS_CHECK_ARG(e == hipSuccess, "cannot raise the dynamic LDS limit");
@@ -1256,4 +1075,4 @@ extern "C" int32_t gs_presort_buckets(uint64_t n, int64_t *keys_in, const int32_
     return 0;
 }
 
-extern "C" size_t gs_presort_temp_bytes(uint64_t n) { return ((sort_layout(n).total + 255) & ~(size_t)255) + n * sizeof(uint64_t); }
+extern "C" size_t gs_presort_temp_bytes(uint64_t n) { return ((sort_layout(n, sizeof(uint64_t)).total + 255) & ~(size_t)255) + n * sizeof(uint64_t); }

@@ -58,7 +58,7 @@ int main() {
     printf("events (ms): split %.4f  count %.4f  scan+scatter+local %.4f\n", t_split, t_count, t_bucket);
     // the slowest local-sort workgroup: the largest bucket
     {
-        const SortLayout L = sort_layout(n);
+        const SortLayout L = sort_layout(n, sizeof(uint64_t));
         std::vector<uint32_t> tot(256);
         hipMemcpy(tot.data(), (char *)temp + L.off_totals, 256 * 4, hipMemcpyDeviceToHost);
         unsigned int arg = (unsigned int)(std::max_element(tot.begin(), tot.end()) - tot.begin());
