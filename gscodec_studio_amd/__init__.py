@@ -6,7 +6,8 @@ Public surface (mirrors the reference's ``gsplat`` package for this path only):
   ``optimizers.{Adam, SelectiveAdam, step_all, visibility_mask}`` and ``losses.{fused_ssim, photometric_loss}`` and
   ``strategy.{Strategy, DefaultStrategy, MCMCStrategy, STG_Strategy, Modified_STG_Strategy}`` (``from gscodec_studio_amd.strategy import ...``, as in the reference) with
   ``relocation.compute_relocation``, and ``bilagrid.{BilateralGrid, slice, slice_image, total_variation_loss,
-  color_affine_transform}`` (``from gscodec_studio_amd.bilagrid import ...`` in place of ``from lib_bilagrid import ...``), and the 2D Gaussian splatting
+  color_affine_transform}`` (``from gscodec_studio_amd.bilagrid import ...`` in place of ``from lib_bilagrid import ...``) with the
+  evaluation's ``color_correct.color_correct`` (``from gscodec_studio_amd.color_correct import color_correct``), and the 2D Gaussian splatting
   renderer ``rasterization_2dgs`` with its operators ``fully_fused_projection_2dgs`` / ``rasterize_to_pixels_2dgs`` (``surfel.py``) and
   ``utils.{depth_to_points, depth_to_normal}``, and the spacetime trainer's colour decoder
   ``dynamic.{Sandwich, getcolormodel, decode_colors, trbfunction}`` (``from gscodec_studio_amd.dynamic import getcolormodel, trbfunction``

@@ -23,7 +23,8 @@ so its last bits can differ from run to run; every other result is bit-identical
 ``[0, num)`` are the caller's error: the kernels clamp them, they never read outside ``grids``.  Nothing here synchronises with
 the host.  Inputs the kernels do not cover raise ``ValueError``; there is no CPU path.
 
-Out of scope: ``color_correct`` (evaluation-time least squares), ``BilateralGridCP4D`` and ``slice4d``.
+Out of scope: ``BilateralGridCP4D`` and ``slice4d``.  ``color_correct`` (evaluation-time least squares) is in
+``gscodec_studio_amd.color_correct``.
 """
 from __future__ import annotations
 

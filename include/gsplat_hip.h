@@ -53,7 +53,8 @@ extern "C" {
  * PLY entries (gs_ply_unpack, gs_ply_pack, gs_ply_max_stride, gs_ply_max_columns, gs_ply_block_rows), and the hash-grid Gaussian entropy model's (gs_hashgrid_encode_fwd / _bwd,
  * gs_gaussian_bits_fwd / _bwd), and the Gaussian entropy coder's (gs_ans_pack_slots, gs_gauss_ans_slot_bytes,
  * gs_gauss_ans_encode_bytes, gs_gauss_ans_params, gs_gauss_ans_encode, gs_gauss_ans_decode), and the SparseAdam entries
- * (gs_sparse_adam_desc, gs_sparse_adam_multi, gs_sparse_adam_desc_layout). */
+ * (gs_sparse_adam_desc, gs_sparse_adam_multi, gs_sparse_adam_desc_layout), and the colour-matching entries
+ * (gs_color_correct_pass, gs_color_correct_solve, gs_color_correct_record_doubles, gs_color_correct_rcond_log2). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -1472,6 +1473,37 @@ int32_t gs_bilagrid_tv_fwd(const float *x, uint32_t N, uint32_t C, uint32_t L, u
                            uint64_t work_bytes, float *out, gs_stream_t stream);
 int32_t gs_bilagrid_tv_bwd(const float *x, uint32_t N, uint32_t C, uint32_t L, uint32_t H, uint32_t W, const float *grad,
                            float *v_x, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * B1c  The evaluation-time colour matching of the same file (examples/lib_bilagrid.py:56-126, color_correct): masked least squares
+ * of a quadratic colour warp, iterated.  No host synchronisation, no atomics: bit-identical from run to run.
+ * Pixels: G groups of P pixels of n = 1..3 channels (G P <= 2^31 - 1); every group is one least-squares problem per channel.
+ * Features of a pixel x, in double, K = n (n + 1) / 2 + n + 1 columns (3, 6, 10): x_c x_c' for c' >= c (c outer), then x, then 1.
+ * A record is the upper triangle of A^T A by rows (K (K + 1) / 2 doubles) followed by A^T b (K doubles):
+ * gs_color_correct_record_doubles(n) = 9, 27, 65 (0 for another n).  A warp is K n doubles, w[k n + c].
+ *
+ * gs_color_correct_pass, one pass over the pixels, does either or both of
+ *   apply       (warp != NULL; needs out): out = float(clip(A(x) w, 0, 1)), the product summed in double in column order;
+ *   accumulate  (partials != NULL): with y = out where applied and x otherwise, the rows of channel c are those with
+ *               lo <= z <= hi (compared in float) for z = x0[c], y[c] and ref[c]; they add A(y)^T A(y) and A(y)^T ref[c] to the
+ *               lane's record of channel c, which is reduced over the wave, then over the workgroup: ONE record per workgroup,
+ *               partials[((g n + c) blocks + b) record_doubles], every one written (zeros where a workgroup saw no row).
+ * x and x0 (the image the mask of the first iteration is taken from) are read at pixel strides x_stride and x0_stride
+ * (elements, >= n: columns 0..n-1 of a wider render work without a copy); ref [G P, n] and out [G P, n] are contiguous, and out
+ * must not overlap x.  blocks >= 1 workgroups per (group, channel) walk the pixels of a group in a grid-stride loop
+ * (blocks n G <= 2^31 - 1; blocks <= 65535).  warp: DEVICE [G, K n] doubles; partials: DEVICE, 8-byte aligned.
+ *
+ * gs_color_correct_solve: per (group, channel) sums the `blocks` records in a fixed order and solves the K x K normal equations
+ * in double through a symmetric eigen-decomposition (cyclic Jacobi): w = V diag(1 / lambda_i if lambda_i > 2^-L max lambda,
+ * else 0) V^T A^T b with L = gs_color_correct_rcond_log2() = 40, so a full-rank system gets the least-squares solution and a
+ * rank-deficient one (no row, a constant channel, fewer rows than columns) the minimum-norm one; a system with a non-finite sum
+ * gets w = 0.  The warp is always finite. */
+uint32_t gs_color_correct_rcond_log2(void);
+uint32_t gs_color_correct_record_doubles(uint32_t n);
+int32_t gs_color_correct_pass(const float *x, int64_t x_stride, const float *x0, int64_t x0_stride, const float *ref, uint32_t G,
+                              uint64_t P, uint32_t n, float lo, float hi, const double *warp, float *out, double *partials,
+                              uint32_t blocks, gs_stream_t stream);
+int32_t gs_color_correct_solve(const double *partials, uint32_t G, uint32_t n, uint32_t blocks, double *warp, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * B2  The spacetime trainer's colour decoder (examples/helper/STG/helper_model.py: Sandwich / getcolormodel(), applied to the
