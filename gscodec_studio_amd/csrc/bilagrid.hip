@@ -261,18 +261,6 @@ GS_DEV void point_bwd(const SliceBwdArgs &a, const float *grid, uint32_t b, uint
     }
 }
 
-GS_DEV uint32_t wave_min_u32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, off, 64));
-    return v;
-}
-
-GS_DEV uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
-    return v;
-}
-
 __global__ void __launch_bounds__(GS_BLOCK) bilagrid_slice_bwd_tiled_kernel(SliceBwdArgs a) {
     __shared__ float s_acc[BG_LDS_FLOATS];
     __shared__ uint32_t s_box[4];  // x min, x max, y min, y max over the corners the tile touches
@@ -381,12 +369,6 @@ __global__ void __launch_bounds__(GS_BLOCK) bilagrid_slice_bwd_point_kernel(Slic
 }
 
 // ---------------------------------------------------------------------------------------------------------------- TV
-GS_DEV double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 struct TvGeo {
     uint32_t n, L, H, W;  // n = N C L H W
     double cl, ch, cw;    // 1 / (count_axis N); 0 for an axis of size 1
@@ -412,30 +394,16 @@ __global__ void __launch_bounds__(GS_BLOCK) bilagrid_tv_fwd_kernel(const float *
             acc += (double)(d * d) * g.cl;
         }
     }
-    acc = wave_sum_f64(acc);
-    if (lane_id() == 0) s_red[threadIdx.x / GS_WAVE] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-#pragma unroll
-        for (int i = 0; i < GS_BLOCK / GS_WAVE; ++i) s += s_red[i];
-        partials[blockIdx.x] = s;
-    }
+    acc = block_sum_f64(acc, s_red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
 __global__ void __launch_bounds__(GS_BLOCK) bilagrid_tv_reduce_kernel(const double *partials, uint32_t n, float *out) {
     __shared__ double s_red[GS_BLOCK / GS_WAVE];
     double s = 0.0;
     for (uint32_t i = threadIdx.x; i < n; i += GS_BLOCK) s += partials[i];
-    s = wave_sum_f64(s);
-    if (lane_id() == 0) s_red[threadIdx.x / GS_WAVE] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        s = 0.0;
-#pragma unroll
-        for (int i = 0; i < GS_BLOCK / GS_WAVE; ++i) s += s_red[i];
-        *out = (float)s;
-    }
+    s = block_sum_f64(s, s_red);
+    if (threadIdx.x == 0) *out = (float)s;
 }
 
 __global__ void __launch_bounds__(GS_BLOCK) bilagrid_tv_bwd_kernel(const float *x, TvGeo g, const float *grad, float *v_x) {

@@ -13,12 +13,6 @@ constexpr int CC_RCOND_LOG2 = 40;  // eigenvalues at or below 2^-40 of the large
 constexpr int CC_SWEEPS = 20;  // Jacobi converges quadratically: 10 x 10 is done in 6 to 11 sweeps, the loop leaves then
 static_assert(GS_BLOCK >= cc_record(3) && GS_BLOCK >= cc_cols(3) * cc_cols(3), "a thread per record entry and per matrix entry");
 
-GS_DEV double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // the quadratic expansion of one pixel, in the reference's column order
 template <int N>
 GS_DEV void features(const float (&x)[N], double (&a)[cc_cols(N)]) {

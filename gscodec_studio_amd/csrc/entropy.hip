@@ -177,17 +177,6 @@ GS_DEV Lik likelihood(float lower, float upper) {
     return r;
 }
 
-// 64-lane sum with DPP row shifts + row broadcasts; the total lands in lane 63
-GS_DEV float wave_sum63(float v) {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xf, 0xf, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xf, 0xf, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xf, 0xf, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xa, 0xf, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xc, 0xf, false));
-    return v;
-}
-
 // grid: x = run of rows inside a chunk, y = chunk j (0..31), z = channel c.  One (chunk, channel) pair
 // has ONE parameter set, so inside a workgroup the parameters are wave-uniform: they are transformed
 // once (softplus / tanh), parked in LDS and pulled into SGPRs -- the MLP's multiply-adds take them as
@@ -260,7 +249,7 @@ __global__ void __launch_bounds__(256) entropy_kernel(EntArgs a, float *__restri
         // atomics serialise at the memory side)
 #pragma unroll
         for (int k = 0; k < P; ++k) {
-            const float tot = wave_sum63(acc[k]);
+            const float tot = wave_sum_lane63(acc[k]);
             if ((tid & 63u) == 63u) atomicAdd(&s_sum[k], tot);
         }
         __syncthreads();

@@ -14,6 +14,11 @@
 #define GS_WAVE 64
 #define GS_BLOCK 256
 
+// Compositing thresholds of every alpha-blending kernel (tile, surfel, index and accumulate ops)
+constexpr float GS_ALPHA_MIN = 1.f / 255.f; // a sample below it is skipped
+constexpr float GS_ALPHA_MAX = 0.999f;      // alpha clamp; above it the backward passes no gradient to conic / xy / opacity
+constexpr float GS_T_MIN = 1e-4f;           // the forward's exclusive stop: the sample that would take T to <= GS_T_MIN ends the pixel
+
 #define GS_DEV __device__ __forceinline__
 // First statement of a device function whose results must not depend on the kernel it is inlined into: no fma contraction of its
 // operations.  The default, -ffp-contract=fast-honor-pragmas, fuses a multiply into an add wherever the surrounding code lets it, so
@@ -224,6 +229,26 @@ GS_DEV Sym3 covar_from_rot_scale(const Mat3 &R, float sx, float sy, float sz) {
     return S;
 }
 
+// d L / d q of R = rot(q / |q|), ADDED to vq, given V = d L / d R   (quat.cuh:33-57)
+GS_DEV void rotmat_vjp_quat(float qw, float qx, float qy, float qz, const Mat3 &V, float vq[4]) {
+    // d R / d q_normalised
+    float inv = rsqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
+    float w = qw * inv, x = qx * inv, y = qy * inv, z = qz * inv;
+    float gw = 2.f * (x * (V.m[2][1] - V.m[1][2]) + y * (V.m[0][2] - V.m[2][0]) + z * (V.m[1][0] - V.m[0][1]));
+    float gx = 2.f * (-2.f * x * (V.m[1][1] + V.m[2][2]) + y * (V.m[1][0] + V.m[0][1]) +
+                      z * (V.m[2][0] + V.m[0][2]) + w * (V.m[2][1] - V.m[1][2]));
+    float gy = 2.f * (x * (V.m[1][0] + V.m[0][1]) - 2.f * y * (V.m[0][0] + V.m[2][2]) +
+                      z * (V.m[2][1] + V.m[1][2]) + w * (V.m[0][2] - V.m[2][0]));
+    float gz = 2.f * (x * (V.m[2][0] + V.m[0][2]) + y * (V.m[2][1] + V.m[1][2]) -
+                      2.f * z * (V.m[0][0] + V.m[1][1]) + w * (V.m[1][0] - V.m[0][1]));
+    // through the normalisation: (g - (g . qn) qn) / |q|
+    float dot = gw * w + gx * x + gy * y + gz * z;
+    vq[0] += (gw - dot * w) * inv;
+    vq[1] += (gx - dot * x) * inv;
+    vq[2] += (gy - dot * y) * inv;
+    vq[3] += (gz - dot * z) * inv;
+}
+
 // VJP of Sigma = (R S)(R S)^T w.r.t. quaternion and scale, given a SYMMETRISED
 // upstream gradient G (G = v_Sigma + v_Sigma^T already folded: pass the full
 // matrix gradient as Mat3, not assumed symmetric).
@@ -256,22 +281,7 @@ GS_DEV void covar_vjp_quat_scale(
         V.m[i][1] = vM.m[i][1] * sy;
         V.m[i][2] = vM.m[i][2] * sz;
     }
-    // d R / d q_normalised
-    float inv = rsqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-    float w = qw * inv, x = qx * inv, y = qy * inv, z = qz * inv;
-    float gw = 2.f * (x * (V.m[2][1] - V.m[1][2]) + y * (V.m[0][2] - V.m[2][0]) + z * (V.m[1][0] - V.m[0][1]));
-    float gx = 2.f * (-2.f * x * (V.m[1][1] + V.m[2][2]) + y * (V.m[1][0] + V.m[0][1]) +
-                      z * (V.m[2][0] + V.m[0][2]) + w * (V.m[2][1] - V.m[1][2]));
-    float gy = 2.f * (x * (V.m[1][0] + V.m[0][1]) - 2.f * y * (V.m[0][0] + V.m[2][2]) +
-                      z * (V.m[2][1] + V.m[1][2]) + w * (V.m[0][2] - V.m[2][0]));
-    float gz = 2.f * (x * (V.m[2][0] + V.m[0][2]) + y * (V.m[2][1] + V.m[1][2]) -
-                      2.f * z * (V.m[0][0] + V.m[1][1]) + w * (V.m[1][0] - V.m[0][1]));
-    // through the normalisation: (g - (g . qn) qn) / |q|
-    float dot = gw * w + gx * x + gy * y + gz * z;
-    vq[0] += (gw - dot * w) * inv;
-    vq[1] += (gx - dot * x) * inv;
-    vq[2] += (gy - dot * y) * inv;
-    vq[3] += (gz - dot * z) * inv;
+    rotmat_vjp_quat(qw, qx, qy, qz, V, vq);
 }
 
 // ---------------------------------------------------------------------------
@@ -286,11 +296,60 @@ GS_DEV float wave_sum(float v) {
     return v;
 }
 
+// full-wave double sum (xor butterfly: every lane adds the same two values in the same order); double2: two sums side by side
+GS_DEV double wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+GS_DEV double2 wave_sum_f64(double2 v) { return make_double2(wave_sum_f64(v.x), wave_sum_f64(v.y)); }
+
+// Block sum of a double or a double2, valid in thread 0 only: the wave sums, then thread 0 adds the waves in index order -- a fixed
+// order, so the result is bit-identical from run to run.  Every thread of an NW-wave block calls it (one barrier inside).
+template <typename T, int NW>
+GS_DEV T block_sum_f64(T v, T (&s_red)[NW]) {
+    v = wave_sum_f64(v);
+    if (lane_id() == 0) s_red[threadIdx.x / GS_WAVE] = v;
+    __syncthreads();
+    T s = {};
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < NW; ++i) s += s_red[i];
+    }
+    return s;
+}
+
+// 64-lane sum with DPP row shifts + row broadcasts (GFX9 family).  The total is valid in lane 63 only.  All 64 lanes must be
+// active.  Builtins, scheduled by the compiler; dpp_reduce.h's wave_reduce_sum_N are inline asm that interleaves N such chains.
+GS_DEV float wave_sum_lane63(float v) {
+    // row_shr:1, row_shr:2, row_shr:4, row_shr:8 -> inclusive scan inside each row of 16
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, false));
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xf, 0xf, false));
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xf, 0xf, false));
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xf, 0xf, false));
+    // row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xa, 0xf, false));
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xc, 0xf, false));
+    return v;
+}
+
 GS_DEV int wave_max_i32(int v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         int o = __shfl_xor(v, off, 64);
         v = v > o ? v : o;
     }
+    return v;
+}
+
+GS_DEV uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, off, 64));
+    return v;
+}
+
+GS_DEV uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
     return v;
 }

@@ -35,13 +35,6 @@ namespace {
 constexpr float kC1 = 0.01f * 0.01f;
 constexpr float kC2 = 0.03f * 0.03f;
 
-// full-wave double sum (xor butterfly: every lane adds the same two values in the same order)
-GS_DEV double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 struct Window {
     float w[11];
 };
@@ -106,7 +99,7 @@ __global__ void __launch_bounds__(GS_BLOCK) ssim_fwd_kernel(SsimFwdArgs a) {
     __shared__ __attribute__((aligned(16))) float s_x[SSIM_HR * SSIM_PITCH];
     __shared__ __attribute__((aligned(16))) float s_y[SSIM_HR * SSIM_PITCH];
     __shared__ __attribute__((aligned(16))) float s_h[5][SSIM_HR * SSIM_TW];
-    __shared__ double s_red[2][GS_BLOCK / GS_WAVE];
+    __shared__ double2 s_red[GS_BLOCK / GS_WAVE];  // (ssim, l1)
     const Geo &g = a.g;
     const uint32_t b = blockIdx.z;
     const int32_t h0 = (int32_t)(blockIdx.y * SSIM_TH), w0 = (int32_t)(blockIdx.x * SSIM_TW);
@@ -199,50 +192,27 @@ __global__ void __launch_bounds__(GS_BLOCK) ssim_fwd_kernel(SsimFwdArgs a) {
         }
         __syncthreads();  // the staged tiles are overwritten by the next channel
     }
-    acc_s = wave_sum_f64(acc_s);
-    acc_l = wave_sum_f64(acc_l);
-    if (lane_id() == 0) {
-        s_red[0][tid / GS_WAVE] = acc_s;
-        s_red[1][tid / GS_WAVE] = acc_l;
-    }
-    __syncthreads();
+    const double2 sum = block_sum_f64(make_double2(acc_s, acc_l), s_red);
     if (tid == 0) {
-        double s = 0.0, l = 0.0;
-#pragma unroll
-        for (int i = 0; i < GS_BLOCK / GS_WAVE; ++i) {
-            s += s_red[0][i];
-            l += s_red[1][i];
-        }
         const uint64_t blk = ((uint64_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        a.partials[2 * blk] = s;
-        a.partials[2 * blk + 1] = l;
+        a.partials[2 * blk] = sum.x;
+        a.partials[2 * blk + 1] = sum.y;
     }
 }
 
 // one block: the partials in a fixed order (thread t takes t, t + 1024, ...; then a fixed tree), the means and the weighted loss
 __global__ void __launch_bounds__(SSIM_RED_THREADS) ssim_reduce_kernel(const double *partials, uint32_t n, double inv_s, double inv_l,
                                                                        float lam, float *out_ssim, float *out_l1, float *out_loss) {
-    __shared__ double s_red[2][SSIM_RED_THREADS / GS_WAVE];
+    __shared__ double2 s_red[SSIM_RED_THREADS / GS_WAVE];  // (ssim, l1)
     const uint32_t tid = threadIdx.x;
     double s = 0.0, l = 0.0;
     for (uint32_t i = tid; i < n; i += SSIM_RED_THREADS) {
         s += partials[2 * i];
         l += partials[2 * i + 1];
     }
-    s = wave_sum_f64(s);
-    l = wave_sum_f64(l);
-    if (lane_id() == 0) {
-        s_red[0][tid / GS_WAVE] = s;
-        s_red[1][tid / GS_WAVE] = l;
-    }
-    __syncthreads();
+    const double2 sum = block_sum_f64(make_double2(s, l), s_red);
     if (tid == 0) {
-        s = l = 0.0;
-        for (int i = 0; i < SSIM_RED_THREADS / GS_WAVE; ++i) {
-            s += s_red[0][i];
-            l += s_red[1][i];
-        }
-        const float ssim = (float)(s * inv_s), l1 = (float)(l * inv_l);
+        const float ssim = (float)(sum.x * inv_s), l1 = (float)(sum.y * inv_l);
         if (out_ssim) *out_ssim = ssim;
         if (out_l1) *out_l1 = l1;
         if (out_loss) *out_loss = l1 * (1.f - lam) + (1.f - ssim) * lam;

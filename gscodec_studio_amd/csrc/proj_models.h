@@ -1,5 +1,5 @@
-// proj_models.h -- camera models shared by the fused projection kernels (projection.hip) and the
-// unfused public ops (unfused.hip): Jacobians of pinhole / orthographic / equidistant-fisheye
+// proj_models.h -- the camera and its loaders, and the camera models shared by the fused projection kernels (projection.hip)
+// and the unfused public ops (unfused.hip): Jacobians of pinhole / orthographic / equidistant-fisheye
 // projection at a camera-space point and the matching mean VJP.
 // Reference: gsplat/cuda/include/proj.cuh (persp 80-199, ortho 9-77, fisheye 202-343).
 #pragma once
@@ -12,16 +12,27 @@ struct Camera {
     float fx, fy, cx, cy;
 };
 
-GS_DEV Camera load_camera(const float *__restrict__ viewmats, const float *__restrict__ Ks, uint32_t c) {
-    const float *V = viewmats + 16 * c;
-    const float *K = Ks + 9 * c;
-    Camera cam;
+// rotation of a row-major 4x4 pose: its upper-left 3x3
+GS_DEV Mat3 load_rot(const float *V) {
+    Mat3 r;
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) cam.W.m[i][j] = V[4 * i + j];
-    cam.tx = V[3]; cam.ty = V[7]; cam.tz = V[11];
+        for (int j = 0; j < 3; ++j) r.m[i][j] = V[4 * i + j];
+    return r;
+}
+
+// the intrinsics alone, from a row-major 3x3 K: all that the ops on camera-space points and depth-to-normal need of a Camera
+GS_DEV void load_intrinsics(Camera &cam, const float *K) {
     cam.fx = K[0]; cam.cx = K[2]; cam.fy = K[4]; cam.cy = K[5];
+}
+
+GS_DEV Camera load_camera(const float *__restrict__ viewmats, const float *__restrict__ Ks, uint32_t c) {
+    const float *V = viewmats + 16 * c;
+    Camera cam;
+    cam.W = load_rot(V);
+    cam.tx = V[3]; cam.ty = V[7]; cam.tz = V[11];
+    load_intrinsics(cam, Ks + 9 * c);
     return cam;
 }
 

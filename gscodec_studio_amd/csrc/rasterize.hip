@@ -132,7 +132,7 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_fwd_kernel(RasterArgs a, 
             const float a_eff = ok ? sm.alpha : 0.f;
             const float Tj = T;
             const float next_T = Tj - Tj * a_eff;     // the loop-carried chain
-            const bool stop = ok && (next_T <= T_MIN); // exclusive stop
+            const bool stop = ok && (next_T <= GS_T_MIN); // exclusive stop
             const bool use = !done && !stop;           // this record is composited
             Tkeep = done ? Tkeep : Tj;                 // transmittance before the stopping splat
             const float vis = use ? a_eff * Tj : 0.f;
@@ -375,7 +375,7 @@ __global__ void __launch_bounds__(256, CDIM > 9 ? GS_WIDE_FWD_WAVES : 1) raster_
             // select (the alpha actually applied: 0 for a finished or finishing pixel) instead of separate selects
             // for the weight and for T -- T is then recomputed with it (a second fma is cheaper than a select)
             const float Tj = T;
-            const bool stop = ok[g] && (__builtin_fmaf(-Tj, alpha[g], Tj) <= T_MIN);
+            const bool stop = ok[g] && (__builtin_fmaf(-Tj, alpha[g], Tj) <= GS_T_MIN);
             done = done || stop;
             const bool use = ok[g] && !done; // composited: accepted, and the pixel neither finished nor finishing
             const float a_use = use ? alpha[g] : 0.f;
@@ -769,8 +769,8 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_bwd_kernel(RasterArgs a, 
                 }
             }
             const float v_alpha = D * Tn + (Tw - Bq) * ra;
-            // gradient gate: nothing for conic / xy / opacity when o * vis > ALPHA_MAX (`&`: see seg_sample)
-            const float v_sigma = (valid & (araw <= ALPHA_MAX)) ? -araw * v_alpha : 0.f;
+            // gradient gate: nothing for conic / xy / opacity when o * vis > GS_ALPHA_MAX (`&`: see seg_sample)
+            const float v_sigma = (valid & (araw <= GS_ALPHA_MAX)) ? -araw * v_alpha : 0.f;
             Bq += facv * D;
             T = valid ? Tn : T;
             const float sdx = v_sigma * dx, sdy = v_sigma * dy;
@@ -790,22 +790,22 @@ __global__ void __launch_bounds__(GS_WAVE) raster_wave_bwd_kernel(RasterArgs a, 
                 // any channel count: one reduction + atomic per channel
                 for (uint32_t k = 0; k < cnt; ++k) {
                     // (0.f +: the sum used to start from zero -- one fma, a -0 product enters the reduction as +0)
-                    const float c = wave_reduce_sum_dpp(0.f + facv * (inside ? ga.v_render_colors[vpix + k * ga.s_vrc_ch] : 0.f));
+                    const float c = wave_sum_lane63(0.f + facv * (inside ? ga.v_render_colors[vpix + k * ga.s_vrc_ch] : 0.f));
                     if (lane == GS_WAVE - 1) unsafeAtomicAdd(vcol + k, c); // (more than 4 channels: no deterministic mode, checked by the caller)
                 }
             } else {
 #pragma unroll
-                for (int k = 0; k < CR; ++k) Cs[k] = wave_reduce_sum_dpp(Cs[k]);
+                for (int k = 0; k < CR; ++k) Cs[k] = wave_sum_lane63(Cs[k]);
             }
-            S0 = wave_reduce_sum_dpp(S0);
-            Sx = wave_reduce_sum_dpp(Sx);
-            Sy = wave_reduce_sum_dpp(Sy);
-            Sxx = wave_reduce_sum_dpp(Sxx);
-            Sxy = wave_reduce_sum_dpp(Sxy);
-            Syy = wave_reduce_sum_dpp(Syy);
+            S0 = wave_sum_lane63(S0);
+            Sx = wave_sum_lane63(Sx);
+            Sy = wave_sum_lane63(Sy);
+            Sxx = wave_sum_lane63(Sxx);
+            Sxy = wave_sum_lane63(Sxy);
+            Syy = wave_sum_lane63(Syy);
             if (ABS) {
-                Ax = wave_reduce_sum_dpp(Ax);
-                Ay = wave_reduce_sum_dpp(Ay);
+                Ax = wave_sum_lane63(Ax);
+                Ay = wave_sum_lane63(Ay);
             }
             if (lane == GS_WAVE - 1) {
                 const size_t gr = (size_t)g;

@@ -1,4 +1,4 @@
-// rasterize_common.h -- argument blocks and wave64 primitives shared by the compositing kernels.
+// rasterize_common.h -- argument blocks, gradient accumulation and host-side routing types shared by the compositing kernels.
 #pragma once
 
 #include "gs_common.h"
@@ -77,20 +77,6 @@ GS_DEV void grad_add(const RasterGradArgs &ga, float *p, size_t row, uint32_t co
     } else {
         unsafeAtomicAdd(p, v);
     }
-}
-
-// 64-lane sum with DPP row shifts + row broadcasts (GFX9 family).  The total is valid in
-// lane 63 only.  All 64 lanes must be active.
-GS_DEV float wave_reduce_sum_dpp(float v) {
-    // row_shr:1, row_shr:2, row_shr:4, row_shr:8 -> inclusive scan inside each row of 16
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xf, 0xf, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xf, 0xf, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xf, 0xf, false));
-    // row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xa, 0xf, false));
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xc, 0xf, false));
-    return v;
 }
 
 // Host side (rasterize.hip; the wide backward's launcher in rasterize_wide.hip).  The kernels a call runs on: the tile forward /

@@ -1,8 +1,9 @@
 // rasterize_dev.h -- device helpers shared by the compositing kernels of rasterize.hip (1..4 channels, generic route) and
-// rasterize_wide.hip (5..32 channels): the sample decision (splat_sample: exponent, alpha, accept -- its ONE definition, with
-// the thresholds ALPHA_MIN / ALPHA_MAX / T_MIN), splat fetch, exact rectangle culling, XCD remap, tile geometry, the stages of
-// the forward kernels (pixel of a lane, masked tile, priority, record write, checkpoint cursor, list index, epilogue), the
-// segmented backward's arguments.  The stages of the two segmented backwards themselves: rasterize_seg_dev.h.
+// rasterize_wide.hip (5..32 channels): the sample decision (splat_sample: exponent, alpha, accept -- its ONE definition; the
+// thresholds GS_ALPHA_MIN / GS_ALPHA_MAX / GS_T_MIN have theirs in gs_common.h), splat fetch, exact rectangle culling, XCD
+// remap, tile geometry, the stages of the forward kernels (pixel of a lane, masked tile, priority, record write, checkpoint
+// cursor, list index, epilogue), the segmented backward's arguments.  The stages of the two segmented backwards themselves:
+// rasterize_seg_dev.h.
 #pragma once
 
 #include "gs_common.h"
@@ -12,9 +13,6 @@ namespace {
 
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
-constexpr float ALPHA_MIN = 1.f / 255.f; // a sample below it is skipped
-constexpr float ALPHA_MAX = 0.999f;      // alpha clamp; above it the backward passes no gradient to conic / xy / opacity
-constexpr float T_MIN = 1e-4f;           // the forward's exclusive stop: the sample that would take T to <= T_MIN ends the pixel
 constexpr float LOG2_255 = 7.994353436858858f;
 constexpr int HEAVY_TILE = 1024; // list length from which a wave raises its priority
 // cost classes of the backward's work items: a segment of `seg` entries costs at most 4 * seg record evaluations
@@ -27,17 +25,17 @@ GS_DEV uint32_t cost_class(uint32_t c, int32_t seg) { return min(c * 8u / (uint3
 // log2(opacity).  pl = power + log2(opacity) with the constant riding in the last fma; the reference's "sigma < 0" (reject)
 // is read off as pl > log2(opacity): the two differ only for |sigma| below the rounding of pl, where the sign of a computed
 // sigma is rounding noise in any case.  Returns the accept bit: pre (the caller's own condition on the sample, such as "the
-// entry is not behind the pixel's last contributor"), sigma >= 0 and alpha >= ALPHA_MIN.
+// entry is not behind the pixel's last contributor"), sigma >= 0 and alpha >= GS_ALPHA_MIN.
 struct SplatSample {
     float pl;    // log2 of the unclamped alpha
     float araw;  // exp2(pl) = o exp(-sigma)
-    float alpha; // min(ALPHA_MAX, araw)
+    float alpha; // min(GS_ALPHA_MAX, araw)
 };
 GS_DEV bool splat_sample(float dx, float dy, float qa, float qb, float qc, float lo2, SplatSample &s, bool pre = true) {
     s.pl = __builtin_fmaf(dx, __builtin_fmaf(qb, dy, qa * dx), __builtin_fmaf(qc * dy, dy, lo2));
     s.araw = __builtin_amdgcn_exp2f(s.pl);
-    s.alpha = fminf(ALPHA_MAX, s.araw);
-    return pre && !(s.pl > lo2) && (s.alpha >= ALPHA_MIN);
+    s.alpha = fminf(GS_ALPHA_MAX, s.araw);
+    return pre && !(s.pl > lo2) && (s.alpha >= GS_ALPHA_MIN);
 }
 
 struct SplatRaw {

@@ -200,9 +200,9 @@ GS_DEV void seg_sample(const float4 &r0, float qc, float lo2, const float (&col)
             o.Cs[k] += facv * p.vc[i][k];
         }
         const float v_alpha = D * Tn + p.Wq[i] * ra;
-        // gradient gate: nothing for conic / xy / opacity when o * vis > ALPHA_MAX.  (`&`: two plain compares.  As `&&` the
+        // gradient gate: nothing for conic / xy / opacity when o * vis > GS_ALPHA_MAX.  (`&`: two plain compares.  As `&&` the
         // condition reaches the code generator as a select, which costs this loop a v_max canonicalisation of araw per sample.)
-        const float v_sigma = (valid & (sm.araw <= ALPHA_MAX)) ? -sm.araw * v_alpha : 0.f;
+        const float v_sigma = (valid & (sm.araw <= GS_ALPHA_MAX)) ? -sm.araw * v_alpha : 0.f;
         p.Wq[i] -= facv * D;
         p.T[i] = Tn;
         const float sdx = v_sigma * dx, sdy = v_sigma * dy;

@@ -10,33 +10,13 @@
 // lane.  This is the simple first shape: correct on every case, not yet tuned.
 #include "gs_common.h"
 #include "dpp_reduce.h"
+#include "proj_models.h"
 
 #define SF_BATCH 256
-#define SF_ALPHA_MAX 0.999f
-#define SF_ALPHA_MIN (1.f / 255.f)
-#define SF_T_MIN 1e-4f
 
 // ---------------------------------------------------------------------------
 // projection
 // ---------------------------------------------------------------------------
-struct SurfelCam {
-    Mat3 R;
-    float t[3];
-    float fx, fy, cx, cy;
-};
-
-GS_DEV SurfelCam surfel_cam(const float *vm, const float *K) {
-    SurfelCam c;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) c.R.m[i][j] = vm[i * 4 + j];
-        c.t[i] = vm[i * 4 + 3];
-    }
-    c.fx = K[0]; c.cx = K[2]; c.fy = K[4]; c.cy = K[5];
-    return c;
-}
-
 __global__ void __launch_bounds__(GS_BLOCK) surfel_projection_fwd_kernel(
     uint32_t N, const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
     const float *__restrict__ viewmats, const float *__restrict__ Ks, int32_t width, int32_t height, float near_plane, float far_plane,
@@ -46,17 +26,18 @@ __global__ void __launch_bounds__(GS_BLOCK) surfel_projection_fwd_kernel(
     if (n >= N) return;
     const uint32_t c = blockIdx.y;
     const uint64_t idx = (uint64_t)c * N + n;
-    const SurfelCam cam = surfel_cam(viewmats + c * 16, Ks + c * 9);
+    const Camera cam = load_camera(viewmats, Ks, c);
     const float mx = means[n * 3], my = means[n * 3 + 1], mz = means[n * 3 + 2];
+    const float ct[3] = {cam.tx, cam.ty, cam.tz};
     float p[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) p[i] = cam.R.m[i][0] * mx + cam.R.m[i][1] * my + cam.R.m[i][2] * mz + cam.t[i];
+    for (int i = 0; i < 3; ++i) p[i] = cam.W.m[i][0] * mx + cam.W.m[i][1] * my + cam.W.m[i][2] * mz + ct[i];
 
     int32_t radius = 0;
     float M[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, m2[2] = {0.f, 0.f}, nrm[3] = {0.f, 0.f, 0.f}, depth = 0.f;
     if (!(p[2] < near_plane || p[2] > far_plane)) {
         const Mat3 Rq = quat_to_rotmat(quats[n * 4], quats[n * 4 + 1], quats[n * 4 + 2], quats[n * 4 + 3]);
-        const Mat3 RR = mat3_mul(cam.R, Rq);
+        const Mat3 RR = mat3_mul(cam.W, Rq);
         const float sx = scales[n * 3], sy = scales[n * 3 + 1];
         // WH = [a | b | p], rows of M = K WH
         float WH[3][3];
@@ -105,24 +86,6 @@ __global__ void __launch_bounds__(GS_BLOCK) surfel_projection_fwd_kernel(
     for (int i = 0; i < 3; ++i) normals[idx * 3 + i] = nrm[i];
 }
 
-// d L / d q of R = rot(q / |q|), given V = d L / d R (the quaternion part of covar_vjp_quat_scale, gs_common.h)
-GS_DEV void surfel_rotmat_vjp_quat(float qw, float qx, float qy, float qz, const Mat3 &V, float vq[4]) {
-    const float inv = rsqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-    const float w = qw * inv, x = qx * inv, y = qy * inv, z = qz * inv;
-    const float gw = 2.f * (x * (V.m[2][1] - V.m[1][2]) + y * (V.m[0][2] - V.m[2][0]) + z * (V.m[1][0] - V.m[0][1]));
-    const float gx = 2.f * (-2.f * x * (V.m[1][1] + V.m[2][2]) + y * (V.m[1][0] + V.m[0][1]) + z * (V.m[2][0] + V.m[0][2]) +
-                            w * (V.m[2][1] - V.m[1][2]));
-    const float gy = 2.f * (x * (V.m[1][0] + V.m[0][1]) - 2.f * y * (V.m[0][0] + V.m[2][2]) + z * (V.m[2][1] + V.m[1][2]) +
-                            w * (V.m[0][2] - V.m[2][0]));
-    const float gz = 2.f * (x * (V.m[2][0] + V.m[0][2]) + y * (V.m[2][1] + V.m[1][2]) - 2.f * z * (V.m[0][0] + V.m[1][1]) +
-                            w * (V.m[1][0] - V.m[0][1]));
-    const float dot = gw * w + gx * x + gy * y + gz * z;
-    vq[0] = (gw - dot * w) * inv;
-    vq[1] = (gx - dot * x) * inv;
-    vq[2] = (gy - dot * y) * inv;
-    vq[3] = (gz - dot * z) * inv;
-}
-
 __global__ void __launch_bounds__(GS_BLOCK) surfel_projection_bwd_kernel(
     uint32_t N, const float *__restrict__ means, const float *__restrict__ quats, const float *__restrict__ scales,
     const float *__restrict__ viewmats, const float *__restrict__ Ks, const int32_t *__restrict__ radii,
@@ -136,7 +99,7 @@ __global__ void __launch_bounds__(GS_BLOCK) surfel_projection_bwd_kernel(
     const bool live = n < N && radii[idx] > 0;
     float vR[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, vt[3] = {0.f, 0.f, 0.f};
     if (live) {
-        const SurfelCam cam = surfel_cam(viewmats + c * 16, Ks + c * 9);
+        const Camera cam = load_camera(viewmats, Ks, c);
         const float *M = ray_transforms + idx * 9;
         float vM[9];
 #pragma unroll
@@ -173,11 +136,12 @@ __global__ void __launch_bounds__(GS_BLOCK) surfel_projection_bwd_kernel(
         // the normal: sgn * R_c * (third column of Rq); sgn from the forward's facing test
         float vn[3] = {0.f, 0.f, 0.f};
         if (v_normals) {
+            const float ct[3] = {cam.tx, cam.ty, cam.tz};
             float p[3], w3[3];
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                p[i] = cam.R.m[i][0] * mx + cam.R.m[i][1] * my + cam.R.m[i][2] * mz + cam.t[i];
-                w3[i] = cam.R.m[i][0] * Rq.m[0][2] + cam.R.m[i][1] * Rq.m[1][2] + cam.R.m[i][2] * Rq.m[2][2];
+                p[i] = cam.W.m[i][0] * mx + cam.W.m[i][1] * my + cam.W.m[i][2] * mz + ct[i];
+                w3[i] = cam.W.m[i][0] * Rq.m[0][2] + cam.W.m[i][1] * Rq.m[1][2] + cam.W.m[i][2] * Rq.m[2][2];
             }
             const float facing = -(w3[0] * p[0] + w3[1] * p[1] + w3[2] * p[2]);
             const float sgn = facing > 0.f ? 1.f : -1.f;
@@ -190,10 +154,10 @@ __global__ void __launch_bounds__(GS_BLOCK) surfel_projection_bwd_kernel(
         float vmean[3], vsx = 0.f, vsy = 0.f;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            const float ga = cam.R.m[0][i] * vWH[0][0] + cam.R.m[1][i] * vWH[1][0] + cam.R.m[2][i] * vWH[2][0];
-            const float gb = cam.R.m[0][i] * vWH[0][1] + cam.R.m[1][i] * vWH[1][1] + cam.R.m[2][i] * vWH[2][1];
-            const float gp = cam.R.m[0][i] * vWH[0][2] + cam.R.m[1][i] * vWH[1][2] + cam.R.m[2][i] * vWH[2][2];
-            const float gn = cam.R.m[0][i] * vn[0] + cam.R.m[1][i] * vn[1] + cam.R.m[2][i] * vn[2];
+            const float ga = cam.W.m[0][i] * vWH[0][0] + cam.W.m[1][i] * vWH[1][0] + cam.W.m[2][i] * vWH[2][0];
+            const float gb = cam.W.m[0][i] * vWH[0][1] + cam.W.m[1][i] * vWH[1][1] + cam.W.m[2][i] * vWH[2][1];
+            const float gp = cam.W.m[0][i] * vWH[0][2] + cam.W.m[1][i] * vWH[1][2] + cam.W.m[2][i] * vWH[2][2];
+            const float gn = cam.W.m[0][i] * vn[0] + cam.W.m[1][i] * vn[1] + cam.W.m[2][i] * vn[2];
             V.m[i][0] = ga * sx;
             V.m[i][1] = gb * sy;
             V.m[i][2] = gn;
@@ -201,8 +165,8 @@ __global__ void __launch_bounds__(GS_BLOCK) surfel_projection_bwd_kernel(
             vsy += gb * Rq.m[i][1];
             vmean[i] = gp;
         }
-        float vq[4];
-        surfel_rotmat_vjp_quat(qw, qx, qy, qz, V, vq);
+        float vq[4] = {0.f, 0.f, 0.f, 0.f};
+        rotmat_vjp_quat(qw, qx, qy, qz, V, vq);
 #pragma unroll
         for (int i = 0; i < 3; ++i) atomicAdd(v_means + n * 3 + i, vmean[i]);
 #pragma unroll
@@ -288,8 +252,8 @@ GS_DEV bool surfel_eval(const float *M, float mx, float my, float opac, float px
     const float sigma = 0.5f * (e.use3d ? w3 : w2);
     e.G = __expf(-sigma);
     e.raw = opac * e.G;
-    e.alpha = fminf(SF_ALPHA_MAX, e.raw);
-    return !(sigma < 0.f || e.alpha < SF_ALPHA_MIN);
+    e.alpha = fminf(GS_ALPHA_MAX, e.raw);
+    return !(sigma < 0.f || e.alpha < GS_ALPHA_MIN);
 }
 
 template <int CH>
@@ -339,7 +303,7 @@ __global__ void __launch_bounds__(SF_BATCH) surfel_rasterize_fwd_kernel(
             SurfelEval e;
             if (!surfel_eval(geo + 3, geo[0], geo[1], geo[2], px, py, e)) continue;
             const float next_T = T * (1.f - e.alpha);
-            if (next_T <= SF_T_MIN) {
+            if (next_T <= GS_T_MIN) {
                 done = true;
                 break;
             }
@@ -491,7 +455,7 @@ __global__ void __launch_bounds__(SF_BATCH) surfel_rasterize_bwd_kernel(
                     beh_wd += w * depth;
                 }
                 beh_w += w;
-                if (e.raw <= SF_ALPHA_MAX) {
+                if (e.raw <= GS_ALPHA_MAX) {
                     g_o = e.G * v_alpha;
                     const float v_G = geo[2] * v_alpha;
                     if (e.use3d) {
@@ -548,27 +512,25 @@ __global__ void __launch_bounds__(SF_BATCH) surfel_rasterize_bwd_kernel(
 // ---------------------------------------------------------------------------
 // depth -> normal
 // ---------------------------------------------------------------------------
+// Its own struct, not Camera: the rotation here is camera->world, Camera::W is world->camera
 struct DepthCam {
-    float R[3][3], fx, fy, cx, cy;
+    Mat3 R;
+    float fx, fy, cx, cy;
     int z_depth;
 };
 
 GS_DEV DepthCam depth_cam(const float *c2w, const float *K, int z_depth) {
-    DepthCam c;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) c.R[i][j] = c2w[i * 4 + j];
-    c.fx = K[0]; c.cx = K[2]; c.fy = K[4]; c.cy = K[5];
-    c.z_depth = z_depth;
-    return c;
+    const Mat3 R = load_rot(c2w);
+    Camera k;
+    load_intrinsics(k, K);
+    return {R, k.fx, k.fy, k.cx, k.cy, z_depth};
 }
 
 // world-space ray direction of pixel (i, j): the point is origin + depth * dir, and the origin cancels in the differences
 GS_DEV void depth_dir(const DepthCam &c, int i, int j, float dir[3]) {
     const float x = ((float)j - c.cx + 0.5f) / c.fx, y = ((float)i - c.cy + 0.5f) / c.fy;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) dir[k] = c.R[k][0] * x + c.R[k][1] * y + c.R[k][2];
+    for (int k = 0; k < 3; ++k) dir[k] = c.R.m[k][0] * x + c.R.m[k][1] * y + c.R.m[k][2];
     if (!c.z_depth) {
         const float inv = 1.f / fmaxf(sqrtf(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]), 1e-12f);
 #pragma unroll

@@ -13,47 +13,20 @@
 
 namespace {
 
-struct M3 {
-    float m[3][3];
-};
-
-GS_DEV M3 load_m3(const float *p) {
-    M3 r;
+// a row-major [9] array <-> Mat3
+GS_DEV Mat3 load_m3(const float *p) {
+    Mat3 r;
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) r.m[i][j] = p[3 * i + j];
     return r;
 }
-GS_DEV void store_m3(float *p, const M3 &a) {
+GS_DEV void store_m3(float *p, const Mat3 &a) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) p[3 * i + j] = a.m[i][j];
-}
-GS_DEV M3 mul(const M3 &a, const M3 &b) {
-    M3 r;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) r.m[i][j] = a.m[i][0] * b.m[0][j] + a.m[i][1] * b.m[1][j] + a.m[i][2] * b.m[2][j];
-    return r;
-}
-GS_DEV M3 transpose(const M3 &a) {
-    M3 r;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) r.m[i][j] = a.m[j][i];
-    return r;
-}
-GS_DEV M3 rot_of(const float *V) { // upper-left 3x3 of a row-major 4x4
-    M3 r;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) r.m[i][j] = V[4 * i + j];
-    return r;
 }
 
 // ---------------------------------------------------------------- world_to_cam
@@ -64,7 +37,7 @@ __global__ void __launch_bounds__(GS_BLOCK) world_to_cam_fwd_kernel(uint32_t C, 
     const uint32_t c = blockIdx.y;
     if (n >= N) return;
     const float *V = viewmats + 16 * c; // wave-uniform
-    const M3 R = rot_of(V);
+    const Mat3 R = load_rot(V);
     const size_t o = (size_t)c * N + n;
     if (means_c != nullptr) {
         const float *p = means + 3 * (size_t)n;
@@ -72,8 +45,8 @@ __global__ void __launch_bounds__(GS_BLOCK) world_to_cam_fwd_kernel(uint32_t C, 
         for (int i = 0; i < 3; ++i) means_c[3 * o + i] = R.m[i][0] * p[0] + R.m[i][1] * p[1] + R.m[i][2] * p[2] + V[4 * i + 3];
     }
     if (covars_c != nullptr) {
-        const M3 S = load_m3(covars + 9 * (size_t)n);
-        store_m3(covars_c + 9 * o, mul(mul(R, S), transpose(R)));
+        const Mat3 S = load_m3(covars + 9 * (size_t)n);
+        store_m3(covars_c + 9 * o, mat3_mult(mat3_mul(R, S), R));
     }
 }
 
@@ -86,20 +59,20 @@ __global__ void __launch_bounds__(GS_BLOCK) world_to_cam_bwd_kernel(uint32_t C, 
     const uint32_t n = blockIdx.x * GS_BLOCK + threadIdx.x;
     const bool live = n < N;
     float p[3] = {0.f, 0.f, 0.f};
-    M3 S = {};
+    Mat3 S = {};
     if (live) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) p[i] = means[3 * (size_t)n + i];
         if (covars != nullptr) S = load_m3(covars + 9 * (size_t)n);
     }
     float vp[3] = {0.f, 0.f, 0.f};
-    M3 vS = {};
+    Mat3 vS = {};
     for (uint32_t c = 0; c < C; ++c) {
         const float *V = viewmats + 16 * c;
-        const M3 R = rot_of(V);
+        const Mat3 R = load_rot(V);
         const size_t o = (size_t)c * N + n;
         float g[3] = {0.f, 0.f, 0.f};
-        M3 G = {};
+        Mat3 G = {};
         if (live && v_means_c != nullptr) {
 #pragma unroll
             for (int i = 0; i < 3; ++i) g[i] = v_means_c[3 * o + i];
@@ -108,15 +81,15 @@ __global__ void __launch_bounds__(GS_BLOCK) world_to_cam_bwd_kernel(uint32_t C, 
         // v_p += R^T g ; v_S += R^T G R   (transform.cuh:19-37, 49-68)
 #pragma unroll
         for (int j = 0; j < 3; ++j) vp[j] += R.m[0][j] * g[0] + R.m[1][j] * g[1] + R.m[2][j] * g[2];
-        const M3 t = mul(mul(transpose(R), G), R);
+        const Mat3 t = mat3_mul(mat3_tmul(R, G), R);
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
             for (int j = 0; j < 3; ++j) vS.m[i][j] += t.m[i][j];
         if (NEED_VIEW) {
             // v_R = g p^T + G R S^T + G^T R S ; v_t = g   -- summed over the gaussians of this wave
-            const M3 a = mul(mul(G, R), transpose(S));
-            const M3 b = mul(mul(transpose(G), R), S);
+            const Mat3 a = mat3_mult(mat3_mul(G, R), S);
+            const Mat3 b = mat3_mul(mat3_tmul(G, R), S);
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
 #pragma unroll
@@ -138,13 +111,6 @@ __global__ void __launch_bounds__(GS_BLOCK) world_to_cam_bwd_kernel(uint32_t C, 
 }
 
 // ---------------------------------------------------------------- proj
-GS_DEV Camera intrinsics_only(const float *__restrict__ Ks, uint32_t c) {
-    const float *K = Ks + 9 * c;
-    Camera cam = {};
-    cam.fx = K[0]; cam.cx = K[2]; cam.fy = K[4]; cam.cy = K[5];
-    return cam;
-}
-
 GS_DEV void model_jac(const Camera &cam, int camera_model, float x, float y, float z, int W, int H, Jac &J, float &mx, float &my) {
     float txc, tyc;
     if (camera_model == GS_CAMERA_PINHOLE) pinhole_jac(cam, x, y, z, W, H, J, mx, my, txc, tyc);
@@ -158,10 +124,11 @@ __global__ void __launch_bounds__(GS_BLOCK) proj_fwd_kernel(uint32_t C, uint32_t
     const uint32_t n = blockIdx.x * GS_BLOCK + threadIdx.x;
     const uint32_t c = blockIdx.y;
     if (n >= N) return;
-    const Camera cam = intrinsics_only(Ks, c);
+    Camera cam = {};
+    load_intrinsics(cam, Ks + 9 * c);
     const size_t o = (size_t)c * N + n;
     const float *p = means + 3 * o;
-    const M3 S = load_m3(covars + 9 * o);
+    const Mat3 S = load_m3(covars + 9 * o);
     Jac J;
     float mx, my;
     model_jac(cam, camera_model, p[0], p[1], p[2], W, H, J, mx, my);
@@ -187,10 +154,11 @@ __global__ void __launch_bounds__(GS_BLOCK) proj_bwd_kernel(uint32_t C, uint32_t
     const uint32_t n = blockIdx.x * GS_BLOCK + threadIdx.x;
     const uint32_t c = blockIdx.y;
     if (n >= N) return;
-    const Camera cam = intrinsics_only(Ks, c);
+    Camera cam = {};
+    load_intrinsics(cam, Ks + 9 * c);
     const size_t o = (size_t)c * N + n;
     const float *p = means + 3 * o;
-    const M3 S = load_m3(covars + 9 * o);
+    const Mat3 S = load_m3(covars + 9 * o);
     Jac J;
     float mx, my;
     model_jac(cam, camera_model, p[0], p[1], p[2], W, H, J, mx, my);
@@ -283,10 +251,10 @@ __global__ void indices_in_range_kernel(uint32_t range_start, uint32_t range_end
             const IdxRec r = s_batch[t];
             const float dx = r.x - px, dy = r.y - py;
             const float sigma = 0.5f * (r.ca * dx * dx + r.cc * dy * dy) + r.cb * dx * dy;
-            const float alpha = fminf(0.999f, r.opac * __expf(-sigma));
-            if (sigma < 0.f || alpha < 1.f / 255.f) continue;
+            const float alpha = fminf(GS_ALPHA_MAX, r.opac * __expf(-sigma));
+            if (sigma < 0.f || alpha < GS_ALPHA_MIN) continue;
             const float next_trans = trans * (1.f - alpha);
-            if (next_trans <= 1e-4f) { // exclusive stop
+            if (next_trans <= GS_T_MIN) { // exclusive stop
                 done = true;
                 break;
             }
@@ -506,7 +474,7 @@ GS_DEV AccAlpha acc_alpha(const AccArgs &a, uint64_t m) {
     const float sigma = 0.5f * (ca * r.dx * r.dx + cc * r.dy * r.dy) + cb * r.dx * r.dy;
     r.e = expf(-sigma);
     r.raw = a.opacities[r.elem] * r.e;
-    r.alpha = fminf(r.raw, 0.999f);
+    r.alpha = fminf(r.raw, GS_ALPHA_MAX);
     return r;
 }
 
@@ -595,7 +563,7 @@ __global__ void __launch_bounds__(GS_BLOCK) accumulate_bwd_scatter_kernel(AccArg
     }
     const AccAlpha r = acc_alpha(a, m);
     const float va = v_alpha_pair[m];
-    if (!(r.raw <= 0.999f)) return; // clamp_max: no gradient above the cap (torch passes it at equality)
+    if (!(r.raw <= GS_ALPHA_MAX)) return; // clamp_max: no gradient above the cap (torch passes it at equality)
     if (v_opacities != nullptr) atomicAdd(v_opacities + r.elem, va * r.e);
     const float vs = -va * r.raw; // d / d sigma
     if (v_conics != nullptr) {
