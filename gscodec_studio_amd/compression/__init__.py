@@ -40,6 +40,13 @@
   symbol coded against the Gaussian that the trained ``Entropy_gaussian`` predicts at the splat's position (csrc/gauss_ans.hip:
   the regressor's MLP in one stated float32 order, lane-per-stream encode and decode at 16-bit resolution), with the reference's
   model files and meta keys around a bitstream defined by the numpy coder ``gauss_ans_reference``.
+
+* ``hevc_compression``: ``HevcCompression``, the reference's ``--compression hevc`` -- the same directory, with scales, quats,
+  opacities and sh0 as lossy transform-coded planes under HEVC's quantisation parameter ``qp``, the one codec with a rate knob.
+  The reference shells out to ffmpeg / libx265; the payload here is this project's own bitstream, not a replication of x265.
+* ``plane_codec``: ``plane_encode`` / ``plane_decode``, that payload on the GPU (csrc/plane_codec.hip: HEVC's 8 x 8 integer
+  transform and flat quantiser with one lane per block, then the rANS streams over 15 static tables), defined by the numpy code
+  ``plane_codec_reference`` that the kernels match byte for byte.
 """
 from .decode import decode_to_dynamic_inputs, decode_to_rasterizer_inputs, kmeans_decode, kmeans_encode, morton_order, reorder_splats, sort_splats
 from ._container import png_read, png_write
@@ -48,6 +55,8 @@ from .ans import ans_decode, ans_encode, normalize_frequencies, symbol_histogram
 from .gauss_ans import gauss_ans_decode, gauss_ans_encode, gaussian_params
 from .entropy_coding_compression import EntropyCodingCompression
 from .stg_compression import STGPngCompression
+from .plane_codec import plane_decode, plane_encode
+from .hevc_compression import HevcCompression
 from .grid_sort import grid_sort_order, sort_splats_grid
 from .kmeans import KMeans, kmeans_fit
 from .grid_codec import (
@@ -63,4 +72,5 @@ __all__ = ["quantize_grid", "dequantize_grid", "compress_to_arrays", "decompress
            "inverse_log_transform", "decode_to_rasterizer_inputs", "kmeans_decode", "kmeans_encode", "morton_order",
            "sort_splats", "reorder_splats", "PngCompression", "png_read", "png_write", "EntropyCodingCompression", "ans_encode",
            "ans_decode", "normalize_frequencies", "symbol_histogram", "grid_sort_order", "sort_splats_grid", "STGPngCompression",
-           "decode_to_dynamic_inputs", "KMeans", "kmeans_fit", "gaussian_params", "gauss_ans_encode", "gauss_ans_decode"]
+           "decode_to_dynamic_inputs", "KMeans", "kmeans_fit", "gaussian_params", "gauss_ans_encode", "gauss_ans_decode",
+           "HevcCompression", "plane_encode", "plane_decode"]

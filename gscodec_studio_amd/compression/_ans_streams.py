@@ -1,4 +1,5 @@
-"""What the two GPU coders (``ans.py``: a table per channel; ``gauss_ans.py``: a Gaussian per symbol) do around their kernels, once:
+"""What the GPU coders (``ans.py``: a table per channel; ``gauss_ans.py``: a Gaussian per symbol; ``plane_codec.py``: a table per
+scan diagonal of a transform-coded plane, its flat symbols as ``[N, 1]``) do around their kernels, once:
 the check of the symbol tensor, the encoder's tail (private slots -> lengths -> scan -> one read-back -> dense payload) and the
 decoder's head (limits, uploads, output).  A route brings its model, its encode / decode launch and its slot size; the stream layer
 under the kernels is csrc/ans_stream_dev.h."""

@@ -153,7 +153,7 @@ def _encode_streams(n: int, n_channels: int, stream_len: int, bits: int, slot: i
     buf = np.zeros((rows.size, slot), np.uint8)
     pos = np.full(rows.size, slot, np.int64)
     x = np.full(rows.size, STATE_LOW, np.uint64)
-    for j in range(stream_len - 1, -1, -1):
+    for j in range(int(lens.max()) - 1, -1, -1):  # no row has a symbol behind the longest one's
         act = j < lens
         f, cum = model(j)
         f = np.where(act, f, 1).astype(np.uint64)
@@ -194,7 +194,7 @@ def _decode_streams(offsets: np.ndarray, payload: np.ndarray, n: int, n_channels
     for b in range(4):
         x |= next_byte(everyone) << np.uint64(8 * b)
     out = np.zeros((rd.size, stream_len), np.uint8)
-    for j in range(stream_len):
+    for j in range(int(lens.max())):
         act = j < lens
         slot = (x & np.uint64((1 << bits) - 1)).astype(np.int64)
         s, f, cum = lookup(j, slot)

@@ -1,5 +1,5 @@
-// ans_stream_dev.h -- ONE rANS STREAM, the layer under both coders of the on-disk format (ans.hip: a static table per channel;
-// gauss_ans.hip: a Gaussian per symbol).  Nothing here knows a model: a model hands in the frequency f and the cumulative frequency
+// ans_stream_dev.h -- ONE rANS STREAM, the layer under the coders of the on-disk formats (ans.hip: a static table per channel;
+// gauss_ans.hip: a Gaussian per symbol; plane_codec.hip: a static table per scan diagonal).  Nothing here knows a model: a model hands in the frequency f and the cumulative frequency
 // cum of a symbol at a probability resolution of 2^P (a plain value: it folds where it is a constant) and names the symbol of a slot.
 //   state x: 32 bits, kept in [2^23, 2^31) between symbols
 //   encode (f, cum):  while x >= f << (31 - P): emit x & 255, x >>= 8;   x = (x / f << P) + x % f + cum

@@ -54,7 +54,8 @@ extern "C" {
  * gs_gaussian_bits_fwd / _bwd), and the Gaussian entropy coder's (gs_ans_pack_slots, gs_gauss_ans_slot_bytes,
  * gs_gauss_ans_encode_bytes, gs_gauss_ans_params, gs_gauss_ans_encode, gs_gauss_ans_decode), and the SparseAdam entries
  * (gs_sparse_adam_desc, gs_sparse_adam_multi, gs_sparse_adam_desc_layout), and the colour-matching entries
- * (gs_color_correct_pass, gs_color_correct_solve, gs_color_correct_record_doubles, gs_color_correct_rcond_log2). */
+ * (gs_color_correct_pass, gs_color_correct_solve, gs_color_correct_record_doubles, gs_color_correct_rcond_log2), and the plane codec's (gs_plane_transform_fwd / _inv,
+ * gs_plane_ans_slot_bytes, gs_plane_ans_encode, gs_plane_ans_decode). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -1034,6 +1035,37 @@ int32_t gs_gauss_ans_encode(uint64_t N, uint32_t C, uint32_t S, const uint8_t *c
 int32_t gs_gauss_ans_decode(uint64_t N, uint32_t C, uint32_t S, const uint8_t *payload, uint64_t payload_bytes,
                             const int64_t *offsets, const int16_t *mu_q, const uint8_t *k, const uint16_t *table, uint8_t *symbols,
                             gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Transform-coded attribute planes (plane_codec.hip): the payload of HevcCompression's <name>.bin -- a small intra codec for 8-bit
+ * planes [H, W, ch] (ch = 1..4) under HEVC's quantisation parameter qp (0..51), in place of the reference's ffmpeg / libx265 call
+ * (gsplat/compression/hevc_compression.py).  Not an HEVC stream: HEVC's 8-point integer transform and flat quantiser, no prediction,
+ * no RDO, rANS (the stream layer above, ans_stream_dev.h) over 15 static tables.  The format's definition is
+ * gscodec_studio_amd/compression/plane_codec_reference.py; integer arithmetic only, the kernels' results equal it element for
+ * element.  n_blocks = ceil(H / 8) ceil(W / 8); levels int16 [ch, n_blocks, 64], 16-byte aligned, the 64 of a block in scan order.
+ *
+ * gs_plane_transform_fwd: plane uint8 [H, W, ch] -> levels: one lane per 8 x 8 block of one channel, coordinates clamped into the
+ *   plane (edge replication), transform along x then y, quantiser.
+ * gs_plane_transform_inv: levels (any values: clamped to +-32767) -> plane uint8 [H, W, ch] (the layout gs_grid_dequantize reads):
+ *   dequantiser, transform along y then x, clip, only the pixels inside the plane are stored.
+ * gs_plane_ans_encode: the flat symbols uint8 [N] (N = 64 ch n_blocks, ordered channel, block, scan position) as ONE channel of
+ *   streams of S symbols, one lane per stream; the model of symbol i is row CTX[i % 64] (the anti-diagonal of its scan position) of
+ *   cum uint16 [15, 257] (cumulative frequencies, cum[c][256] = 2^P, 8 <= P <= 14; kept in LDS).  Slots of
+ *   gs_plane_ans_slot_bytes(S, P) = ceil(S P / 8) + 8 bytes in scratch (>= n_streams slots), lengths / states [n_streams];
+ *   gs_ans_pack_slots copies them.  *status (device uint32, zero-filled by the caller): bit 0 = a symbol with frequency 0 was met,
+ *   bit 1 = a slot was too small (no write leaves the slot).
+ * gs_plane_ans_decode: payload + offsets (int64 [n_streams + 1], device) -> symbols uint8 [N].  Reads are bounded to the stream's
+ *   byte range clamped to [0, payload_bytes], a byte beyond it is 0; the symbol is found by an 8-step binary search and at most two
+ *   bytes are read per symbol: a damaged file decodes to wrong symbols. */
+uint32_t gs_plane_ans_slot_bytes(uint32_t S, uint32_t P);
+int32_t gs_plane_transform_fwd(uint32_t H, uint32_t W, uint32_t ch, uint32_t qp, const uint8_t *plane, int16_t *levels,
+                               gs_stream_t stream);
+int32_t gs_plane_transform_inv(uint32_t H, uint32_t W, uint32_t ch, uint32_t qp, const int16_t *levels, uint8_t *plane,
+                               gs_stream_t stream);
+int32_t gs_plane_ans_encode(uint64_t N, uint32_t S, uint32_t P, const uint8_t *symbols, const uint16_t *cum, uint8_t *scratch,
+                            uint64_t scratch_bytes, uint32_t *lengths, uint32_t *states, uint32_t *status, gs_stream_t stream);
+int32_t gs_plane_ans_decode(uint64_t N, uint32_t S, uint32_t P, const uint8_t *payload, uint64_t payload_bytes,
+                            const int64_t *offsets, const uint16_t *cum, uint8_t *symbols, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Grid sort (grid_sort.hip): the order of the splats on the S x S image grid of the PNG codecs that makes every attribute image

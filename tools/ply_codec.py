@@ -1,11 +1,13 @@
 #!/usr/bin/env python
-"""The PNG codec on splats that were not trained here: a .ply in, a compressed directory out, and back.
+"""The file codecs on splats that were not trained here: a .ply in, a compressed directory out, and back.
 
-    python tools/ply_codec.py compress IN.ply DIR [--sort morton|grid|none]     load_ply, then PngCompression.compress
-    python tools/ply_codec.py decompress DIR OUT.ply                             PngCompression.decompress, then save_ply
+    python tools/ply_codec.py compress IN.ply DIR [--sort morton|grid|none] [--codec png|hevc] [--qp QP]
+                                                                load_ply, then PngCompression / HevcCompression.compress
+    python tools/ply_codec.py decompress DIR OUT.ply [--codec png|hevc]      the codec's decompress, then save_ply
 
-A thin script over the two APIs (gscodec_studio_amd.utils.load_ply / save_ply, gscodec_studio_amd.compression.PngCompression):
-the codec drops splats below its opacity threshold and crops to a square count, as it does for a trainer's splats.
+A thin script over the APIs (gscodec_studio_amd.utils.load_ply / save_ply, gscodec_studio_amd.compression.PngCompression /
+HevcCompression): the codec drops splats below its opacity threshold and crops to a square count, as it does for a trainer's splats.
+``--codec hevc`` is the lossy one: ``--qp`` (0..51, default 4) trades bytes for quality.
 """
 import argparse
 import os
@@ -21,20 +23,28 @@ def main(argv=None) -> int:
     c.add_argument("ply")
     c.add_argument("dir")
     c.add_argument("--sort", choices=("morton", "grid", "none"), default="morton")
+    c.add_argument("--codec", choices=("png", "hevc"), default="png")
+    c.add_argument("--qp", type=int, default=4, help="quantisation parameter of --codec hevc, 0..51")
     d = sub.add_parser("decompress")
     d.add_argument("dir")
     d.add_argument("ply")
+    d.add_argument("--codec", choices=("png", "hevc"), default="png")
     args = ap.parse_args(argv)
 
-    from gscodec_studio_amd.compression import PngCompression
+    from gscodec_studio_amd.compression import HevcCompression, PngCompression
     from gscodec_studio_amd.utils import load_ply, save_ply
 
     if args.command == "compress":
+        if not 0 <= args.qp <= 51:
+            ap.error("--qp must lie in 0..51")
+        sort = False if args.sort == "none" else args.sort
+        codec = HevcCompression(use_sort=sort, verbose=False, qp=args.qp) if args.codec == "hevc" else PngCompression(use_sort=sort, verbose=False)
         splats = load_ply(args.ply)
-        PngCompression(use_sort=False if args.sort == "none" else args.sort, verbose=False).compress(args.dir, dict(splats.items()))
+        codec.compress(args.dir, dict(splats.items()))
         print(f"{args.ply}: {splats['means'].shape[0]} splats -> {args.dir}")
     else:
-        splats = PngCompression(verbose=False).decompress(args.dir)
+        codec = HevcCompression(verbose=False) if args.codec == "hevc" else PngCompression(verbose=False)
+        splats = codec.decompress(args.dir)
         save_ply(splats, args.ply)
         print(f"{args.dir}: {splats['means'].shape[0]} splats -> {args.ply}")
     return 0
