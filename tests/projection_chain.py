@@ -7,8 +7,13 @@ Every floating-point piece already lives in ``oracle/``: ``gs_oracle.projection_
 in float32 and once in float64 from the same source), ``unfused_oracle.temporal_slice`` (torch) and ``gs_oracle.quant_round_fwd``.
 ``chain(bits, ...)`` strings them together in ``bits`` = 64 (the ground truth) or 32 (the reference's own arithmetic: the yardstick for
 how far ANY float32 evaluation is from the truth) from the same float32 inputs; what is hand-written here -- the opacity / compensation
-product rule, the per-camera sums, the clamp gate of the SH colours, the view-direction gradient added to ``v_means``, the activations and
-the straight-through quantizer in front of the slice -- is held against central differences by tests/test_projection_chain_cpu.py."""
+product rule, the per-camera sums, the clamp gate of the SH colours, the view-direction gradient added to ``v_means`` (and, with
+``need_viewmats``, carried through the camera centre ``inverse(viewmats)[:, :3, 3]`` into ``v_viewmats``), the activations and the
+straight-through quantizer in front of the slice -- is held against central differences by tests/test_projection_chain_cpu.py.
+
+One deliberate deviation from the reference's autograd: ``torch.inverse``'s backward, ``-inv^T G inv^T``, also puts a gradient on the bottom
+row of ``viewmats`` (the camera centre times the centre's cotangent).  That row is the constant (0, 0, 0, 1) of a world-to-camera matrix; the
+chain takes rows 0..2 of the same expression and leaves the bottom row of ``v_viewmats`` zero, as ``O.projection_bwd`` and the kernels do."""
 from __future__ import annotations
 
 import numpy as np
@@ -132,6 +137,13 @@ def chain(bits, P, viewmats, Ks, width, height, camera_model="pinhole", antialia
             v_coeffs, v_dirs = O.sh_bwd(sh_degree, dirs, coeffs, np.ascontiguousarray(v_col), masks=vis)
             v_sliced["sh"] = v_coeffs.sum(0)
             v_means = v_means + v_dirs.sum(0)  # dirs = means - campos
+            if need_viewmats:
+                # campos = inverse(viewmats)[:, :3, 3] and d inverse = -inverse dV inverse (float64, as the inverse itself), rows 0..2:
+                # the bottom row of a world-to-camera matrix is the constant (0, 0, 0, 1)
+                inv = np.linalg.inv(np.asarray(viewmats, np.float64))
+                v_campos = -v_dirs.sum(1).astype(np.float64)
+                v_view = v_view.copy()
+                v_view[:, :3] += (-np.einsum("cai,ca,cj->cij", inv[:, :3, :3], v_campos, inv[:, :, 3])).astype(f)
         elif "colors" in s:
             v_sliced["colors"] = z("colors", (C, N, 3)).sum(0)
     v_sliced["means"] = v_means

@@ -1,110 +1,93 @@
-"""Which native entry points one ``rasterization()`` forward + ``loss.backward()`` goes through, per call shape: the routes
-(step driver, splat rows through the operators, packed COO, fused / detoured dynamic slice, split / concatenated / masked SH
-pair, the four SH evaluations) are host-side decisions, and the sequence of entry-point names is what they decide.  The table
-below was recorded with this test body on the commit before the route decision moved into ``_route.py``."""
+"""``rasterization()`` forward + ``loss.backward()`` per call shape, over one table of 54 shapes: WHICH native entry points it goes through and
+WHAT it computes.
+
+The routes (step driver, splat rows through the operators, packed COO, fused / detoured dynamic slice, split / concatenated / masked SH
+pair, the four SH evaluations) are host-side decisions.  ``test_native_call_sequence`` holds the sequence of entry-point names they decide
+(the table below was recorded with that test body on the commit before the route decision moved into ``_route.py``).
+``test_route_values_against_float64`` holds the numbers: the image, the alphas, the projection outputs, the binning and every gradient of
+the same run against tests/render_chain.py, the whole call evaluated on the CPU in float64 -- so that a route which reads the wrong buffer,
+hands a cotangent to the wrong place, takes the wrong per-camera sum or renders the wrong channel as the depth fails, whatever its
+kernels are called.  Both tests share one GPU run per case (``run_case`` is cached), and every case runs as it is: no extra determinism
+switch, so that the path checked is the path used.
+
+The bar is the one of tests/test_gpu_surfel.py: per quantity relative L2 against float64 <= max(1e-4, 4 e32), where e32 is the relative L2
+of the SAME chain evaluated in float32 on the CPU against its float64 run -- what float32 arithmetic alone does to that quantity -- and the
+factor 4 covers summation order and the hardware ``exp``; the forward outputs (image, alphas, ``means2d``, ``depths``, ``conics``) also largest entry error <= max(1e-4, 4 m32) of the largest
+float64 entry.  Pixels where a compositing decision lies within a few ulp of flipping in either build get zero weight in the loss on both
+sides -- the 0.5 x alphas term included, which a flipped decision moves like the image -- and are left out of the forward comparison (at most 2 %: tests/test_render_chain_cpu.py, which also holds identical radii of the two
+builds and no SH colour at its clamp, for all 54 cases, on the reference alone).  ``radii`` equal the chain's; the binning equals the
+oracle's on the call's own projection, bit for bit; rows of splats no camera sees are exactly zero; a tensor whose float64 gradient is
+identically zero is zero or ``None``.  Every case prints one line per quantity with ``pytest -s``; the MI355X run is
+profiles/routes_parity.txt.  Every case is expressed by the chain; none is held against a sibling instead.
+
+Measured on the MI355X: on this scene the float32 chain is within 1.5e-5 of float64 in every quantity of every case (worst: ``means2d`` gradient
+of the ED modes), so NO quantity rides on ``4 e32``: every bar of the table is the fixed 1e-4.  The kernels' worst is 1.7e-5 (the same
+gradient, ratio 0.17); the image is within 9.5e-7 in relative L2 and 6.7e-6 in its largest entry (896 rows: 540 forward, 356 gradients).  Mutations that each failed value tests while every call sequence still passed: the
+depth swapped with the blue channel in the packed RGB+D mode (``render`` and every gradient of packed-RGB+D), the SH gradient's sum over
+cameras dropped (``colors`` / ``sh0`` / ``shN`` / ``mask_logits`` gradients of the two C = 2 shared-SH cases, 0.4 ... 0.6), the SH direction term left
+out of ``v_means`` (``means`` gradient of 18 SH cases, 2e-3 ... 2e-2), the packed tile lists in gaussian order (``flatten_ids``, ``render``).
+"""
+import functools
+import math
+
+import numpy as np
 import pytest
 import torch
 
-from util import T, garden, garden_sh
+from oracle import gs_oracle as O
+from render_chain import CASES, HEIGHT, N_SPLATS, WIDTH, render_chain, route_scene
+from util import N, T, rel_l2
 
 pytestmark = pytest.mark.gpu
 
-N_SPLATS, WIDTH, HEIGHT = 300, 48, 32  # two projection blocks; 3 x 2 tiles of 16 pixels
-MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")
-
-# colors: n3 / n5 [N,D] | cn3 [C,N,3] | sh [N,K,3] | csh [C,N,K,3] | pair (sh0, shN) | mask (sh0, MaskedShN) | mask_view (its shN a
-# misaligned view); patch: {(module, attribute): value} for the duration of the call
-CASES = {
-    **{f"rows-{m}": dict(colors="n3", render_mode=m) for m in MODES},
-    **{f"packed-{m}": dict(colors="n3", render_mode=m, packed=True) for m in MODES},
-    "rows-n5": dict(colors="n5"),
-    "rows-cn3": dict(colors="cn3", C=2),
-    "packed-n5": dict(colors="n5", packed=True),
-    "packed-cn3": dict(colors="cn3", C=2, packed=True),
-    **{f"rows-sh{K}": dict(colors="sh", K=K) for K in (4, 9, 16)},
-    **{f"rows-csh{K}": dict(colors="csh", K=K, C=2) for K in (4, 9, 16)},
-    **{f"rows-pair{K}": dict(colors="pair", K=K) for K in (4, 9, 16)},
-    "packed-sh16": dict(colors="sh", K=16, packed=True),
-    "packed-csh16": dict(colors="csh", K=16, C=2, packed=True),
-    "packed-pair16": dict(colors="pair", K=16, packed=True),
-    "mask4": dict(colors="mask", K=4),
-    "mask9": dict(colors="mask", K=9),
-    "mask16": dict(colors="mask", K=16),
-    "mask16-view": dict(colors="mask_view", K=16),
-    "mask16-C2": dict(colors="mask", K=16, C=2, render_mode="RGB+D"),
-    "packed-sparse_grad": dict(colors="n3", packed=True, sparse_grad=True),
-    "covars": dict(colors="sh", K=16, covars=True),
-    "pose-sh16": dict(colors="sh", K=16, pose_grads=True),
-    "pose-pair16": dict(colors="pair", K=16, pose_grads=True),
-    "pose-n3": dict(colors="n3", pose_grads=True),
-    "antialiased-sh16": dict(colors="sh", K=16, antialiased=True),
-    "antialiased-packed": dict(colors="sh", K=16, antialiased=True, packed=True),
-    "absgrad": dict(colors="sh", K=16, absgrad=True),
-    "deterministic": dict(colors="n3", deterministic=True),
-    "channel_chunk2": dict(colors="n3", channel_chunk=2),
-    "tile32": dict(colors="sh", K=16, tile_size=32),
-    "rows-sh16-RGB+ED-C2": dict(colors="sh", K=16, C=2, render_mode="RGB+ED"),
-    "dynamic-fused": dict(colors="n3", dynamic="plain"),
-    "dynamic-fused-qcolors": dict(colors="n3", dynamic="qcolors"),
-    "dynamic-detour-qcolors-n5": dict(colors="n5", dynamic="qcolors"),
-    "dynamic-detour-sh16": dict(colors="sh", K=16, dynamic="plain"),
-    "step-off-sh16": dict(colors="sh", K=16, patch={("_step", "ENABLED"): False}),
-    "step-off-n3": dict(colors="n3", patch={("_step", "ENABLED"): False}),
-    "two-launch-sh-bwd": dict(colors="sh", K=16, patch={("_wrapper", "_FUSE_SH_BWD"): False}),
-    "two-launch-sh-bwd-mask16": dict(colors="mask", K=16, patch={("_wrapper", "_FUSE_SH_BWD"): False}),
-    "prefill-off": dict(colors="sh", K=16, patch={("_wrapper", "PREFILL_ENABLED"): False}),
-    "prefill-off-operators": dict(colors="sh", K=16, patch={("_wrapper", "PREFILL_ENABLED"): False, ("_step", "ENABLED"): False}),
-    "pinned-direct-max-0": dict(colors="sh", K=16, patch={("_readback", "_PINNED_DIRECT_MAX"): 0}),
-}
+@functools.lru_cache(maxsize=None)
+def _reference(key):
+    """-> (scene, bool [C,H,W]: the pixels where neither build of the chain has a compositing decision near its threshold); one evaluation
+    per set of inputs (``key``: the options of a case that choose an input, as sorted items), shared by ``run_case`` and the value test."""
+    case = dict(key)
+    scene = route_scene(**case)
+    o32, _ = render_chain(32, case, scene=scene)
+    o64, _ = render_chain(64, case, scene=scene)
+    return scene, ~(o32["borderline"] | o64["borderline"])
 
 
+_INPUT_KEYS = ("colors", "K", "C", "render_mode", "covars", "pose_grads", "antialiased", "tile_size", "dynamic", "packed")
+_DEFAULTS = dict(K=None, C=1, render_mode="RGB", covars=False, pose_grads=False, antialiased=False, tile_size=16, dynamic=None, packed=False)
+
+
+def _input_key(case):
+    return tuple((k, case.get(k, _DEFAULTS.get(k))) for k in _INPUT_KEYS)
+
+
+def _cached(fn):
+    memo = {}
+
+    @functools.wraps(fn)
+    def wrapper(*a, **kw):
+        key = repr((a, sorted(kw.items())))
+        if key not in memo:
+            memo[key] = fn(*a, **kw)
+        return memo[key]
+    return wrapper
+
+
+@_cached
 def run_case(colors, K=None, C=1, render_mode="RGB", packed=False, sparse_grad=False, covars=False, pose_grads=False, antialiased=False,
              absgrad=False, deterministic=False, channel_chunk=32, tile_size=16, dynamic=None, patch=None):
-    """-> (entry-point names, render, alphas, meta, {name: gradient})"""
+    """-> (entry-point names, render, alphas, meta, {name: gradient}); one GPU run per call shape, shared by the tests of this module.
+    The loss is (render * weights).sum() + 0.5 * alphas.sum() over the pixels that are not borderline."""
     import gscodec_studio_amd as G
     from gscodec_studio_amd import _backend, _readback, _step, _wrapper
     from gscodec_studio_amd.compression_simulation.ada_mask import MaskedShN
     from gscodec_studio_amd.dynamic import DynamicSlice
 
-    g = garden(N_SPLATS, scale_mult=4.0)
+    S, ok = _reference(_input_key(dict(colors=colors, K=K, C=C, render_mode=render_mode, covars=covars, pose_grads=pose_grads,
+                                       antialiased=antialiased, tile_size=tile_size, dynamic=dynamic, packed=packed)))
     n = N_SPLATS
-    gen = torch.Generator(device="cuda:0").manual_seed(3)
-
-    def R(*shape):
-        return torch.rand(shape, device="cuda:0", generator=gen)
-
-    P = {"means": T(g["means"]), "opacities": T(g["opacities"])}
-    if covars:
-        c6, _ = _wrapper.quat_scale_to_covar_preci(T(g["quats"]), T(g["scales"]), compute_preci=False, triu=False)
-        P["covars"] = c6.detach().clone()
-    else:
-        P["quats"], P["scales"] = T(g["quats"]), T(g["scales"])
-    sh = garden_sh(g["rgb"], K=K) if K else None
-    if colors == "n3":
-        P["colors"] = T(g["rgb"])
-    elif colors == "n5":
-        P["colors"] = torch.cat([T(g["rgb"]), R(n, 2)], dim=1)
-    elif colors == "cn3":
-        P["colors"] = T(g["rgb"])[None].repeat(C, 1, 1) * R(C, 1, 1)
-    elif colors == "sh":
-        P["colors"] = T(sh)
-    elif colors == "csh":
-        P["colors"] = T(sh)[None].repeat(C, 1, 1, 1)
-    else:
-        P["sh0"] = T(sh[:, :1])
-        P["shN"] = torch.cat([R(1), T(sh[:, 1:]).reshape(-1)]) if colors == "mask_view" else T(sh[:, 1:])
-        if colors != "pair":
-            P["mask_logits"] = (R(n, 1, 1) - 0.5) * 4
+    P = {k: T(v) for k, v in S["P"].items()}
+    vm = P["viewmats"] if pose_grads else T(S["viewmats"])
+    Ks = T(S["Ks"])
     dyn = None
-    if dynamic:
-        P.update(motion=0.02 * (R(n, 9) - 0.5), omega=0.1 * (R(n, 4) - 0.5), trbf_center=R(n, 1), trbf_scale=R(n, 1) + 0.5)
-    vm = T(g["viewmats"][:C])
-    Ks = g["Ks"][:C].copy()
-    Ks[:, 0] *= WIDTH / g["width"]
-    Ks[:, 1] *= HEIGHT / g["height"]
-    Ks = T(Ks)
-    if pose_grads:
-        P["viewmats"] = vm
     for p in P.values():
         p.requires_grad_(True)
     if dynamic:
@@ -135,8 +118,9 @@ def run_case(colors, K=None, C=1, render_mode="RGB", packed=False, sparse_grad=F
             rasterize_mode="antialiased" if antialiased else "classic", deterministic=deterministic, channel_chunk=channel_chunk,
             tile_size=tile_size, dynamic=dyn)
         meta["means2d"].retain_grad()
-        weights = torch.rand(rc.shape, device="cuda:0", generator=gen)
-        ((rc * weights).sum() + 0.5 * ra.sum()).backward()
+        weights, mask = T(S["weights"] * ok[..., None]), T(ok[..., None].astype(np.float32))
+        assert rc.shape == weights.shape, (rc.shape, weights.shape)
+        ((rc * weights).sum() + 0.5 * (ra * mask).sum()).backward()
         torch.cuda.synchronize()
     finally:
         for k, v in saved.items():
@@ -326,3 +310,103 @@ def test_native_call_sequence(name):
     assert calls == EXPECTED[name].split()
     assert meta["flatten_ids"].numel() > 0 and float(ra.max()) > 0  # (the scene is visible: every stage had work)
     assert grads["means"] is not None and all(bool(torch.isfinite(v).all()) for v in grads.values() if v is not None)
+
+
+def _bar(e32):
+    return max(1e-4, 4.0 * e32)
+
+
+def _dense(meta, key, C):
+    """A projection output of the call as numpy [C,N,...]: packed routes scatter their (camera_ids, gaussian_ids) form."""
+    v = N(meta[key]) if torch.is_tensor(meta[key]) else np.asarray(meta[key])
+    if meta["camera_ids"] is None:
+        return v
+    out = np.zeros((C, N_SPLATS) + v.shape[1:], v.dtype)
+    out[N(meta["camera_ids"]), N(meta["gaussian_ids"])] = v
+    return out
+
+
+def _per_splat(colors, key, g):
+    """A gradient as [N, ...] rows, one per splat (None: not a per-splat tensor)."""
+    if key in ("viewmats", "backgrounds", "means2d", "absgrad"):
+        return None
+    if key == "colors" and colors in ("cn3", "csh"):
+        return np.moveaxis(g, 0, 1)
+    if key == "shN" and colors == "mask_view":
+        return g[1:].reshape(N_SPLATS, -1)
+    return g
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_route_values_against_float64(name):
+    case = CASES[name]
+    calls, rc, ra, meta, grads = run_case(**case)
+    S, ok = _reference(_input_key(case))
+    print()  # (the table starts on a line of its own, not behind pytest's progress dot)
+    C, ts = S["viewmats"].shape[0], case.get("tile_size", 16)
+    w = S["weights"] * ok[..., None]
+    a = 0.5 * ok[..., None]
+    o64, g64 = render_chain(64, case, cot=dict(render=w, alphas=a), scene=S)
+    o32, g32 = render_chain(32, case, cot=dict(render=w, alphas=a.astype(np.float32)), scene=S)
+    rows, failures = [], []
+
+    def hold(quantity, hip, f32, f64, max_norm=False):
+        hip, f32, f64 = (np.asarray(v, np.float64) for v in (hip, f32, f64))
+        assert hip.shape == f64.shape, (quantity, hip.shape, f64.shape)
+        checks = [("l2", rel_l2(hip, f64), _bar(rel_l2(f32, f64)))]
+        if max_norm:
+            top = np.abs(f64).max()
+            checks.append(("max", np.abs(hip - f64).max() / top, _bar(np.abs(f32 - f64).max() / top)))
+        for kind, err, bar in checks:
+            row = f"[routes] {name:28s} {quantity:18s} {kind:3s} err {err:.3e}  bar {bar:.3e}  ratio {err / bar:.3f}"
+            print(row)
+            rows.append(row)
+            if not err <= bar:
+                failures.append(row)
+
+    # ---- forward: the image and the alphas where not borderline
+    m = ok[..., None]
+    assert tuple(rc.shape) == o64["render"].shape and tuple(ra.shape) == o64["alphas"].shape
+    hold("render", N(rc) * m, o32["render"] * m, o64["render"] * m, max_norm=True)
+    hold("alphas", N(ra) * m, o32["alphas"] * m, o64["alphas"] * m, max_norm=True)
+
+    # ---- the projection where visible
+    radii = _dense(meta, "radii", C)
+    assert np.array_equal(radii, o64["radii"]) and np.array_equal(o32["radii"], o64["radii"]), "radii differ from the chain's"
+    vis = radii > 0
+    for k in ("means2d", "depths", "conics"):
+        v = _dense(meta, k, C)
+        sel = vis.reshape(vis.shape + (1,) * (v.ndim - 2))
+        hold(k, np.where(sel, v, 0), np.where(sel, o32[k], 0), np.where(sel, o64[k], 0), max_norm=True)
+
+    # ---- the binning, bit for bit, on the call's own projection
+    tw, th = math.ceil(WIDTH / ts), math.ceil(HEIGHT / ts)
+    packed = meta["camera_ids"] is not None
+    o_tpg, o_ids, o_flat = O.isect_tiles(N(meta["means2d"]), N(meta["radii"]), N(meta["depths"]), ts, tw, th, n_cameras=C,
+                                         camera_ids=N(meta["camera_ids"]) if packed else None)
+    assert np.array_equal(N(meta["tiles_per_gauss"]), o_tpg), "tiles_per_gauss"
+    assert np.array_equal(N(meta["flatten_ids"]), o_flat), "flatten_ids"
+    assert np.array_equal(N(meta["isect_offsets"]), O.isect_offset_encode(o_ids, C, tw, th)), "isect_offsets"
+
+    # ---- every gradient
+    assert set(S["P"]) <= set(grads) and set(S["P"]) <= set(g64)
+    unseen = ~vis.any(0)
+    assert unseen.any() and not unseen.all()
+    for k in list(S["P"]) + ["means2d"] + (["absgrad"] if case.get("absgrad") else []):
+        h = grads[k]
+        if not g64[k].any():  # (colours in a depth-only mode)
+            assert h is None or not bool(h.any()), (k, "the float64 gradient is identically zero")
+            continue
+        assert h is not None, k
+        h = _dense({**meta, k: h}, k, C) if k in ("means2d", "absgrad") else N(h)
+        a32, a64 = g32[k], g64[k]
+        if k == "viewmats":
+            assert not h[:, 3].any(), "the bottom row of v_viewmats stays zero"
+            h, a32, a64 = h[:, :3], a32[:, :3], a64[:, :3]
+        if k in ("means2d", "absgrad"):
+            assert not h[~vis].any(), (k, "entries of pairs that are not visible are exactly zero")
+        per = _per_splat(case["colors"], k, h)
+        if per is not None:
+            assert not per[unseen].any(), (k, "rows of splats no camera sees are exactly zero")
+        hold("grad " + k, h, a32, a64)
+    assert not failures, "\n".join(failures)

@@ -100,3 +100,38 @@ def test_chain_float32_run_is_close_to_its_float64_run():
     for k in g64:
         assert g32[k].dtype == np.float32 and g64[k].dtype == np.float64
         assert np.linalg.norm(g32[k] - g64[k]) <= 1e-4 * np.linalg.norm(g64[k]), k
+
+
+@pytest.mark.parametrize("sh", [False, True], ids=["colors", "sh2"])
+def test_chain_pose_gradient_equals_central_differences(sh):
+    """``v_viewmats``: the projection's own, and with SH colours the view direction's dependence on the camera centre on top of it."""
+    P, vm, Ks, _ = _scene(sh, False)
+    kw = dict(sh_degree=2 if sh else None, need_viewmats=True)
+    out, _ = chain(64, P, vm, Ks, W, H, **kw)
+    vis = out["radii"] > 0
+    assert vis.all()
+    rs = np.random.RandomState(11)
+    names = ("means2d", "depths", "conics", "opacities", "colors")
+    cot = {k: rs.randn(*out[k].shape) for k in names}
+    _, grads = chain(64, P, vm, Ks, W, H, cot=cot, vis=vis, **kw)
+    g = grads["viewmats"]
+    assert g.shape == vm.shape and not g[:, 3].any(), "the bottom row of a world-to-camera matrix is constant"
+    if sh:  # the centre term is there: the colours' cotangent alone reaches the pose
+        _, only = chain(64, P, vm, Ks, W, H, cot={"colors": cot["colors"]}, vis=vis, **kw)
+        assert np.abs(only["viewmats"]).max() > 1e-3 * np.abs(g).max()
+
+    def fd(idx, h):
+        lo, hi = vm.copy(), vm.copy()
+        lo[idx] -= h
+        hi[idx] += h
+        val = []
+        for m in (hi, lo):
+            o, _ = chain(64, P, m, Ks, W, H, **kw)
+            assert np.array_equal(o["radii"] > 0, vis)
+            val.append(sum(float((cot[k] * o[k]).sum()) for k in names))
+        return (val[0] - val[1]) / (2 * h)
+
+    h = 1e-3
+    for idx in np.ndindex(vm.shape[0], 3, 4):
+        d1, d2 = fd(idx, h), fd(idx, h / 2)
+        assert abs(g[idx] - d2) <= 4 * abs(d1 - d2) + 1e-9 * np.abs(g).max(), (idx, g[idx], d1, d2)
