@@ -13,7 +13,14 @@ What is hand-written here is the glue the routes decide about, held against cent
 colours that are not the chain's ``[N,3]`` / ``[N,K,3]`` (``[N,5]``, per-camera ``[C,N,3]`` without a camera sum in the VJP, per-camera SH
 ``[C,N,K,3]``), the ``(sh0, shN)`` pair as two slices of one gradient, the soft mask in front of ``shN`` with its VJP to ``shN`` and the logits,
 the depth as last channel, ``ED`` = last / max(alphas, 1e-10) with its VJP into the accumulated depth and the alphas, the backgrounds,
-covariances as ``[N,3,3]``, the quantizer in front of ``[N,5]`` colours, and the misaligned ``shN`` view."""
+covariances as ``[N,3,3]``, the quantizer in front of ``[N,5]`` colours, the misaligned ``shN`` view, an ``sh_degree`` below the bands of K
+and the call options handed on to ``chain``.
+
+The table has two parts.  54 cases choose a route with every argument at its default.  41 more (``BASE`` names the case each is derived
+from) change what no route decision reads and every route has to carry: the keys ``camera_model``, ``near_plane``, ``far_plane``,
+``radius_clip``, ``eps2d`` (the call's and ``chain``'s), ``backgrounds=True`` (``route_scene`` adds a ``[C,D]`` array, drawn after everything
+else, so that no other array moves), ``deg`` (the call's ``sh_degree`` where it is below ``int(sqrt(K)) - 1``) and ``sh_scale`` (multiplies
+the SH coefficients of bands >= 1).  Every default is the behaviour without the key: the inputs of the 54 are bit for bit what they were."""
 from __future__ import annotations
 
 import math
@@ -80,6 +87,59 @@ CASES = {
     "pinned-direct-max-0": dict(colors="sh", K=16, patch={("_readback", "_PINNED_DIRECT_MAX"): 0}),
 }
 
+# ---- the call options, partial SH bands and clamped colours: a case of the table above (its BASE) with keys changed.  No option may
+# change the route: tests/test_gpu_routes.test_native_call_sequence holds each of these to the recorded sequence of its base.
+#   camera_model, near_plane, far_plane, radius_clip, eps2d   the call's; the chain's
+#   backgrounds=True   a [C,D] leaf for the colour channels (zero on a depth channel), with its gradient
+#   deg                the call's ``sh_degree`` where it is below the bands of K: the gradient of the bands above it is identically zero
+#   sh_scale           multiplies the coefficients of bands >= 1: 6.0 gives std 0.3, which puts 5 ... 50 % of the visible colours below the clamp
+# The values are those at which both builds of the chain agree on every radius, no colour lies within GATE_EPS of its clamp and at
+# most 2 % of the pixels are borderline, and at which the option bites (tests/test_render_chain_cpu.py asserts all of it).
+_NEAR_FAR = dict(near_plane=1.0, far_plane=3.0)
+_COMBINED = dict(camera_model="fisheye", radius_clip=3.0, eps2d=0.1, backgrounds=True, **_NEAR_FAR)
+_OPTIONS = {"ortho": dict(camera_model="ortho"), "fisheye": dict(camera_model="fisheye"), "nearfar": _NEAR_FAR,
+            "radius_clip": dict(radius_clip=3.0), "eps2d": dict(eps2d=0.1), "bg": dict(backgrounds=True)}
+_DERIVED = {
+    # step driver, SH
+    **{f"step-sh16-{o}": ("rows-sh16", v) for o, v in _OPTIONS.items()},
+    "step-sh16-tile8": ("rows-sh16", dict(tile_size=8)),
+    "step-sh16-aa-ortho-eps2d": ("antialiased-sh16", dict(camera_model="ortho", eps2d=0.1)),  # (the compensation depends on eps2d)
+    # step driver, [N,3] colours
+    **{f"step-n3-{o}": ("rows-RGB", _OPTIONS[o]) for o in ("fisheye", "nearfar", "bg")},
+    # every option together, through the operators (a depth channel, whose background is zero; the pair with the step driver off)
+    "combined-sh16-RGB+ED-C2": ("rows-sh16-RGB+ED-C2", _COMBINED),
+    "combined-pair16": ("step-off-sh16", dict(colors="pair", **_COMBINED)),
+    "combined-mask16-C2": ("mask16-C2", _COMBINED),
+    # packed
+    **{f"packed-sh16-{o}": ("packed-sh16", v) for o, v in _OPTIONS.items()},
+    "packed-RGB+D-bg": ("packed-RGB+D", dict(backgrounds=True)),
+    # the dynamic kernels
+    "dynamic-fused-fisheye": ("dynamic-fused", dict(camera_model="fisheye")),
+    "dynamic-fused-nearfar-clip": ("dynamic-fused", dict(radius_clip=3.0, **_NEAR_FAR)),
+    "dynamic-fused-bg": ("dynamic-fused", dict(backgrounds=True)),
+    # partial bands of K = 16
+    **{f"step-sh16-deg{d}": ("rows-sh16", dict(deg=d)) for d in (0, 1, 2)},
+    "pair16-deg1": ("rows-pair16", dict(deg=1)),
+    "mask16-deg2": ("mask16", dict(deg=2)),
+    "packed-sh16-deg1": ("packed-sh16", dict(deg=1)),
+    "csh16-deg2": ("rows-csh16", dict(deg=2)),
+    "two-launch-sh-bwd-deg1": ("two-launch-sh-bwd", dict(deg=1)),
+    "step-off-sh16-deg0": ("step-off-sh16", dict(deg=0)),
+    # colours below the clamp
+    "clamp-sh16": ("rows-sh16", dict(sh_scale=6.0)),
+    "clamp-sh16-C2": ("rows-sh16", dict(sh_scale=6.0, C=2)),  # (the camera sum of a gated gradient)
+    "clamp-pair16": ("rows-pair16", dict(sh_scale=6.0)),
+    "clamp-mask16": ("mask16", dict(sh_scale=7.0)),  # (at 6.0 the mask leaves one colour 5.8e-5 from its clamp; at 7.0 the nearest is 3.2e-3)
+    "clamp-packed-sh16": ("packed-sh16", dict(sh_scale=6.0)),
+    "clamp-csh16": ("rows-csh16", dict(sh_scale=6.0)),
+    "clamp-sh16-deg1": ("rows-sh16", dict(sh_scale=6.0, deg=1)),
+    "clamp-two-launch-sh-bwd": ("two-launch-sh-bwd", dict(sh_scale=6.0)),
+}
+OLD_CASES = tuple(CASES)
+BASE = {name: base for name, (base, _) in _DERIVED.items()}
+CASES.update({name: {**CASES[base], **changes} for name, (base, changes) in _DERIVED.items()})
+CHAIN_OPTIONS = dict(camera_model="pinhole", eps2d=0.3, near_plane=0.01, far_plane=1e10, radius_clip=0.0)  # (and their defaults)
+
 
 def channels(colors, render_mode="RGB"):
     """Channels of the rendered image of a case."""
@@ -87,9 +147,29 @@ def channels(colors, render_mode="RGB"):
     return 1 if render_mode in _DEPTH_ONLY else d + (render_mode in _WITH_DEPTH)
 
 
-def route_scene(colors, K=None, C=1, render_mode="RGB", covars=False, pose_grads=False, dynamic=None, **_):
-    """The float32 numbers of one case of the routes table (the remaining options of a case choose a route, not an input):
-    -> dict(P: the differentiable inputs by ``run_case``'s names, viewmats, Ks, weights [C,H,W,X] of the loss, width, height)."""
+def sh_degree_of(case):
+    """The ``sh_degree`` of a case's call (None without SH): every band of K unless ``deg`` says less."""
+    if not case.get("K"):
+        return None
+    full = int(case["K"] ** 0.5) - 1
+    deg = case.get("deg")
+    assert deg is None or 0 <= deg <= full, (deg, full)
+    return full if deg is None else deg
+
+
+def sh_band(colors, b):
+    """-> (name of the input that holds band ``b`` of the SH coefficients, the index of that band in it)."""
+    lo, hi = b * b, (b + 1) ** 2
+    if colors in ("sh", "csh"):
+        return "colors", (Ellipsis, slice(lo, hi), slice(None))
+    assert colors in ("pair", "mask"), colors
+    return ("sh0", (Ellipsis, slice(0, 1), slice(None))) if b == 0 else ("shN", (Ellipsis, slice(lo - 1, hi - 1), slice(None)))
+
+
+def route_scene(colors, K=None, C=1, render_mode="RGB", covars=False, pose_grads=False, dynamic=None, backgrounds=False, sh_scale=None, **_):
+    """The float32 numbers of one case of the routes table (the remaining options of a case choose a route or an argument, not an input):
+    -> dict(P: the differentiable inputs by ``run_case``'s names, viewmats, Ks, weights [C,H,W,X] of the loss, width, height, and with
+    ``backgrounds`` a [C,D] array for the colour channels).  ``sh_scale`` multiplies the SH coefficients of bands >= 1."""
     g = garden(N_SPLATS, scale_mult=4.0)
     n = N_SPLATS
     rs = np.random.RandomState(3)
@@ -110,6 +190,8 @@ def route_scene(colors, K=None, C=1, render_mode="RGB", covars=False, pose_grads
         P["quats"], P["scales"] = F(g["quats"]), F(g["scales"])
     # (black splats would sit ON the clamp of the SH colour at degree 0 and near it above: their DC coefficient is moved off it)
     sh = garden_sh(np.clip(g["rgb"], 0.05, 1.0), K=K) if K else None
+    if sh_scale is not None:
+        sh[:, 1:] *= np.float32(sh_scale)
     if colors == "n3":
         P["colors"] = F(g["rgb"])
     elif colors == "n5":
@@ -134,7 +216,10 @@ def route_scene(colors, K=None, C=1, render_mode="RGB", covars=False, pose_grads
     Ks[:, 1] *= HEIGHT / g["height"]
     if pose_grads:
         P["viewmats"] = vm
-    return dict(P=P, viewmats=vm, Ks=Ks, weights=R(C, HEIGHT, WIDTH, channels(colors, render_mode)), width=WIDTH, height=HEIGHT)
+    S = dict(P=P, viewmats=vm, Ks=Ks, weights=R(C, HEIGHT, WIDTH, channels(colors, render_mode)), width=WIDTH, height=HEIGHT)
+    if backgrounds:  # (drawn last: every other array is what it is without them)
+        S["backgrounds"] = R(C, 5 if colors == "n5" else 3)
+    return S
 
 
 def soft_mask(bits, logits):
@@ -149,8 +234,9 @@ def render_chain(bits, case, cot=None, scene=None):
     case    a row of the routes table (the keyword arguments of ``run_case``); ``scene`` replaces ``route_scene(**case)`` (a dict of the same
             form, optionally with ``backgrounds`` [C,D] for the colour channels, which then is a differentiable input too).
     -> (out, grads): ``out`` holds render, alphas, radii, means2d, depths, conics, opacities, tiles_per_gauss, flatten_ids, isect_offsets,
-    last_ids, ``borderline`` (bool [C,H,W]: a threshold decision of the compositing within a few ulp of flipping) and the SH ``gate`` of
-    ``chain``; ``grads`` (None without ``cot``) one array per entry of ``P`` (and ``backgrounds``) plus ``means2d`` and ``absgrad`` [C,N,2]."""
+    last_ids, ``borderline`` (bool [C,H,W]: a threshold decision of the compositing within a few ulp of flipping), the SH ``gate`` of
+    ``chain`` and ``sh_raw`` (the SH value before + 0.5 and the clamp; None without SH); ``grads`` (None without ``cot``) one array per
+    entry of ``P`` (and ``backgrounds``) plus ``means2d`` and ``absgrad`` [C,N,2]."""
     S = route_scene(**case) if scene is None else scene
     f = _np(bits)
     form, K, mode, ts = case["colors"], case.get("K"), case.get("render_mode", "RGB"), case.get("tile_size", 16)
@@ -158,7 +244,7 @@ def render_chain(bits, case, cot=None, scene=None):
     pose = "viewmats" in P
     vm = P["viewmats"] if pose else S["viewmats"]
     C, N = vm.shape[0], P["means"].shape[0]
-    deg = int(K ** 0.5) - 1 if K else None
+    deg = sh_degree_of(case)
 
     # ---- what the projection chain takes
     CP = {k: P[k] for k in ("means", "opacities", "quats", "scales") if k in P}
@@ -187,7 +273,8 @@ def render_chain(bits, case, cot=None, scene=None):
         assert form in ("n5", "cn3", "csh"), form
     assert not (pose and form == "csh"), "per-camera SH with pose gradients: not a case of the table"
     kw = dict(antialiased=bool(case.get("antialiased")), sh_degree=deg if "sh" in CP else None, dynamic=dyn, need_viewmats=pose,
-              packed_formula=bool(case.get("packed")))  # (the reference's packed projection has a radius formula of its own)
+              packed_formula=bool(case.get("packed")),  # (the reference's packed projection has a radius formula of its own)
+              **{k: case.get(k, v) for k, v in CHAIN_OPTIONS.items()})
     o, _ = chain(bits, CP, vm, Ks, W, H, **kw)
     seen = o["radii"] > 0
     gate = o["gate"]
@@ -209,7 +296,7 @@ def render_chain(bits, case, cot=None, scene=None):
         col = np.maximum(sh_raw + f(0.5), 0) * seen[..., None]
         gate = (np.abs(sh_raw + f(0.5)) <= GATE_EPS) & seen[..., None]
     else:
-        col = o["colors"]
+        col, sh_raw = o["colors"], o.get("sh_raw")
     col = np.ascontiguousarray(col, f)
     D = col.shape[-1]
 
@@ -235,7 +322,7 @@ def render_chain(bits, case, cot=None, scene=None):
     if mode in _EXPECTED:
         render = np.concatenate([rc[..., :-1], rc[..., -1:] / a_c], -1).astype(f)
     out = dict(render=render, alphas=ra, radii=o["radii"], means2d=o["means2d"], depths=o["depths"], conics=o["conics"], opacities=o["opacities"],
-               tiles_per_gauss=tpg, flatten_ids=flat, isect_offsets=offs, last_ids=li, borderline=bl != 0, gate=gate)
+               tiles_per_gauss=tpg, flatten_ids=flat, isect_offsets=offs, last_ids=li, borderline=bl != 0, gate=gate, sh_raw=sh_raw)
     if cot is None:
         return out, None
 

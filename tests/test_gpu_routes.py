@@ -1,5 +1,5 @@
-"""``rasterization()`` forward + ``loss.backward()`` per call shape, over one table of 54 shapes: WHICH native entry points it goes through and
-WHAT it computes.
+"""``rasterization()`` forward + ``loss.backward()`` per call shape, over one table of 95 shapes (54 that choose a route, 41 that hold the
+arguments every route has to carry): WHICH native entry points it goes through and WHAT it computes.
 
 The routes (step driver, splat rows through the operators, packed COO, fused / detoured dynamic slice, split / concatenated / masked SH
 pair, the four SH evaluations) are host-side decisions.  ``test_native_call_sequence`` holds the sequence of entry-point names they decide
@@ -15,7 +15,7 @@ of the SAME chain evaluated in float32 on the CPU against its float64 run -- wha
 factor 4 covers summation order and the hardware ``exp``; the forward outputs (image, alphas, ``means2d``, ``depths``, ``conics``) also largest entry error <= max(1e-4, 4 m32) of the largest
 float64 entry.  Pixels where a compositing decision lies within a few ulp of flipping in either build get zero weight in the loss on both
 sides -- the 0.5 x alphas term included, which a flipped decision moves like the image -- and are left out of the forward comparison (at most 2 %: tests/test_render_chain_cpu.py, which also holds identical radii of the two
-builds and no SH colour at its clamp, for all 54 cases, on the reference alone).  ``radii`` equal the chain's; the binning equals the
+builds and no SH colour at its clamp, for all 95 cases, on the reference alone).  ``radii`` equal the chain's; the binning equals the
 oracle's on the call's own projection, bit for bit; rows of splats no camera sees are exactly zero; a tensor whose float64 gradient is
 identically zero is zero or ``None``.  Every case prints one line per quantity with ``pytest -s``; the MI355X run is
 profiles/routes_parity.txt.  Every case is expressed by the chain; none is held against a sibling instead.
@@ -26,6 +26,30 @@ gradient, ratio 0.17); the image is within 9.5e-7 in relative L2 and 6.7e-6 in i
 depth swapped with the blue channel in the packed RGB+D mode (``render`` and every gradient of packed-RGB+D), the SH gradient's sum over
 cameras dropped (``colors`` / ``sh0`` / ``shN`` / ``mask_logits`` gradients of the two C = 2 shared-SH cases, 0.4 ... 0.6), the SH direction term left
 out of ``v_means`` (``means`` gradient of 18 SH cases, 2e-3 ... 2e-2), the packed tile lists in gaussian order (``flatten_ids``, ``render``).
+
+THE ARGUMENTS NO ROUTE DECISION READS.  ``_route.route()`` reads neither the camera model, the clip planes, ``radius_clip``, ``eps2d``, the
+backgrounds nor ``sh_degree``; each route carries them to its own kernels (the fields of ``gs_step``, the arguments of ``project_rows``, of
+the packed operators, of the dynamic kernels).  The 54 cases above hold all of them at their defaults, with every SH band active and hardly a
+colour below its clamp.  41 more cases (``render_chain.BASE``: each is a case of the 54, its base, with keys changed) vary them per route:
+``camera_model``, ``near_plane`` / ``far_plane``, ``radius_clip``, ``eps2d`` (to the call and to the chain), ``backgrounds`` (a ``[C,D]`` leaf whose
+gradient joins the comparison; zero on a depth channel), ``tile_size=8`` on the step driver, ``deg`` (``sh_degree`` below the bands of K = 16: the
+paths where the coefficient row is longer than the bands read -- the gradient of every band above it must be zero or ``None``, asserted band
+by band) and ``sh_scale`` (bands >= 1 times 6, which puts 6 ... 14 % of the visible colours below the clamp: the gate of the SH backward, which
+reads the forward's colours back at a stride that differs per route).  The bars are the table's own.  No option changes a route:
+``test_native_call_sequence`` holds each of the 41 to the recorded sequence of its base, and on the MI355X all 41 equal it.  That every
+option bites on this scene (pairs culled, radii and conics moved, colours clamped, a last active band with a gradient, a pixel that shows
+the background) is asserted on the reference alone by tests/test_render_chain_cpu.py::test_no_option_case_is_vacuous.
+
+Measured on the MI355X, the 41: 685 rows (410 forward, 275 gradients), the float32 chain within 2.5e-5 of float64 in every one of them, so NO new
+quantity rides on ``4 e32`` either: every bar is the fixed 1e-4.  Worst 1.0e-5 (``means2d`` gradient of combined-sh16-RGB+ED-C2, ratio 0.10);
+``grad backgrounds`` at most 5.8e-8.  Mutations, each on a copy of the tree, all 95 value tests run: the step driver entering pinhole whatever
+``camera_model`` says (``radii`` of the 5 step-driver ortho / fisheye cases; the 54 pass), ``radius_clip`` passed as 0 to the packed projection
+(``radii`` of packed-sh16-radius_clip; the 54 pass), the full degree in place of ``sh_degree`` in the step driver's forward (``render`` of 7 cases
+with ``deg``, 2.6e-2 ... 6.7e-2; the 54 pass), ``alpha`` in place of ``1 - alpha`` in the background gradient (``grad backgrounds`` of all 8
+backgrounds cases, 0.53 ... 0.77; the 54 pass), and the clamp gate of ``sh_bwd_lane`` removed: ``grad colors`` / ``sh0`` / ``shN`` / ``means`` of 18
+new cases (0.46 on clamp-sh16 against 0.14 on rows-sh16) -- and of 21 of the 54, whose degree-3 scene has 11 of 597 colours below the clamp;
+what the 54 do not see is the gate below degree 3 (step-sh16-deg0 / deg1 pass without it: no colour is clamped there), which
+clamp-sh16-deg1 closes.
 """
 import functools
 import math
@@ -35,7 +59,7 @@ import pytest
 import torch
 
 from oracle import gs_oracle as O
-from render_chain import CASES, HEIGHT, N_SPLATS, WIDTH, render_chain, route_scene
+from render_chain import BASE, CASES, CHAIN_OPTIONS, HEIGHT, N_SPLATS, WIDTH, render_chain, route_scene, sh_band, sh_degree_of
 from util import N, T, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -51,8 +75,10 @@ def _reference(key):
     return scene, ~(o32["borderline"] | o64["borderline"])
 
 
-_INPUT_KEYS = ("colors", "K", "C", "render_mode", "covars", "pose_grads", "antialiased", "tile_size", "dynamic", "packed")
-_DEFAULTS = dict(K=None, C=1, render_mode="RGB", covars=False, pose_grads=False, antialiased=False, tile_size=16, dynamic=None, packed=False)
+_INPUT_KEYS = ("colors", "K", "C", "render_mode", "covars", "pose_grads", "antialiased", "tile_size", "dynamic", "packed", "camera_model",
+               "near_plane", "far_plane", "radius_clip", "eps2d", "backgrounds", "deg", "sh_scale")
+_DEFAULTS = dict(K=None, C=1, render_mode="RGB", covars=False, pose_grads=False, antialiased=False, tile_size=16, dynamic=None, packed=False,
+                 backgrounds=False, deg=None, sh_scale=None, **CHAIN_OPTIONS)
 
 
 def _input_key(case):
@@ -73,7 +99,8 @@ def _cached(fn):
 
 @_cached
 def run_case(colors, K=None, C=1, render_mode="RGB", packed=False, sparse_grad=False, covars=False, pose_grads=False, antialiased=False,
-             absgrad=False, deterministic=False, channel_chunk=32, tile_size=16, dynamic=None, patch=None):
+             absgrad=False, deterministic=False, channel_chunk=32, tile_size=16, dynamic=None, patch=None, camera_model="pinhole",
+             near_plane=0.01, far_plane=1e10, radius_clip=0.0, eps2d=0.3, backgrounds=False, deg=None, sh_scale=None):
     """-> (entry-point names, render, alphas, meta, {name: gradient}); one GPU run per call shape, shared by the tests of this module.
     The loss is (render * weights).sum() + 0.5 * alphas.sum() over the pixels that are not borderline."""
     import gscodec_studio_amd as G
@@ -82,9 +109,13 @@ def run_case(colors, K=None, C=1, render_mode="RGB", packed=False, sparse_grad=F
     from gscodec_studio_amd.dynamic import DynamicSlice
 
     S, ok = _reference(_input_key(dict(colors=colors, K=K, C=C, render_mode=render_mode, covars=covars, pose_grads=pose_grads,
-                                       antialiased=antialiased, tile_size=tile_size, dynamic=dynamic, packed=packed)))
+                                       antialiased=antialiased, tile_size=tile_size, dynamic=dynamic, packed=packed,
+                                       camera_model=camera_model, near_plane=near_plane, far_plane=far_plane, radius_clip=radius_clip,
+                                       eps2d=eps2d, backgrounds=backgrounds, deg=deg, sh_scale=sh_scale)))
     n = N_SPLATS
     P = {k: T(v) for k, v in S["P"].items()}
+    if backgrounds:
+        P["backgrounds"] = T(S["backgrounds"])
     vm = P["viewmats"] if pose_grads else T(S["viewmats"])
     Ks = T(S["Ks"])
     dyn = None
@@ -113,10 +144,11 @@ def run_case(colors, K=None, C=1, render_mode="RGB", packed=False, sparse_grad=F
         for k, v in patches.items():
             setattr(mods[k[0]], k[1], v)
         rc, ra, meta = G.rasterization(
-            P["means"], P.get("quats"), P.get("scales"), P["opacities"], col, vm, Ks, WIDTH, HEIGHT, sh_degree=int(K ** 0.5) - 1 if K else None,
+            P["means"], P.get("quats"), P.get("scales"), P["opacities"], col, vm, Ks, WIDTH, HEIGHT, sh_degree=sh_degree_of(dict(K=K, deg=deg)),
             packed=packed, sparse_grad=sparse_grad, render_mode=render_mode, covars=P.get("covars"), absgrad=absgrad,
             rasterize_mode="antialiased" if antialiased else "classic", deterministic=deterministic, channel_chunk=channel_chunk,
-            tile_size=tile_size, dynamic=dyn)
+            tile_size=tile_size, dynamic=dyn, camera_model=camera_model, near_plane=near_plane, far_plane=far_plane, radius_clip=radius_clip,
+            eps2d=eps2d, backgrounds=P.get("backgrounds"))
         meta["means2d"].retain_grad()
         weights, mask = T(S["weights"] * ok[..., None]), T(ok[..., None].astype(np.float32))
         assert rc.shape == weights.shape, (rc.shape, weights.shape)
@@ -307,7 +339,7 @@ EXPECTED = {
 @pytest.mark.parametrize("name", list(CASES))
 def test_native_call_sequence(name):
     calls, rc, ra, meta, grads = run_case(**CASES[name])
-    assert calls == EXPECTED[name].split()
+    assert calls == EXPECTED[BASE.get(name, name)].split()  # (an option, a lower sh_degree or other coefficients change no route)
     assert meta["flatten_ids"].numel() > 0 and float(ra.max()) > 0  # (the scene is visible: every stage had work)
     assert grads["means"] is not None and all(bool(torch.isfinite(v).all()) for v in grads.values() if v is not None)
 
@@ -392,7 +424,12 @@ def test_route_values_against_float64(name):
     assert set(S["P"]) <= set(grads) and set(S["P"]) <= set(g64)
     unseen = ~vis.any(0)
     assert unseen.any() and not unseen.all()
-    for k in list(S["P"]) + ["means2d"] + (["absgrad"] if case.get("absgrad") else []):
+    if case.get("deg") is not None:  # the bands above sh_degree: identically zero in float64, so zero or None here, band by band
+        for b in range(case["deg"] + 1, int(case["K"] ** 0.5)):
+            k, idx = sh_band(case["colors"], b)
+            assert not g64[k][idx].any() and not g32[k][idx].any(), (k, b)
+            assert grads[k] is None or not N(grads[k])[idx].any(), (k, b, "the float64 gradient of this band is identically zero")
+    for k in list(S["P"]) + (["backgrounds"] if case.get("backgrounds") else []) + ["means2d"] + (["absgrad"] if case.get("absgrad") else []):
         h = grads[k]
         if not g64[k].any():  # (colours in a depth-only mode)
             assert h is None or not bool(h.any()), (k, "the float64 gradient is identically zero")

