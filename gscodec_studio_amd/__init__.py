@@ -18,7 +18,10 @@ Public surface (mirrors the reference's ``gsplat`` package for this path only):
   in place of ``from utils import knn``; exact grid k-NN on the GPU, ``init_scales`` is the three lines that size the initial splats),
   and ``.ply`` files in the INRIA 3DGS layout without plyfile: ``utils.{load_ply, save_ply, load_ply_to_rasterizer_inputs,
   read_ply_header}`` (``ply.py``, ``csrc/ply.hip``), with ``utils.{rgb_to_sh, set_random_seed}`` beside them, so that
-  ``from utils import knn, rgb_to_sh, set_random_seed, load_ply`` reads ``from gscodec_studio_amd.utils import ...``.
+  ``from utils import knn, rgb_to_sh, set_random_seed, load_ply`` reads ``from gscodec_studio_amd.utils import ...``,
+  and the file codecs of ``compression`` (``PngCompression``, ``EntropyCodingCompression``, ``HevcCompression``,
+  ``STGPngCompression`` and, for a sequence of splat dictionaries such as one ``.ply`` per frame, ``SeqHevcCompression``:
+  ``from gscodec_studio_amd.compression import SeqHevcCompression`` in place of ``from gsplat.compression.seq_hevc_compression import ...``).
 """
 from ._wrapper import (
     accumulate,

@@ -47,6 +47,14 @@
 * ``plane_codec``: ``plane_encode`` / ``plane_decode``, that payload on the GPU (csrc/plane_codec.hip: HEVC's 8 x 8 integer
   transform and flat quantiser with one lane per block, then the rANS streams over 15 static tables), defined by the numpy code
   ``plane_codec_reference`` that the kernels match byte for byte.
+
+* ``seq_hevc_compression``: ``SeqHevcCompression``, the reference's codec for a SEQUENCE of splat dictionaries (one ``.ply`` per
+  frame of a dynamic scene): ``reorganize`` / ``compress`` / ``decompress`` / ``deorganize`` with the reference's fields, every
+  attribute a video of grids, frame t predicted from the decoded frame t - 1 (or all-intra).  The reference shells out to
+  ffmpeg / libx265 here too; the payload is this project's own bitstream, the means are lossless.
+* ``plane_seq_codec``: ``plane_seq_encode`` / ``plane_seq_decode``, that payload on the GPU (the sequence kernels of
+  csrc/plane_codec.hip: the plane codec's stages with one lane owning a block through all frames, the reconstruction in registers,
+  the closed loop in one launch), defined by the numpy code ``plane_seq_codec_reference`` that the kernels match byte for byte.
 """
 from .decode import decode_to_dynamic_inputs, decode_to_rasterizer_inputs, kmeans_decode, kmeans_encode, morton_order, reorder_splats, sort_splats
 from ._container import png_read, png_write
@@ -57,6 +65,8 @@ from .entropy_coding_compression import EntropyCodingCompression
 from .stg_compression import STGPngCompression
 from .plane_codec import plane_decode, plane_encode
 from .hevc_compression import HevcCompression
+from .plane_seq_codec import plane_seq_decode, plane_seq_encode
+from .seq_hevc_compression import SeqHevcCompression
 from .grid_sort import grid_sort_order, sort_splats_grid
 from .kmeans import KMeans, kmeans_fit
 from .grid_codec import (
@@ -66,11 +76,12 @@ from .grid_codec import (
     inverse_log_transform,
     log_transform,
     quantize_grid,
+    quantize_grid_sequence,
 )
 
-__all__ = ["quantize_grid", "dequantize_grid", "compress_to_arrays", "decompress_from_arrays", "log_transform",
+__all__ = ["quantize_grid", "quantize_grid_sequence", "dequantize_grid", "compress_to_arrays", "decompress_from_arrays", "log_transform",
            "inverse_log_transform", "decode_to_rasterizer_inputs", "kmeans_decode", "kmeans_encode", "morton_order",
            "sort_splats", "reorder_splats", "PngCompression", "png_read", "png_write", "EntropyCodingCompression", "ans_encode",
            "ans_decode", "normalize_frequencies", "symbol_histogram", "grid_sort_order", "sort_splats_grid", "STGPngCompression",
            "decode_to_dynamic_inputs", "KMeans", "kmeans_fit", "gaussian_params", "gauss_ans_encode", "gauss_ans_decode",
-           "HevcCompression", "plane_encode", "plane_decode"]
+           "HevcCompression", "plane_encode", "plane_decode", "SeqHevcCompression", "plane_seq_encode", "plane_seq_decode"]

@@ -61,6 +61,26 @@ def quantize_grid(params: Tensor, n_sidelen: int, bits: int = 8, kbit: bool = Fa
 
 
 @torch.no_grad()
+def quantize_grid_sequence(params: Tensor, bits: int = 8) -> Tuple[List[Tensor], Dict[str, Any]]:
+    """``quantize_grid`` for a sequence of grids ``[T, side, side, ...]`` (the attribute videos of ``SeqHevcCompression``): ONE
+    min-max range per channel over frames and pixels (seq_hevc_compression.py:318-324), through the same ``gs_grid_quantize``.
+    Returns (planes, meta): uint8 [T, side, side, C] (never squeezed), one plane or (low, high) for 16 bits; meta has shape / dtype /
+    mins / maxs, and ``dequantize_grid(planes, meta)`` is the exact inverse."""
+    if not params.is_cuda:
+        raise RuntimeError("quantize_grid_sequence: the HIP path needs device tensors (no CPU fallback)")
+    assert bits in (8, 16) and params.dim() >= 3, (bits, params.shape)
+    grid = params.reshape(tuple(params.shape[:3]) + (-1,)).contiguous().float()
+    mins = torch.amin(grid, dim=(0, 1, 2)).contiguous()
+    maxs = torch.amax(grid, dim=(0, 1, 2)).contiguous()
+    lo = torch.empty(grid.shape, dtype=torch.uint8, device=grid.device)
+    hi = torch.empty(grid.shape, dtype=torch.uint8, device=grid.device) if bits == 16 else None
+    with torch.cuda.device(grid.device):
+        B.call("gs_grid_quantize", grid.numel(), grid.shape[-1], B.ptr(grid), B.ptr(mins), B.ptr(maxs), bits, B.ptr(lo), B.ptr(hi), _stream(grid))
+    meta = {"shape": list(params.shape), "dtype": str(params.dtype).split(".")[1], "mins": mins.tolist(), "maxs": maxs.tolist()}
+    return ([lo] if hi is None else [lo, hi]), meta
+
+
+@torch.no_grad()
 def dequantize_grid(planes: List[Tensor], meta: Dict[str, Any], device=None) -> Tensor:
     """Inverse of ``quantize_grid`` (= _decompress_png / _decompress_png_kbit / _decompress_png_16bit), bit-exact."""
     shape = list(meta["shape"])

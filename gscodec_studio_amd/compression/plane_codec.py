@@ -80,21 +80,15 @@ def _context_index(n: int, dev: torch.device) -> Tensor:
     return (torch.from_numpy(R.CTX * 256).to(dev)).repeat(n // 64)
 
 
-@torch.no_grad()
-def plane_encode(plane: Tensor, qp: int, stream_len: int = R.DEFAULT_STREAM_LEN, bits: int = R.DEFAULT_BITS) -> np.ndarray:
-    """Encode a uint8 device plane [H, W] or [H, W, ch] (ch = 1..4) at ``qp`` (0..51) -> the container as a numpy uint8 array,
-    byte-identical to ``plane_codec_reference.encode``.  Refused before any launch: a host tensor (RuntimeError), a wrong dtype,
-    shape, channel count, qp, stream length or resolution (ValueError)."""
-    plane = _check_plane(plane, qp)
-    if isinstance(stream_len, bool) or not isinstance(stream_len, (int, np.integer)) or not 1 <= stream_len <= R.MAX_STREAM_LEN:
-        raise ValueError(f"stream_len = {stream_len!r}")
-    if not R.A.MIN_BITS <= bits <= R.A.MAX_BITS:
-        raise ValueError(f"probability resolution of {bits} bits, supported: {R.A.MIN_BITS}..{R.A.MAX_BITS}")
-    h, w, ch = plane.shape
-    dev = plane.device
-    # levels_to_symbols: DC differences, fold, escapes
-    l = transform_levels(plane, qp).to(torch.int32)
-    l[:, 1:, 0] = l[:, 1:, 0] - l[:, :-1, 0]
+def encode_levels(levels: Tensor, dc_differences: bool, stream_len: int, bits: int):
+    """int16 device levels [rows, n_blocks, 64] -> (freq uint32 [15, 256], offsets, payload, escapes), all numpy: the module's
+    ``levels_to_symbols`` (DC differences along the blocks of a row when ``dc_differences``, fold, escapes), the per-context
+    histogram, the host-side tables and ``gs_plane_ans_encode``.  The plane codec calls it once, the plane-sequence codec once per
+    group of frames."""
+    dev = levels.device
+    l = levels.to(torch.int32)
+    if dc_differences:
+        l[:, 1:, 0] = l[:, 1:, 0] - l[:, :-1, 0]
     u = (2 * l.abs() - (l < 0).to(torch.int32)).reshape(-1)
     symbols = u.clamp(max=R.ESCAPE).to(torch.uint8)
     escapes = (u[torch.nonzero(u >= R.ESCAPE).reshape(-1)] - R.ESCAPE).cpu().numpy().astype(np.uint16)
@@ -110,6 +104,43 @@ def plane_encode(plane: Tensor, qp: int, stream_len: int = R.DEFAULT_STREAM_LEN,
 
     offsets, payload = encode_streams(sym2d, int(stream_len), int(B.query("gs_plane_ans_slot_bytes", int(stream_len), bits)), launch,
                                       "gs_plane_ans_encode", "1: a symbol with frequency 0, 2: slot too small")
+    return freq, offsets, payload, escapes
+
+
+def decode_levels(freq: np.ndarray, offsets: np.ndarray, payload: np.ndarray, escapes: np.ndarray, n: int, rows: int, dc_sums: bool,
+                  stream_len: int, bits: int, dev: torch.device, what: str) -> Tensor:
+    """The inverse of ``encode_levels`` on a parsed group of ``n`` symbols -> int16 device levels [rows, n / (64 rows), 64]:
+    ``gs_plane_ans_decode``, then the module's ``symbols_to_levels`` (escapes, unfold, DC sums when ``dc_sums``, clamp)."""
+    d_off, d_payload, symbols = decode_buffers(n, 1, stream_len, 1, offsets, payload, dev, what)
+    if d_payload.numel() == 0:  # unreachable behind parse_container (a stream has its 4 state bytes); the kernel takes no null
+        raise ValueError(f"{what}: empty payload")
+    cum = torch.from_numpy(R.cumulative16(freq).view(np.int16)).to(dev)
+    with torch.cuda.device(dev):
+        B.call("gs_plane_ans_decode", n, stream_len, bits, B.ptr(d_payload), d_payload.numel(), B.ptr(d_off), B.ptr(cum),
+               B.ptr(symbols), _stream(symbols))
+    u = symbols.reshape(-1).to(torch.int64)
+    esc = torch.from_numpy(np.concatenate([escapes.astype(np.int64), [0]])).to(dev)
+    is_esc = u == R.ESCAPE
+    rank = (torch.cumsum(is_esc, dim=0) - 1).clamp(min=0, max=esc.numel() - 1)
+    u = torch.where(is_esc, R.ESCAPE + esc[rank], u)
+    l = torch.where((u & 1) != 0, -((u + 1) >> 1), u >> 1).reshape(rows, -1, 64)
+    if dc_sums:
+        l[:, :, 0] = torch.cumsum(l[:, :, 0], dim=1)
+    return l.clamp(-R.LEVEL_MAX, R.LEVEL_MAX).to(torch.int16)
+
+
+@torch.no_grad()
+def plane_encode(plane: Tensor, qp: int, stream_len: int = R.DEFAULT_STREAM_LEN, bits: int = R.DEFAULT_BITS) -> np.ndarray:
+    """Encode a uint8 device plane [H, W] or [H, W, ch] (ch = 1..4) at ``qp`` (0..51) -> the container as a numpy uint8 array,
+    byte-identical to ``plane_codec_reference.encode``.  Refused before any launch: a host tensor (RuntimeError), a wrong dtype,
+    shape, channel count, qp, stream length or resolution (ValueError)."""
+    plane = _check_plane(plane, qp)
+    if isinstance(stream_len, bool) or not isinstance(stream_len, (int, np.integer)) or not 1 <= stream_len <= R.MAX_STREAM_LEN:
+        raise ValueError(f"stream_len = {stream_len!r}")
+    if not R.A.MIN_BITS <= bits <= R.A.MAX_BITS:
+        raise ValueError(f"probability resolution of {bits} bits, supported: {R.A.MIN_BITS}..{R.A.MAX_BITS}")
+    h, w, ch = plane.shape
+    freq, offsets, payload, escapes = encode_levels(transform_levels(plane, qp), True, int(stream_len), bits)
     return R.build_container(R.Header(bits, int(stream_len), int(qp), h, w, ch, escapes.size), freq, offsets, payload, escapes)
 
 
@@ -123,20 +154,5 @@ def plane_decode(blob, device="cuda", what: str = "the buffer") -> Tensor:
         raise RuntimeError("the plane codec runs on the GPU (no CPU fallback); plane_codec_reference.decode is the numpy form")
     head, freq, offsets, payload, escapes = R.parse_container(blob, what)
     n = 64 * head.channels * R.n_blocks(head.height, head.width)
-    d_off, d_payload, symbols = decode_buffers(n, 1, head.stream_len, 1, offsets, payload, dev, what)
-    if d_payload.numel() == 0:  # unreachable behind parse_container (a stream has its 4 state bytes); the kernel takes no null
-        raise ValueError(f"{what}: empty payload")
-    cum = torch.from_numpy(R.cumulative16(freq).view(np.int16)).to(dev)
-    with torch.cuda.device(dev):
-        B.call("gs_plane_ans_decode", n, head.stream_len, head.bits, B.ptr(d_payload), d_payload.numel(), B.ptr(d_off), B.ptr(cum),
-               B.ptr(symbols), _stream(symbols))
-    # symbols_to_levels: escapes, unfold, DC sums, clamp
-    u = symbols.reshape(-1).to(torch.int64)
-    esc = torch.from_numpy(np.concatenate([escapes.astype(np.int64), [0]])).to(dev)
-    is_esc = u == R.ESCAPE
-    rank = (torch.cumsum(is_esc, dim=0) - 1).clamp(min=0, max=esc.numel() - 1)
-    u = torch.where(is_esc, R.ESCAPE + esc[rank], u)
-    l = torch.where((u & 1) != 0, -((u + 1) >> 1), u >> 1).reshape(head.channels, -1, 64)
-    l[:, :, 0] = torch.cumsum(l[:, :, 0], dim=1)
-    levels = l.clamp(-R.LEVEL_MAX, R.LEVEL_MAX).to(torch.int16)
+    levels = decode_levels(freq, offsets, payload, escapes, n, head.channels, True, head.stream_len, head.bits, dev, what)
     return inverse_transform(levels, head.qp, head.height, head.width)

@@ -116,14 +116,44 @@ def _blocks(plane: np.ndarray) -> np.ndarray:
     return p.reshape(hp // 8, 8, wp // 8, 8, ch).transpose(4, 0, 2, 1, 3).reshape(ch, -1, 8, 8)
 
 
-def forward_levels(plane, qp: int) -> np.ndarray:
-    """uint8 plane -> int16 levels [ch, n_blocks, 64] in scan order: transform and quantiser."""
-    x = _blocks(check_plane(plane, qp))
-    t = rs(np.einsum("ux,cbyx->cbyu", M, x), 2)  # along x
-    c = rs(np.einsum("vy,cbyu->cbvu", M, t), 9)  # along y
+def transform_blocks(blocks: np.ndarray) -> np.ndarray:
+    """int64 [ch, n_blocks, 8 (y), 8 (x)] (pixels, or residuals in -255..255) -> coefficients int64 [ch, n_blocks, 8 (v), 8 (u)]:
+    the forward transform, |coefficient| <= 32640."""
+    t = rs(np.einsum("ux,cbyx->cbyu", M, blocks), 2)  # along x
+    return rs(np.einsum("vy,cbyu->cbvu", M, t), 9)  # along y
+
+
+def forward_blocks(blocks: np.ndarray, qp: int) -> np.ndarray:
+    """int64 [ch, n_blocks, 8, 8] -> int64 levels [ch, n_blocks, 64] in scan order: transform and quantiser (on sign and magnitude)."""
+    c = transform_blocks(blocks)
     qbits = 18 + qp // 6
     level = np.sign(c) * ((np.abs(c) * QS[qp % 6] + (171 << (qbits - 9))) >> qbits)
-    return level.reshape(level.shape[0], level.shape[1], 64)[:, :, SCAN].astype(np.int16)
+    return level.reshape(level.shape[0], level.shape[1], 64)[:, :, SCAN]
+
+
+def inverse_blocks(levels: np.ndarray, qp: int) -> np.ndarray:
+    """levels [ch, n_blocks, 64] in scan order (any values: clamped to +-32767) -> int64 [ch, n_blocks, 8 (y), 8 (x)]: dequantiser
+    and inverse transform up to the last ``rs(., 12)``, NOT clipped to 0..255 (a plane clips it; a residual is added to its
+    prediction first)."""
+    lv = np.asarray(levels)
+    level = np.zeros(lv.shape, np.int64)
+    level[:, :, SCAN] = np.clip(lv.astype(np.int64), -LEVEL_MAX, LEVEL_MAX)
+    c = np.clip((((level * LS[qp % 6]) << (qp // 6)) + 2) >> 2, -32768, 32767).reshape(lv.shape[0], -1, 8, 8)
+    t = np.clip(rs(np.einsum("vy,cbvu->cbyu", M, c), 7), -32768, 32767)  # along y
+    return rs(np.einsum("ux,cbyu->cbyx", M, t), 12)  # along x
+
+
+def _unblocks(x: np.ndarray, height: int, width: int) -> np.ndarray:
+    """The inverse of ``_blocks``: [ch, n_blocks, 8, 8] with values in 0..255 -> uint8 [H, W, ch], the padding cropped."""
+    ch = x.shape[0]
+    hb, wb = -(-height // 8), -(-width // 8)
+    full = x.reshape(ch, hb, wb, 8, 8).transpose(1, 3, 2, 4, 0).reshape(hb * 8, wb * 8, ch)
+    return np.ascontiguousarray(full[:height, :width]).astype(np.uint8)
+
+
+def forward_levels(plane, qp: int) -> np.ndarray:
+    """uint8 plane -> int16 levels [ch, n_blocks, 64] in scan order: transform and quantiser."""
+    return forward_blocks(_blocks(check_plane(plane, qp)), qp).astype(np.int16)
 
 
 def inverse_levels(levels, qp: int, height: int, width: int) -> np.ndarray:
@@ -132,14 +162,7 @@ def inverse_levels(levels, qp: int, height: int, width: int) -> np.ndarray:
     ch = lv.shape[0]
     if lv.ndim != 3 or lv.shape[1:] != (n_blocks(height, width), 64) or not 1 <= ch <= MAX_CHANNELS or not 0 <= qp <= MAX_QP:
         raise ValueError(f"levels {lv.shape} do not belong to a {height} x {width} plane of 1..{MAX_CHANNELS} channels at qp {qp}")
-    level = np.zeros(lv.shape, np.int64)
-    level[:, :, SCAN] = np.clip(lv.astype(np.int64), -LEVEL_MAX, LEVEL_MAX)
-    c = np.clip((((level * LS[qp % 6]) << (qp // 6)) + 2) >> 2, -32768, 32767).reshape(ch, -1, 8, 8)
-    t = np.clip(rs(np.einsum("vy,cbvu->cbyu", M, c), 7), -32768, 32767)  # along y
-    x = np.clip(rs(np.einsum("ux,cbyu->cbyx", M, t), 12), 0, 255)  # along x
-    hb, wb = -(-height // 8), -(-width // 8)
-    full = x.reshape(ch, hb, wb, 8, 8).transpose(1, 3, 2, 4, 0).reshape(hb * 8, wb * 8, ch)
-    return np.ascontiguousarray(full[:height, :width]).astype(np.uint8)
+    return _unblocks(np.clip(inverse_blocks(lv, qp), 0, 255), height, width)
 
 
 def reconstruct(plane, qp: int) -> np.ndarray:
@@ -206,6 +229,22 @@ def _pack_tables(freq: np.ndarray) -> bytes:
     return b"".join(out)
 
 
+def _unpack_tables(buf: np.ndarray, pos: int, bits: int, what: str, n_tables: int = N_CONTEXTS) -> Tuple[np.ndarray, int]:
+    """The inverse of ``_pack_tables`` at ``buf[pos:]`` -> (freq uint32 [n_tables, 256], the position behind the tables); ValueError
+    for a table that is truncated, empty, out of order, holds a zero or does not sum to 2^bits."""
+    freq = np.zeros((n_tables, 256), np.uint32)
+    for c in range(n_tables):
+        count = int(buf[pos:pos + 2].view("<u2")[0]) if pos + 2 <= buf.size else -1
+        if not 1 <= count <= 256 or pos + 2 + 3 * count > buf.size:
+            raise ValueError(f"{what}: truncated or empty frequency table of context {c}")
+        rec = buf[pos + 2:pos + 2 + 3 * count].view([("s", "u1"), ("f", "<u2")])
+        pos += 2 + 3 * count
+        if np.any(np.diff(rec["s"].astype(np.int64)) <= 0) or np.any(rec["f"] == 0) or int(rec["f"].astype(np.int64).sum()) != 1 << bits:
+            raise ValueError(f"{what}: the frequency table of context {c} is out of order, holds a zero or does not sum to 2^{bits}")
+        freq[c, rec["s"]] = rec["f"]
+    return freq, pos
+
+
 def build_container(head: Header, freq: np.ndarray, offsets: np.ndarray, payload: np.ndarray, escapes: np.ndarray) -> np.ndarray:
     """Header + tables + offset table + payload + escapes -> the file's bytes (uint8 array)."""
     front = _HEADER.pack(MAGIC, VERSION, head.bits, head.stream_len, head.qp, head.height, head.width, head.channels,
@@ -231,17 +270,7 @@ def parse_container(blob, what: str = "the buffer") -> Tuple[Header, np.ndarray,
         raise ValueError(f"{what}: bad plane header (P = {bits}, S = {stream_len}, qp = {qp}, ch = {channels})")
     if height * width < 1 or 64 * channels * n_blocks(height, width) >= 1 << 31:
         raise ValueError(f"{what}: bad plane header (H = {height}, W = {width})")
-    pos = _HEADER.size
-    freq = np.zeros((N_CONTEXTS, 256), np.uint32)
-    for c in range(N_CONTEXTS):
-        count = int(buf[pos:pos + 2].view("<u2")[0]) if pos + 2 <= buf.size else -1
-        if not 1 <= count <= 256 or pos + 2 + 3 * count > buf.size:
-            raise ValueError(f"{what}: truncated or empty frequency table of context {c}")
-        rec = buf[pos + 2:pos + 2 + 3 * count].view([("s", "u1"), ("f", "<u2")])
-        pos += 2 + 3 * count
-        if np.any(np.diff(rec["s"].astype(np.int64)) <= 0) or np.any(rec["f"] == 0) or int(rec["f"].astype(np.int64).sum()) != 1 << bits:
-            raise ValueError(f"{what}: the frequency table of context {c} is out of order, holds a zero or does not sum to 2^{bits}")
-        freq[c, rec["s"]] = rec["f"]
+    freq, pos = _unpack_tables(buf, _HEADER.size, bits, what)
     n_streams = -(-64 * channels * n_blocks(height, width) // stream_len)
     offsets, rest = A._split_container(buf, pos, n_streams, what)
     end = int(offsets[-1])

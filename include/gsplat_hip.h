@@ -55,7 +55,8 @@ extern "C" {
  * gs_gauss_ans_encode_bytes, gs_gauss_ans_params, gs_gauss_ans_encode, gs_gauss_ans_decode), and the SparseAdam entries
  * (gs_sparse_adam_desc, gs_sparse_adam_multi, gs_sparse_adam_desc_layout), and the colour-matching entries
  * (gs_color_correct_pass, gs_color_correct_solve, gs_color_correct_record_doubles, gs_color_correct_rcond_log2), and the plane codec's (gs_plane_transform_fwd / _inv,
- * gs_plane_ans_slot_bytes, gs_plane_ans_encode, gs_plane_ans_decode). */
+ * gs_plane_ans_slot_bytes, gs_plane_ans_encode, gs_plane_ans_decode), and the plane-sequence codec's (gs_plane_seq_fwd,
+ * gs_plane_seq_inv). */
 #define GS_ABI_VERSION 6
 
 /* reference: gsplat/cuda/include/bindings.h:34-38 (enum CameraModelType) */
@@ -1066,6 +1067,26 @@ int32_t gs_plane_ans_encode(uint64_t N, uint32_t S, uint32_t P, const uint8_t *s
                             uint64_t scratch_bytes, uint32_t *lengths, uint32_t *states, uint32_t *status, gs_stream_t stream);
 int32_t gs_plane_ans_decode(uint64_t N, uint32_t S, uint32_t P, const uint8_t *payload, uint64_t payload_bytes,
                             const int64_t *offsets, const uint16_t *cum, uint8_t *symbols, gs_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * Transform-coded plane SEQUENCES (plane_codec.hip): the payload of SeqHevcCompression's <name>.bin -- T planes uint8 [T, H, W, ch]
+ * with temporal prediction, in place of the reference's ffmpeg / libx265 call on a video of attribute grids
+ * (gsplat/compression/seq_hevc_compression.py).  The format's definition is
+ * gscodec_studio_amd/compression/plane_seq_codec_reference.py; the stages (transform, quantiser, dequantiser, inverse, scan) are the
+ * plane codec's above, integer arithmetic only, the kernels' results equal the module element for element.  Frame t is an I frame
+ * when t % gop == 0 (its levels are gs_plane_transform_fwd's), otherwise a P frame: the levels of the difference between the
+ * edge-replicated source block and the padded reconstruction of frame t - 1 (all 64 pixels of every block, values 0..255), which
+ * then becomes clip(reconstruction + inverse(levels), 0, 255).  No motion search and no spatial prediction: a block depends on the
+ * co-located block alone, so ONE LANE OWNS ONE 8 x 8 BLOCK of one channel THROUGH ALL T FRAMES, with the reconstruction in
+ * registers (64 bytes packed into 16 words); one launch runs the whole closed loop.  levels int16 [T, ch, n_blocks, 64], 16-byte
+ * aligned, T ch n_blocks 64 < 2^31.
+ *
+ * gs_plane_seq_fwd: planes -> levels, and the decoder's frames into recon uint8 [T, H, W, ch] when recon is not NULL (cropped).
+ * gs_plane_seq_inv: levels (any values: clamped to +-32767) -> planes uint8 [T, H, W, ch]: the second half of gs_plane_seq_fwd. */
+int32_t gs_plane_seq_fwd(uint32_t T, uint32_t gop, uint32_t H, uint32_t W, uint32_t ch, uint32_t qp, const uint8_t *planes,
+                         int16_t *levels, uint8_t *recon /* or NULL */, gs_stream_t stream);
+int32_t gs_plane_seq_inv(uint32_t T, uint32_t gop, uint32_t H, uint32_t W, uint32_t ch, uint32_t qp, const int16_t *levels,
+                         uint8_t *planes, gs_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * Grid sort (grid_sort.hip): the order of the splats on the S x S image grid of the PNG codecs that makes every attribute image
